@@ -14,10 +14,14 @@ A step is one process() call over one batch of `--items` samples; the stream sta
 from step to step exactly as in the reference block.  With N GPUs every rank runs its own
 channel (the path shards by channel, no data-path collective): weak scaling.
 
+A plain run sets up, warms up, times exactly --steps steps (one region), writes the last step's outputs when
+--dump-outputs DIR is given, and prints the line.  The sub-records and legs below (roofline, cpu_baseline, config2 /
+config3, config5, host_stream, sparse) are measured with --full only.
+
 Extra objects on the JSON line:
   repeats / values / value_min / value_max
-                the timed region (exactly --steps steps between barriers) is run --repeats times back to back;
-                `value` and `ms_per_step` are the median region's.
+                the timed region (exactly --steps steps between barriers) is run --repeats times back to back
+                (default 1, 5 with --full); `value` and `ms_per_step` are the median region's.
   roofline      the dominant kernel (k_correlate_w64) timed alone with HIP events on the launch
                 stream; achieved = 8 B/sample (HBM read, SURVEY.md 8(d) read-only variant)
                 x samples per launch / mean launch time, against the 8 TB/s HBM peak; per_bins: the same for
@@ -636,9 +640,11 @@ def config5(args):
     # oracle alike: 305 tags instead of 8 on 480k samples) fires on plain data
     sd = pkg.SyncwordDetection(rrc, SYNCWORD, bpsk, -BINS, BINS, fft_size=nfft, power_threshold=30.0, max_items=n)
     cap = 1 << 16
+    last = {}
 
     def step():
         st, _, tags, nd = sd.process_bulk(x, want_output=False, tags_cap=cap)
+        last.update(status=st, tags=tags, consumed=nd)
         return nd, tags.size
 
     for _ in range(args.warmup):
@@ -652,6 +658,8 @@ def config5(args):
         n_tags += nt
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs)
     # the 1025-tap filter leg, timed beside it (symbols in, 4 samples per symbol out)
     for _ in range(2):
         fir.process_bulk(sym)
@@ -1318,6 +1326,77 @@ def channels64_leg(pkg, dist, device, rank, world, rrc, steps, warmup, repeats, 
             **({"latency": latency} if latency else {})}
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+DUMP_WHOLE_BYTES = 1 << 20  # arrays up to this size are always written whole
+
+
+def _dump_arrays(prefix, v, out):
+    """the arrays of a step's result, flattened to names: dicts and lists by key / position, the fields of a record
+    array one by one; strings and None are left out"""
+    if v is None or isinstance(v, (str, bytes)):
+        return
+    if isinstance(v, dict):
+        for k, e in v.items():
+            _dump_arrays(f"{prefix}_{k}" if prefix else str(k), e, out)
+    elif isinstance(v, (list, tuple)):
+        for i, e in enumerate(v):
+            _dump_arrays(f"{prefix}_{i}" if prefix else str(i), e, out)
+    elif isinstance(v, np.ndarray) and v.dtype.names:
+        for f in v.dtype.names:
+            out[f"{prefix}_{f}"] = v[f]
+    elif isinstance(v, (torch.Tensor, np.ndarray)):
+        out[prefix] = v
+    else:
+        out[prefix] = np.asarray(v)
+
+
+def _dump_dtype(dtype):
+    """float32 for float32 / complex64 (as [..., 2]) and integers of up to 16 bits, float64 for the rest"""
+    if isinstance(dtype, torch.dtype):
+        dtype = torch.empty(0, dtype=dtype).numpy().dtype
+    if dtype.kind == "c":
+        return np.float32 if dtype.itemsize == 8 else np.float64
+    if dtype == np.float32 or dtype == np.float16 or (dtype.kind in "iub" and dtype.itemsize <= 2):
+        return np.float32
+    return np.float64
+
+
+def dump_outputs(res, directory):
+    """--dump-outputs: what the timed path's last step returned, as directory/<name>.npy.  Arrays of up to
+    DUMP_WHOLE_BYTES are written whole; the larger ones share what is left of DUMP_BYTES, each as a sample of its rows
+    drawn with a fixed seed (sorted; the row numbers beside it as <name>_sample_index.npy, float64)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    _dump_arrays("", res, arrays)
+    plan = {}
+    for name, a in arrays.items():
+        dt = np.dtype(_dump_dtype(a.dtype))
+        cplx = a.is_complex() if isinstance(a, torch.Tensor) else a.dtype.kind == "c"
+        rows = a.shape[0] if a.ndim else 1
+        row_elems = int(np.prod(a.shape[1:])) * (2 if cplx else 1)
+        plan[name] = (dt, rows, dt.itemsize * row_elems)
+    small = [n for n, (_, rows, rb) in plan.items() if rows * rb <= DUMP_WHOLE_BYTES]
+    large = [n for n in plan if n not in small]
+    left = DUMP_BYTES - sum(plan[n][1] * plan[n][2] for n in small)
+    share = left // max(len(large), 1)
+    for name, a in arrays.items():
+        dt, rows, rb = plan[name]
+        if name in large and rows * rb > share:
+            k = share // (rb + 8)  # the row numbers are written too
+            idx = np.sort(np.random.default_rng(0).choice(rows, size=k, replace=False))
+            if isinstance(a, torch.Tensor):
+                a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+            else:
+                a = a[idx]
+            np.save(os.path.join(directory, name + "_sample_index.npy"), idx.astype(np.float64))
+        if isinstance(a, torch.Tensor):
+            a = torch.view_as_real(a) if a.is_complex() else a
+            a = a.cpu().numpy()
+        elif a.dtype.kind == "c":
+            a = np.stack([a.real, a.imag], axis=-1)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=dt))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1327,9 +1406,16 @@ def main():
                     help="samples per step per GPU (per channel with --channels).  Default: 2^28 (SURVEY.md 8(d) config 2: "
                          "2^28 samples resident in HBM per pass), 2^22 per channel with --channels (config 3), 2^26 with "
                          "--config 5")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (exactly --steps steps between two barriers) is run this many times back to "
-                         "back; `value` is the median region, min / max beside it")
+                         "back; `value` is the median region, min / max beside it.  Default: 1, and 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the in-run PMC traffic passes, the configs[2] / [3] "
+                         "channels leg, the configs[4] / host-stream / packet-density sub-records, the roofline legs and "
+                         "the CPU baseline (each can still be left out with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB in all: a fixed, seeded sample of the rows of larger arrays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-channels-leg", action="store_true",
                     help="skip the 64-channels-per-GPU sub-record (configs[2] at N = 1, configs[3] at N > 1) that follows "
@@ -1384,7 +1470,7 @@ def main():
                     help="do not measure roofline.traffic in this run (two rocprofv3 --pmc passes over the correlator alone, "
                          "about 20 s, before anything else): the committed PMC file is quoted instead")
     ap.add_argument("--sparse-leg-only", action="store_true",
-                    help="(what the default run starts as a child process) the packet-density sub-record alone, printed as JSON")
+                    help="(what a --full run starts as a child process) the packet-density sub-record alone, printed as JSON")
     ap.add_argument("--sparse-streams", default=",".join(SPARSE_STREAMS),
                     help="with --sparse-leg-only: which of its streams (comma-separated)")
     ap.add_argument("--selfcheck", action="store_true",
@@ -1394,6 +1480,8 @@ def main():
                     help="launcher / aggregation check without a GPU: every rank joins a gloo group, aggregates "
                          "fixed numbers and rank 0 prints the line (tests/test_distributed_cpu.py)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.items is None:
         args.items = 1 << 26 if args.config == 5 else (1 << 22 if args.channels > 1 else 1 << 28)
     world_env = os.environ.get("WORLD_SIZE")
@@ -1418,9 +1506,11 @@ def main():
     if args.lookahead_depth is None:
         args.lookahead_depth = 2
     # roofline.traffic, measured in this run: child processes under rocprofv3, BEFORE this process makes its first GPU call
-    # (N = 1, the default headline workload only; profiling runs of bench.py itself pass --no-pmc-traffic or --no-per-bins)
+    # (--full, N = 1, the default headline workload only; profiling runs of bench.py itself pass --no-pmc-traffic or
+    # --no-per-bins)
     global MEASURED_TRAFFIC
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.channels == 1 and not args.no_pmc_traffic and not args.no_per_bins
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.channels == 1 and not args.no_pmc_traffic
+            and not args.no_per_bins
             and not args.no_cpu_baseline and not (args.soft_bits or args.decode_headers or args.detector_only or args.no_pipeline)):
         MEASURED_TRAFFIC = measure_traffic_in_run(args.items)
     # three host threads drive the three pipeline stages and spend most of their time inside the
@@ -1543,6 +1633,7 @@ def main():
 
     step_no = 0
     announced_upto = 0
+    last_res = None  # what the latest finished batch returned to its caller (--dump-outputs)
     hdr_stats = {"decoded": 0, "valid_1500": 0, "mismatches": 0, "packets_crc_ok": 0, "packets_crc_failed": 0}
 
     def note_headers(res):
@@ -1561,7 +1652,7 @@ def main():
         """one pass over one window; `left`: how many further steps follow in this region (the
         look-ahead never reaches beyond it, so that exactly `steps` correlator launches fall
         inside the timed region)"""
-        nonlocal out_keep, step_no, announced_upto
+        nonlocal out_keep, step_no, announced_upto, last_res
         w, history = windows[step_no % 2]
         w_next = None
         if not args.no_lookahead:
@@ -1583,12 +1674,14 @@ def main():
                 if res is None:
                     return 0, 0
             out_keep = res[-1]["symbols"]
+            last_res = res
             return sum(r["consumed"] for r in res), sum(r["tags"].size for r in res)
         if args.detector_only:
             with torch.cuda.stream(rx._streams[0]):
                 st, out, tags, n = sd.process_bulk(w, want_output=True, tags_cap=max(64, 2 * n_pkt + 64),
                                                    next_x=w_next)
             out_keep = out
+            last_res = {"status": st, "output": out, "tags": tags, "consumed": n}
             if args.channels > 1:
                 return n * args.channels, sum(t.size for t in tags)
             return n, tags.size
@@ -1597,16 +1690,18 @@ def main():
         if res is None:  # pipelined: first call has no finished batch yet
             return 0, 0
         out_keep = res["symbols"]
+        last_res = res
         note_headers(res)
         return res["consumed"], res["tags"].size
 
     def drain():
-        nonlocal out_keep
+        nonlocal out_keep, last_res
         if multi is not None and not args.python_pipeline and not args.no_pipeline:
             n = nt = 0
             while multi.in_flight():
                 res = multi.collect()
                 out_keep = res[-1]["symbols"]
+                last_res = res
                 n += sum(r["consumed"] for r in res)
                 nt += sum(r["tags"].size for r in res)
             return n, nt
@@ -1615,6 +1710,7 @@ def main():
         n = nt = 0
         for res in rx.flush():
             out_keep = res["symbols"]
+            last_res = res
             note_headers(res)
             n += res["consumed"]
             nt += res["tags"].size
@@ -1658,11 +1754,15 @@ def main():
     dt, total, n_tags = by_rate[len(by_rate) // 2]  # the median region is the number of record
     median_region = regions.index(by_rate[len(by_rate) // 2])
     region_rates = [round(r[1] / r[0] / 1e6, 2) for r in regions]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_res, args.dump_outputs)
 
+    # ---- everything below is --full only: the sub-records, the roofline legs and the CPU baseline
     # ---- 64 channels per GPU (configs[2] at N = 1, configs[3] = 64 x N channels at N > 1), after the headline
     # region, in the same run; only for the default headline workload
     channels_leg = None
-    headline = native and not (args.soft_bits or args.decode_headers or args.no_pipeline or args.no_lookahead or args.copy_delay)
+    headline = args.full and native and not (args.soft_bits or args.decode_headers or args.no_pipeline or args.no_lookahead
+                                             or args.copy_delay)
     if headline and not args.no_channels_leg:
         rx = None  # the headline receiver is done: its stage threads and streams go before the next leg starts
         channels_leg = channels64_leg(pkg, dist, device, rank, world, rrc, steps=max(args.steps, 50), warmup=6,
@@ -1690,7 +1790,7 @@ def main():
     # ---- roofline of the dominant kernel: HIP events on the stream the kernel runs on
     roofline = None
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = 10
         # HIP events must sit on the stream the kernel is launched on: a detector handle created
         # under that stream (the native receiver keeps its own detector inside the library, so the

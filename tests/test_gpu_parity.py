@@ -3627,7 +3627,8 @@ def test_bench_two_ranks_share_the_gpu_through_the_whole_n_gt_1_path(launcher):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--repeats", "2", "--items", str(1 << 24), "--no-cpu-baseline"]
+    args = ["--gpus", "2", "--steps", "3", "--warmup", "2", "--repeats", "2", "--items", str(1 << 24), "--no-cpu-baseline",
+            "--full"]
     env = dict(os.environ, GR4PM_BENCH_SHARED_DEVICE_TEST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -3676,7 +3677,7 @@ def test_bench_eight_ranks_share_the_gpu_with_the_config3_ring_shape():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     n3 = 1 << 16
     args = ["--gpus", "8", "--steps", "2", "--warmup", "1", "--repeats", "1", "--items", str(1 << 22), "--no-cpu-baseline",
-            "--config3-items", str(n3)]
+            "--config3-items", str(n3), "--full"]
     env = dict(os.environ, GR4PM_BENCH_SHARED_DEVICE_TEST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)

@@ -396,7 +396,7 @@ def test_reference_syncword_detection_header_on_the_stub_agrees_with_the_oracle(
             # with a 9000-item chunk the block takes 4 strides + one FFT length per call, the oracle everything at once:
             # the tail the reference leaves unconsumed may be longer, what it did produce must agree
             assert c == p and p <= want.size and want.size - p < 9000 + 2048
-            assert np.array_equal(_bits(y), _bits(want[:p]))
+            assert _same(y, want[:p])
             k = int(np.sum(want_tags["index"] < p))
             assert t.size == k and np.array_equal(t["index"], want_tags["index"][:k])
             for f in ("amplitude", "phase", "freq", "freq_bin", "noise_power", "esn0_db", "time_est"):
@@ -457,13 +457,40 @@ def test_device_arena_with_the_two_ends_of_an_edge_in_two_threads(tmp_path):
 REFERENCE_INCLUDE = "/root/reference/blocks/include"
 
 
+# What the binary below wrote for every (case, chunk) of the two tests that use it: digests of its outputs, the tag
+# records themselves.  Where the reference tree is absent the tests compare the oracle against these.  Regenerate with
+# GR4PM_RECORD_REF_GOLDEN=1 on a machine that has the reference tree.
+REF_GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_headers_on_stub.json")
+
+
+class _Digest:
+    """a block output known by its size and SHA-256 only (compared through _same)"""
+
+    def __init__(self, n, sha256):
+        self.n, self.sha256 = n, sha256
+
+
+def _sha256(a):
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _same(y, want):
+    """bit-for-bit equality of a block output with the oracle's"""
+    if isinstance(y, _Digest):
+        return y.n == want.size and y.sha256 == _sha256(_bits(want))
+    return np.array_equal(_bits(y), _bits(want))
+
+
 @pytest.fixture(scope="module")
 def ref_check(tmp_path_factory):
-    """tests/ref_headers_check.cpp: the reference's OWN block headers compiled against tests/gr4_stub (only where
-    /root/reference exists: the build container).  That it compiles is the first half of the check: the stand-in
-    declares the API surface the reference uses."""
+    """tests/ref_headers_check.cpp: the reference's OWN block headers compiled against tests/gr4_stub (where the
+    reference tree exists: the build container).  That it compiles is the first half of the check: the stand-in
+    declares the API surface the reference uses.  Elsewhere: the outputs it recorded (REF_GOLDEN)."""
     if not os.path.isdir(REFERENCE_INCLUDE):
-        pytest.skip("the reference tree is not on this machine")
+        import json
+        with open(REF_GOLDEN) as f:
+            return json.load(f)
     exe = tmp_path_factory.mktemp("refcheck") / "ref_headers_check"
     subprocess.check_call(["g++", "-std=c++23", "-O2", "-ffp-contract=off", "-I", os.path.join(ROOT, "tests", "gr4_stub"),
                            "-I", REFERENCE_INCLUDE, "-I", os.path.join(ROOT, "tests"), "-o", str(exe),
@@ -474,17 +501,42 @@ def ref_check(tmp_path_factory):
 
 
 def _run_ref(exe, tmp_path, case, x, tags=None, chunk=4000):
+    """(output, output tags, consumed, produced) of one case of the binary; from the recorded digests when `exe` is
+    REF_GOLDEN's contents (the output is then a _Digest)"""
+    import base64
+    import json
+    x = np.ascontiguousarray(x, dtype=np.complex64)
+    tags = None if tags is None else np.ascontiguousarray(tags, dtype=orc.TAG_DTYPE)
+    key = f"{case}/{chunk}"
+    stimulus = _sha256(x) + ("" if tags is None else _sha256(tags))
+    if isinstance(exe, dict):
+        rec = exe[key]
+        assert rec["stimulus_sha256"] == _sha256(np.frombuffer(stimulus.encode(), np.uint8)), f"{key}: stimulus changed"
+        out_tags = np.frombuffer(base64.b64decode(rec["tags"]), dtype=REC).copy()
+        return _Digest(rec["n"], rec["sha256"]), out_tags, rec["consumed"], rec["produced"]
     xin = tmp_path / f"{case}.in.c64"
-    np.ascontiguousarray(x, dtype=np.complex64).tofile(xin)
+    x.tofile(xin)
     tpath = "-"
     if tags is not None:
         tpath = str(tmp_path / f"{case}.tags.bin")
-        np.ascontiguousarray(tags, dtype=orc.TAG_DTYPE).tofile(tpath)
+        tags.tofile(tpath)
     prefix = str(tmp_path / case)
     subprocess.check_call([exe, case, str(xin), tpath, prefix, str(chunk)], stdout=subprocess.DEVNULL)
     out = np.fromfile(prefix + ".out.c64", dtype=np.complex64)
     consumed, produced = np.fromfile(prefix + ".counts.bin", dtype=np.uint64)
-    return out, np.fromfile(prefix + ".out_tags.bin", dtype=REC), int(consumed), int(produced)
+    out_tags = np.fromfile(prefix + ".out_tags.bin", dtype=REC)
+    if os.environ.get("GR4PM_RECORD_REF_GOLDEN"):
+        rec = {}
+        if os.path.exists(REF_GOLDEN):
+            with open(REF_GOLDEN) as f:
+                rec = json.load(f)
+        rec[key] = {"stimulus_sha256": _sha256(np.frombuffer(stimulus.encode(), np.uint8)), "n": int(out.size),
+                    "sha256": _sha256(_bits(out)), "tags": base64.b64encode(out_tags.tobytes()).decode(),
+                    "consumed": int(consumed), "produced": int(produced)}
+        with open(REF_GOLDEN, "w") as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
+            f.write("\n")
+    return out, out_tags, int(consumed), int(produced)
 
 
 def _bits(a):
@@ -515,12 +567,12 @@ def test_reference_headers_on_the_stub_agree_with_the_oracle(ref_check, tmp_path
     for chunk in (4000, 997):
         # Rotator (processOne)
         y, _, c, p = _run_ref(ref_check, tmp_path, "rotator", x, chunk=chunk)
-        assert c == p == n and np.array_equal(_bits(y), _bits(orc.rotator(x, np.float32(0.1))))
+        assert c == p == n and _same(y, orc.rotator(x, np.float32(0.1)))
         # CoarseFrequencyCorrection, delay 26, several set_freq tags incl. two closer than the delay
         tags = _detection_tags([0, 5000, 5010, 12000, 20001, 29990], 1)
         y, t, c, p = _run_ref(ref_check, tmp_path, "cfc", x, tags, chunk)
         want = orc.coarse_frequency_correction(x, tags["index"], tags["freq"], delay=26)
-        assert c == p == n and np.array_equal(_bits(y), _bits(want))
+        assert c == p == n and _same(y, want)
         assert np.array_equal(t["index"], tags["index"])                    # forwarded by the default policy
         # SymbolFilter with tags: every clock-phase case of symbol_filter.hpp:130-206
         idx = [0, 1001, 2002, 2500, 3000, 3003, 4444, 5557, 7000, 7001, 9998, 20000]
@@ -531,7 +583,7 @@ def test_reference_headers_on_the_stub_agree_with_the_oracle(ref_check, tmp_path
         pfb = orc.rrc_taps(32.0 / float(norm), 128.0, 1.0, 0.35, 32 * 4 * 11)[:-1]
         y, t, c, p = _run_ref(ref_check, tmp_path, "symbol_filter", x, tags, chunk)
         want, want_tags, want_cons = orc.symbol_filter(x, pfb, 32, 4, 44, tags=tags)
-        assert c == want_cons and p == want.size and np.array_equal(_bits(y), _bits(want))
+        assert c == want_cons and p == want.size and _same(y, want)
         assert np.array_equal(t["index"], want_tags["index"])
         det = want_tags["flags"] == 1
         for k in ("amplitude", "phase", "time_est"):
@@ -541,19 +593,19 @@ def test_reference_headers_on_the_stub_agree_with_the_oracle(ref_check, tmp_path
         tags = _detection_tags([0, 3000, 3001, 17000], 3)
         y, _, c, p = _run_ref(ref_check, tmp_path, "costas", x, tags, chunk)
         want = orc.costas_loop(x, "QPSK", 0.01, tags["index"], tags["phase"])
-        assert c == p == n and np.array_equal(_bits(y), _bits(want))
+        assert c == p == n and _same(y, want)
         # InterpolatingFirFilter x4 with the 45-tap RRC
         y, _, c, p = _run_ref(ref_check, tmp_path, "interp_fir", x[:8000], chunk=chunk)
         want = orc.interpolating_fir(x[:8000], 4, orc.rrc_taps(1.0, 4.0, 1.0, 0.35, 44))
-        assert c == 8000 and np.array_equal(_bits(y), _bits(want))
+        assert c == 8000 and _same(y, want)
         # PfbArbResampler: float rate 1 + 1.2e-6 (TRate = float) and 1.1234 (TRate = double)
         pkg_taps = np.fromfile(os.path.join(ROOT, "gr4-packet-modem_amd", "data", "pfb_arb_taps.f32"), dtype=np.float32)
         for case, rate, dbl in (("arb_float", float(np.float32(1.0) + np.float32(1.2e-6)), False), ("arb_double", 1.1234, True)):
             y, _, c, p = _run_ref(ref_check, tmp_path, case, x, chunk=chunk)
             want, wcons = orc.pfb_arb_resampler(x, rate, pkg_taps, 32, rate_is_double=dbl, out_cap=8 * n + 4096)
-            assert c == wcons and p == want.size and np.array_equal(_bits(y), _bits(want)), case
+            assert c == wcons and p == want.size and _same(y, want), case
         # SyncwordWipeoff
         sw = np.array([(-1.0 if (i * 7 % 3) else 1.0) for i in range(64)], dtype=np.float32)
         tags = _detection_tags([10, 500, 6000, 29000], 4)
         y, _, c, p = _run_ref(ref_check, tmp_path, "wipeoff", x, tags, chunk)
-        assert c == p == n and np.array_equal(_bits(y), _bits(orc.syncword_wipeoff(x, sw, tags["index"])))
+        assert c == p == n and _same(y, orc.syncword_wipeoff(x, sw, tags["index"]))

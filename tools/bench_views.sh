@@ -2,7 +2,7 @@
 # every view of bench.py on one box, back to back (profiles/r<N>_bench_views.txt); run on the GPU box
 OUT=${1:-gpurun_out/r3_views}
 mkdir -p $OUT
-run() { name=$1; shift; timeout 600 python bench.py --no-cpu-baseline --no-channels-leg --repeats 3 "$@" 2>/dev/null | tail -1 > $OUT/$name.json; python3 - $OUT/$name.json "$name" <<'PY'
+run() { name=$1; shift; timeout 600 python bench.py --full --no-cpu-baseline --no-channels-leg --repeats 3 "$@" 2>/dev/null | tail -1 > $OUT/$name.json; python3 - $OUT/$name.json "$name" <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[1])); r=d.get("roofline") or {}

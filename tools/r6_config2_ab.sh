@@ -5,6 +5,6 @@ R=$GRAFT_REPO_ROOT
 for rep in 1 2 3 4 5; do
 for cfg in "GR4PM_LIB=$R/tools/ab/libgr4pm_hip_before_tail.so" "GR4PM_ROT_GENERIC=1" "X=1"; do
   echo -n "[$cfg] "
-  env $cfg python3 $R/bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-config5-leg --no-host-stream-leg --no-per-bins --no-sparse-leg --no-pmc-traffic 2>/dev/null | tail -1 | python3 -c "
+  env $cfg python3 $R/bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --no-config5-leg --no-host-stream-leg --no-per-bins --no-sparse-leg --no-pmc-traffic 2>/dev/null | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d['config2']; print('config 2', c['value'], c['ms_per_step'], c.get('value_min'), c.get('value_max'), 'warm regions', c.get('warm_regions'))"
 done; done

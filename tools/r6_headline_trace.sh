@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${1:-r6_headline_trace}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof
-COMMON="--no-cpu-baseline --no-channels-leg --no-config5-leg --no-host-stream-leg --no-sparse-leg --no-per-bins --repeats 1"
+COMMON="--full --no-cpu-baseline --no-channels-leg --no-config5-leg --no-host-stream-leg --no-sparse-leg --no-per-bins --repeats 1"
 rocprofv3 --kernel-trace --output-format csv -d $O/prof -- python3 $R/bench.py --steps 30 --warmup 5 $COMMON > $O/run.txt 2>&1
 python3 -c "
 import json

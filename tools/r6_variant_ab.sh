@@ -5,6 +5,6 @@
 R=$GRAFT_REPO_ROOT
 for rep in 1 2; do
 for v in -1 65536 0; do
-  GR4PM_W64_VARIANT=$v python3 $R/bench.py --no-cpu-baseline --no-channels-leg --no-config5-leg --no-host-stream-leg --no-per-bins --no-sparse-leg --no-pmc-traffic --repeats 3 2>/dev/null | tail -1 | python3 -c "
+  GR4PM_W64_VARIANT=$v python3 $R/bench.py --full --no-cpu-baseline --no-channels-leg --no-config5-leg --no-host-stream-leg --no-per-bins --no-sparse-leg --no-pmc-traffic --repeats 3 2>/dev/null | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('variant $v', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 done; done
