@@ -130,6 +130,11 @@ class ScramblerParams(C.Structure):
                 ("item_kind", C.c_int), ("stream", C.c_void_p)]
 
 
+class PacketTransmitterParams(C.Structure):
+    _fields_ = [("samples_per_symbol", C.c_size_t), ("stream_mode", C.c_int), ("max_packets", C.c_size_t),
+                ("max_payload_bytes", C.c_size_t), ("header_generator", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class HeaderPayloadSplitParams(C.Structure):
     _fields_ = [("header_size", C.c_size_t), ("stream", C.c_void_p)]
 
@@ -240,6 +245,8 @@ EXPORTS = [
     "gr4pm_multichannel_receiver_process", "gr4pm_multichannel_receiver_submit", "gr4pm_multichannel_receiver_collect",
     "gr4pm_multichannel_receiver_in_flight",
     "gr4pm_packet_receiver_collect", "gr4pm_packet_receiver_inflight",
+    "gr4pm_packet_transmitter_create", "gr4pm_packet_transmitter_destroy", "gr4pm_packet_transmitter_reset",
+    "gr4pm_packet_transmitter_output_items", "gr4pm_packet_transmitter_process",
 ]
 
 _lib = None
@@ -415,6 +422,12 @@ def lib():
     L.gr4pm_costas_phase_wrap.argtypes = [vp, sz, vp]
     L.gr4pm_firdes_root_raised_cosine.argtypes = [C.c_double] * 4 + [sz, vp]
     L.gr4pm_firdes_root_raised_cosine.restype = sz
+    L.gr4pm_packet_transmitter_create.argtypes = [C.POINTER(PacketTransmitterParams), C.POINTER(vp)]
+    L.gr4pm_packet_transmitter_destroy.argtypes = [vp]
+    L.gr4pm_packet_transmitter_destroy.restype = None
+    L.gr4pm_packet_transmitter_reset.argtypes = [vp]
+    L.gr4pm_packet_transmitter_output_items.argtypes = [vp, vp, vp, vp, sz, szp]
+    L.gr4pm_packet_transmitter_process.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, szp]
     _lib = L
     return L
 

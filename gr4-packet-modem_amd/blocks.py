@@ -1471,6 +1471,98 @@ class BurstGenerator:
         return out
 
 
+class PacketTransmitter:
+    """gr4pm_packet_transmitter: PacketTransmitterPdu (packet_transmitter_pdu.hpp:40-355) on the device.
+
+    Burst mode: one shaped burst of samples_per_symbol * (4 L + 228) samples per packet (L payload bytes), with
+    optional gaps of zeros in front; the ramp-down GLFSR runs on across bursts and calls until reset().  Stream mode:
+    the packets back to back through one filter whose history carries over to the next call.  max_packets and
+    max_payload_bytes bound one process_bulk() call."""
+
+    USER_DATA, IDLE = 0, 1
+
+    def __init__(self, stream_mode=False, samples_per_symbol=4, max_packets=1 << 14, max_payload_bytes=1 << 25):
+        import os
+        here = os.path.dirname(os.path.abspath(__file__))
+        self._generator = np.fromfile(os.path.join(here, "data", "header_ldpc_generator.u32"), dtype="<u4")
+        self.stream_mode, self.samples_per_symbol = bool(stream_mode), samples_per_symbol
+        p = _abi.PacketTransmitterParams(samples_per_symbol, 1 if stream_mode else 0, max_packets, max_payload_bytes,
+                                         _np_ptr(self._generator), _stream_handle())
+        self._h = C.c_void_p()
+        check(lib().gr4pm_packet_transmitter_create(C.byref(p), C.byref(self._h)), "PacketTransmitter")
+
+    def reset(self):
+        check(lib().gr4pm_packet_transmitter_reset(self._h), "PacketTransmitter.reset")
+
+    @staticmethod
+    def _host_args(n, lengths, packet_types, gaps):
+        lens = np.ascontiguousarray(lengths, dtype=np.uint64)
+        if lens.size != n:
+            raise Gr4pmError(f"PacketTransmitter: {lens.size} lengths for {n} packets")
+        types = None
+        if packet_types is not None:
+            types = np.ascontiguousarray([{"USER_DATA": 0, "IDLE": 1}.get(t, t) if isinstance(t, str) else t
+                                          for t in packet_types], dtype=np.int64)
+            if types.size != n or types.min(initial=0) < 0 or types.max(initial=0) > 255:
+                raise Gr4pmError("PacketTransmitter: one packet type per packet, 0 USER_DATA or 1 IDLE")
+            types = types.astype(np.uint8)
+        g = None if gaps is None else np.ascontiguousarray(gaps, dtype=np.uint64)
+        if g is not None and g.size != n:
+            raise Gr4pmError(f"PacketTransmitter: {g.size} gaps for {n} packets")
+        return lens, types, g
+
+    def output_items(self, lengths, packet_types=None, gaps=None):
+        """samples process_bulk() makes for packets of these lengths"""
+        lens, types, g = self._host_args(len(lengths), lengths, packet_types, gaps)
+        n = C.c_size_t(0)
+        check(lib().gr4pm_packet_transmitter_output_items(self._h, _np_ptr(lens), None if types is None else _np_ptr(types),
+                                                          None if g is None else _np_ptr(g), lens.size, C.byref(n)),
+              "PacketTransmitter.output_items")
+        return n.value
+
+    def process_bulk(self, payloads, packet_types=None, gaps=None, lengths=None, out=None):
+        """payloads: a list of bytes, or a CUDA uint8 tensor of the packets back to back with `lengths`.
+        packet_types: per packet 0 / "USER_DATA" or 1 / "IDLE" (None: all USER_DATA); gaps: samples of silence in
+        front of each burst (burst mode).  out: an optional CUDA complex64 tensor to write into.
+        Returns (samples, burst_offsets, burst_lengths)."""
+        torch = _torch()
+        if isinstance(payloads, torch.Tensor):
+            if lengths is None:
+                raise Gr4pmError("PacketTransmitter: a payload tensor needs `lengths`")
+            if not payloads.is_cuda or payloads.dtype != torch.uint8:
+                raise Gr4pmError("PacketTransmitter expects a CUDA uint8 tensor")
+            data = payloads.contiguous()
+        else:
+            payloads = [bytes(b) for b in payloads]
+            lengths = [len(b) for b in payloads]
+            joined = np.frombuffer(b"".join(payloads), dtype=np.uint8)
+            data = torch.from_numpy(joined.copy()).cuda() if joined.size else torch.empty(1, dtype=torch.uint8, device="cuda")
+        _inputs_ready(data)
+        n = len(lengths)
+        lens, types, g = self._host_args(n, lengths, packet_types, gaps)
+        if out is None:
+            out = torch.empty(max(self.output_items(lens, types, g), 1), dtype=torch.complex64, device=data.device)
+        elif not out.is_cuda or out.dtype != torch.complex64 or not out.is_contiguous():
+            raise Gr4pmError("PacketTransmitter: out must be a contiguous CUDA complex64 tensor")
+        offsets = np.zeros(max(n, 1), dtype=np.uint64)
+        blens = np.zeros(max(n, 1), dtype=np.uint64)
+        n_out = C.c_size_t(0)
+        check(lib().gr4pm_packet_transmitter_process(self._h, data.data_ptr(), _np_ptr(lens),
+                                                     None if types is None else _np_ptr(types),
+                                                     None if g is None else _np_ptr(g), n, out.data_ptr(), out.numel(),
+                                                     _np_ptr(offsets), _np_ptr(blens), C.byref(n_out)),
+              "PacketTransmitter.processBulk")
+        return out[: n_out.value], offsets[:n], blens[:n]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _release("gr4pm_packet_transmitter_destroy", self._h)
+                self._h = None
+        except Exception:  # interpreter shutdown
+            pass
+
+
 def _hip_memcpy_d2d(dst, src, nbytes):
     """device-to-device copy through the HIP runtime the library is linked against"""
     import ctypes.util

@@ -879,6 +879,49 @@ gr4pm_status gr4pm_costas_phase_wrap(const float* x, size_t n, float* out);
 size_t gr4pm_firdes_root_raised_cosine(double gain, double sampling_freq, double symbol_rate,
                                        double alpha, size_t ntaps, float* out);
 
+/* ====================================================================================
+ * PacketTransmitterPdu -- packet_transmitter_pdu.hpp:40-355: payload bytes to IQ.
+ * Burst mode (stream_mode = 0): one burst per packet of samples_per_symbol * (4 L + 228) samples
+ * (L = payload bytes): syncword (64 BPSK), the scrambled header (LDPC(128,32) code word twice) and
+ * payload + big-endian CRC-32 (QPSK), 9 ramp-down symbols from a degree-32 GlfsrSource (seed 1,
+ * carried across bursts and calls until reset()), 11 zero symbols; interpolated by the transmitter's
+ * RRC (packet_transmitter_rrc_taps.hpp) and shaped by sine ramps (BurstShaper).  Optional gaps of
+ * zeros in front of each burst.  Stream mode: syncword, header and payload only, back to back through
+ * one filter whose history carries over to the next call.
+ * ================================================================================== */
+typedef struct gr4pm_packet_transmitter gr4pm_packet_transmitter;
+typedef struct {
+    size_t samples_per_symbol;          /* default 4; 1..64 */
+    int stream_mode;                    /* packet_transmitter_pdu.hpp:41 */
+    size_t max_packets;                 /* per process() call */
+    size_t max_payload_bytes;           /* per process() call, all packets together */
+    const uint32_t* header_generator;   /* host: the 96 rows of the header's LDPC(128,32) generator
+                                           (data/header_ldpc_generator.u32), copied at create */
+    void* stream;                       /* hipStream_t (NULL: the default stream) */
+} gr4pm_packet_transmitter_params;
+gr4pm_status gr4pm_packet_transmitter_create(const gr4pm_packet_transmitter_params* params,
+                                             gr4pm_packet_transmitter** out);
+void gr4pm_packet_transmitter_destroy(gr4pm_packet_transmitter* h);
+/* the GLFSR back to its seed, the stream mode filter history to zeros */
+gr4pm_status gr4pm_packet_transmitter_reset(gr4pm_packet_transmitter* h);
+/* samples process() writes for these packets (host arrays as in process()), with the same checks */
+gr4pm_status gr4pm_packet_transmitter_output_items(const gr4pm_packet_transmitter* h, const uint64_t* lengths,
+                                                   const uint8_t* packet_types, const uint64_t* gaps,
+                                                   size_t n_packets, size_t* n_out);
+/* payload: DEVICE bytes of the n_packets packets back to back; lengths: host, 1..65535 each;
+ * packet_types: host, 0 USER_DATA / 1 IDLE (NULL: all USER_DATA); gaps: host, samples of silence in
+ * front of each burst (NULL: none; burst mode only).  out: DEVICE c64, out_cap items.  Host outputs:
+ * burst_offsets[i] / burst_lengths[i] (the "packet_len" tags) and n_out.  A length of 0 (PacketIngress
+ * throws, packet_ingress.hpp:171-172) or above 65535 (HeaderFormatter, header_formatter.hpp:102-106),
+ * an unknown packet type, gaps in stream mode (GR4PM_ERR_INVALID), more packets or payload bytes than
+ * the handle was made for, or an out_cap below the samples of the call (GR4PM_ERR_OVERFLOW) are
+ * refused before anything is written. */
+gr4pm_status gr4pm_packet_transmitter_process(gr4pm_packet_transmitter* h, const uint8_t* payload,
+                                              const uint64_t* lengths, const uint8_t* packet_types,
+                                              const uint64_t* gaps, size_t n_packets, gr4pm_c64* out,
+                                              size_t out_cap, uint64_t* burst_offsets, uint64_t* burst_lengths,
+                                              size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
