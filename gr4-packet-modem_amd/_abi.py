@@ -244,7 +244,7 @@ EXPORTS = [
     "gr4pm_multichannel_receiver_create", "gr4pm_multichannel_receiver_destroy", "gr4pm_multichannel_receiver_announce",
     "gr4pm_multichannel_receiver_process", "gr4pm_multichannel_receiver_submit", "gr4pm_multichannel_receiver_collect",
     "gr4pm_multichannel_receiver_in_flight",
-    "gr4pm_packet_receiver_collect", "gr4pm_packet_receiver_inflight",
+    "gr4pm_packet_receiver_collect", "gr4pm_packet_receiver_inflight", "gr4pm_packet_receiver_max_inflight",
     "gr4pm_packet_transmitter_create", "gr4pm_packet_transmitter_destroy", "gr4pm_packet_transmitter_reset",
     "gr4pm_packet_transmitter_output_items", "gr4pm_packet_transmitter_process",
 ]
@@ -418,6 +418,8 @@ def lib():
     L.gr4pm_zmq_pub_dropped.argtypes = [vp]
     L.gr4pm_zmq_pub_dropped.restype = C.c_uint64
     L.gr4pm_packet_receiver_inflight.restype = sz
+    L.gr4pm_packet_receiver_max_inflight.argtypes = []
+    L.gr4pm_packet_receiver_max_inflight.restype = sz
     L.gr4pm_sincosf.argtypes = [vp, sz, vp, vp]
     L.gr4pm_costas_phase_wrap.argtypes = [vp, sz, vp]
     L.gr4pm_firdes_root_raised_cosine.argtypes = [C.c_double] * 4 + [sz, vp]

@@ -1781,31 +1781,30 @@ class NativePacketReceiver:
         _inputs_ready(x)
         check(lib().gr4pm_packet_receiver_announce(self._h, x.data_ptr(), x.numel()), "PacketReceiver.announce")
 
-    # output buffers.  output_ring=True (streaming callers, bench.py): a ring of _OUT_RING sets (more
-    # than the batches the library keeps in flight), allocated at the first submit and whenever a
-    # bigger batch arrives -- not once per call: a device allocation in the middle of a stream stalls
-    # every stage.  A result's "symbols" / "llr" / "packets" then stay valid until _OUT_RING - 1
-    # further batches have been submitted.
-    _OUT_RING = 8
+    # output buffers.  output_ring=True (streaming callers, bench.py): a ring of _out_ring_sets() sets, one more than
+    # the batches the library accepts in flight (gr4pm_packet_receiver_max_inflight), allocated at the first submit and
+    # whenever a bigger batch arrives -- not once per call: a device allocation in the middle of a stream stalls every
+    # stage.  No two batches in flight share a set, and a result's "symbols" / "llr" / "packets" stay valid until
+    # max_inflight further batches have been submitted (a refused submit takes no set).
+    @staticmethod
+    def _out_ring_sets():
+        return int(lib().gr4pm_packet_receiver_max_inflight()) + 1
+
+    def _new_outputs(self, n, device):
+        torch = _torch()
+        n_sym = n // self.samples_per_symbol + 4160
+        return (torch.empty(n_sym, dtype=torch.complex64, device=device),
+                torch.empty(2 * n_sym if self.soft_bits and not self.packets_only else 1, dtype=torch.float32, device=device),
+                torch.empty((self._packets_cap or n // 16 + 65536) if self.decode_headers else 1, dtype=torch.uint8, device=device))
 
     def _outputs(self, n, device):
-        torch = _torch()
+        """the output set of the next submit; _out_next moves on only once the library has taken the batch"""
         if not self.output_ring:  # fresh buffers for every batch: results stay valid as long as they are referenced
-            n_sym = n // self.samples_per_symbol + 4160
-            return (torch.empty(n_sym, dtype=torch.complex64, device=device),
-                    torch.empty(2 * n_sym if self.soft_bits and not self.packets_only else 1, dtype=torch.float32, device=device),
-                    torch.empty((self._packets_cap or n // 16 + 65536) if self.decode_headers else 1, dtype=torch.uint8, device=device))
+            return self._new_outputs(n, device)
         if getattr(self, "_out_n", -1) < n:
-            n_sym = n // self.samples_per_symbol + 4160
-            self._out_ring = [(torch.empty(n_sym, dtype=torch.complex64, device=device),
-                               torch.empty(2 * n_sym if self.soft_bits and not self.packets_only else 1, dtype=torch.float32,
-                                           device=device),
-                               torch.empty(n // 16 + 65536 if self.decode_headers else 1, dtype=torch.uint8,
-                                           device=device)) for _ in range(self._OUT_RING)]
+            self._out_ring = [self._new_outputs(n, device) for _ in range(self._out_ring_sets())]
             self._out_n, self._out_next = n, 0
-        out = self._out_ring[self._out_next]
-        self._out_next = (self._out_next + 1) % self._OUT_RING
-        return out
+        return self._out_ring[self._out_next]
 
     def submit(self, x, packet_length=None, history=None, next_x=None):
         x = _dev_c64(x)
@@ -1824,6 +1823,8 @@ class NativePacketReceiver:
             0 if packet_length is None else int(packet_length), sym.data_ptr(), sym.numel(),
             llr.data_ptr() if self.soft_bits and not self.packets_only else None, llr.numel(),
             pk.data_ptr() if self.decode_headers else None, pk.numel()), "PacketReceiver.submit")
+        if self.output_ring:
+            self._out_next = (self._out_next + 1) % len(self._out_ring)
         self._keep.append((x, history, nx, sym, llr, pk))
 
     def collect(self):

@@ -200,6 +200,8 @@ gr4pm_status scrambler_plan(::gr4pm_additive_scrambler* h, size_t n, const uint6
 gr4pm_status header_payload_split_plan(::gr4pm_header_payload_split* h, size_t n, const gr4pm_packet_tag* tags_in,
                                        size_t n_tags_in, gr4pm_packet_tag* header_tags, gr4pm_packet_tag* payload_tags,
                                        size_t tags_cap, hostlogic::HpsReplay& rp);
+// payload items HeaderPayloadSplit still owes the packet it is in (0 between payloads)
+uint64_t header_payload_split_owed(const ::gr4pm_header_payload_split* h);
 gr4pm_status tail_fused(::gr4pm_additive_scrambler* scr, DevBuf<hostlogic::TailSpan>& table,
                         const std::vector<hostlogic::TailSpan>& spans, const gr4pm_c64* symbols, float scale, float* header_llr,
                         uint8_t* packed, hipStream_t s);

@@ -1036,6 +1036,10 @@ gr4pm_status gr4pm::header_payload_split_plan(gr4pm_header_payload_split* h, siz
     }
     return GR4PM_OK;
 }
+uint64_t gr4pm::header_payload_split_owed(const gr4pm_header_payload_split* h)
+{
+    return h && h->in_payload ? h->payload_items - h->position : 0;
+}
 gr4pm_status gr4pm::tail_fused(gr4pm_additive_scrambler* scr, DevBuf<hostlogic::TailSpan>& table,
                                const std::vector<hostlogic::TailSpan>& spans, const gr4pm_c64* symbols, float scale,
                                float* header_llr, uint8_t* packed, hipStream_t s)

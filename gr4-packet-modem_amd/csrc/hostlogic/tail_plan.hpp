@@ -119,19 +119,27 @@ GR4PM_HOST_DEVICE inline void tail_payload_byte(const TailSpan& sp, unsigned lon
 // scr:  the descrambler's runs over the LLR stream (LLR j = 2 * data symbol + (0 | 1)), ascending, covering it
 // hps:  HeaderPayloadSplit's spans over the LLR stream (header_spans -> header stream, payload_spans -> payload stream)
 // payload_bit0: where the batch's payload stream starts in the packer's bit stream (the bits of an unfinished packet
-//       carried from the batches before lie in front of it)
+//       carried from the batches before lie in front of it); even
 // Returns false when a boundary does not fall between two symbols (an odd LLR index: cannot happen with the tags
-// PayloadMetadataInsert publishes; the caller then runs the blocks one by one).
+// PayloadMetadataInsert publishes), and when k_tail_fused could not write the payload table: an odd payload_bit0, or a
+// payload run that starts behind the batch's first payload bit at a bit that is not the first of a byte.  The kernel
+// completes partial bytes with a plain read-modify-write, one run per block row, so only the batch's first run may begin
+// inside a byte; two runs that meet inside one would race.  (Packets are whole bytes, so every run behind the first starts
+// a packet on a byte.)  The caller fails the batch.
 inline bool compose_tail(const std::vector<CopySpan>& sr, const std::vector<ScrambleRun>& scr, const HpsReplay& hps,
                          unsigned long long header_llr0, unsigned long long payload_bit0, std::vector<TailSpan>& out)
 {
     out.clear();
+    if (payload_bit0 & 1ull) return false;
     auto emit = [&](const std::vector<CopySpan>& spans, unsigned kind, unsigned long long dst0) -> bool {
         size_t is = 0, ir = 0; // cursors into sr and scr: every list ascends, the spans of one kind ascend in src
         for (const CopySpan& s : spans) {
             unsigned long long a = s.src, end = s.src + s.len, d = dst0 + s.dst;
             if ((a | end | s.dst) & 1ull) return false;
             while (a < end) {
+                // (checked once per run, before the run is cut into 2^30-symbol pieces below: those pieces are the
+                // kernel's bookkeeping, not boundaries between runs)
+                if (kind == 1 && d != dst0 && (d & 7ull)) return false;
                 while (is < sr.size() && 2 * (sr[is].dst + sr[is].len) <= a) ++is;
                 while (ir < scr.size() && scr[ir].start + scr[ir].len <= a) ++ir;
                 if (is >= sr.size() || ir >= scr.size() || 2 * sr[is].dst > a || scr[ir].start > a) return false;

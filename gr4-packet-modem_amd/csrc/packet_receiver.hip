@@ -211,7 +211,8 @@ struct HeaderLoop {
         n_pay_tags = rp.n_payload_tags;
         GR4PM_TRY(reserve_acc(rp.n_header));
         if (!hostlogic::compose_tail(sr_spans, scr_runs, rp, acc_n, payload_bit0, tail_spans)) {
-            set_error("packets_only: the tag stream behind the Costas loop does not compose (a boundary inside a symbol)");
+            set_error("packets_only: the tag stream behind the Costas loop does not compose (a boundary inside a symbol, "
+                      "or two payload runs that meet inside a byte)");
             return GR4PM_ERR_INTERNAL;
         }
         GR4PM_TRY(gr4pm::tail_fused(scr, tail_table, tail_spans, costas_out, llr_scale, acc.p, packed, stream));
@@ -334,6 +335,9 @@ struct gr4pm_packet_receiver {
     DevBuf<uint8_t> packed2[2];
     int packed_cur = 0;
     size_t carry_bits = 0;
+    // payload LLRs still owed to the packet a failed batch cut (drop_unfinished_payload): they come first in the payload
+    // stream of the batches behind it and are skipped there, not sliced as the start of the next packet
+    uint64_t skip_payload = 0;
     Slot slots[kSlots];
     SlotRing free_slots, to_stageA, to_stage1, to_stage1b, to_stage2, to_stage3, done;
     std::thread workers[5];
@@ -380,12 +384,16 @@ struct gr4pm_packet_receiver {
     // A batch that fails in stage3_decode has popped payload lengths without consuming their soft bits, or has not
     // appended its own: `soft` / `soft_n` / `payload_bits` no longer describe one stream.  The stage lives on after a
     // failed batch (run_stage), so the carried state starts empty again -- the packets in flight across the failed
-    // batch are lost with it; everything behind is sliced from consistent state.
+    // batch are lost with it.  The header loop has already split the whole failed batch, though: when the batch ended
+    // inside a payload, the split still owes the rest of that packet, and those LLRs arrive untagged at the head of the
+    // next payload stream(s).  skip_payload counts them, and stage3_decode skips them (over as many batches as they
+    // span), so the packets behind start where their tags say (in packets_only on a byte of the packed stream).
     void drop_unfinished_payload()
     {
         soft_n = 0;
         carry_bits = 0;
         payload_bits.clear();
+        skip_payload = p.decode_headers ? gr4pm::header_payload_split_owed(b_loop.split) : 0;
     }
 };
 
@@ -1021,11 +1029,13 @@ gr4pm_status gr4pm_packet_receiver::stage3_decode(Slot& s)
     for (const auto& m : s.opened) used_msgs.push_back(m);
     s.header_messages.clear();
     s.packet_type.clear();
-    const size_t lean_bit0 = carry_bits; // packets_only: this batch's payload bits go behind the carried ones
+    // packets_only: this batch's payload bits go behind the carried ones -- or, while the rest of a packet that a failed
+    // batch cut is being skipped (nothing is carried then), at the bit that makes the first packet behind it start on a byte
+    const size_t lean_bit0 = skip_payload ? (8 - skip_payload % 8) % 8 : carry_bits;
     if (p.packets_only) {
         uint8_t* stream_bytes = nullptr;
         {   // the packer's byte stream of this batch: carried bits + at most one bit per LLR
-            const size_t want = (carry_bits + n_llr) / 8 + 16;
+            const size_t want = (lean_bit0 + n_llr) / 8 + 16;
             auto& pk = packed2[packed_cur];
             if (pk.n < want) {
                 DevBuf<uint8_t> bigger;
@@ -1060,17 +1070,24 @@ gr4pm_status gr4pm_packet_receiver::stage3_decode(Slot& s)
         }
         if (!same_header(given, got)) ++s.header_mismatches;
     }
-    const size_t n_pay = b_loop.n_pay;
-    const float* pay = p.packets_only ? nullptr : s.payload_llr.p;
-    s.n_payload_llr = n_pay;
+    s.n_payload_llr = b_loop.n_pay;
     s.n_payload_tags = b_loop.n_pay_tags;
     s.payload_tags.assign(b_loop.pay_tags.begin(), b_loop.pay_tags.begin() + b_loop.n_pay_tags);
+    // the rest of a packet cut by a failed batch (drop_unfinished_payload) heads the payload stream: skipped
+    const size_t skipped = static_cast<size_t>(std::min<uint64_t>(skip_payload, b_loop.n_pay));
+    skip_payload -= skipped;
+    const size_t n_pay = b_loop.n_pay - skipped;
+    const float* pay = p.packets_only ? nullptr : s.payload_llr.p + skipped;
     // payload tail, packet_receiver.hpp:140-147 (whole packets only; the rest waits): the stream is
-    // [soft[0 .. soft_n): the unfinished packet of the batches before | pay[0 .. n_pay)], sliced and packed in place
+    // [soft[0 .. soft_n): the unfinished packet of the batches before | pay[0 .. n_pay)], sliced and packed in place;
+    // in packets_only the packed stream is [carried bits | this batch's bits] from bit 0, or [lean_bit0 bits of nothing |
+    // skipped bits | this batch's packets] behind a failed batch (used_bits starts behind the skipped ones, on a byte
+    // when they end in this batch)
     for (size_t i = 0; i < b_loop.n_pay_tags; ++i) payload_bits.push_back(b_loop.pay_tags[i].payload_bits);
-    const size_t total = (p.packets_only ? carry_bits : soft_n) + n_pay;
+    const size_t head = p.packets_only ? lean_bit0 + skipped : soft_n;
+    const size_t total = head + n_pay;
     std::vector<uint64_t> lens, offs;
-    size_t used_bits = 0;
+    size_t used_bits = p.packets_only ? head - carry_bits : 0;
     while (!payload_bits.empty() && used_bits + payload_bits.front() <= total) {
         offs.push_back(used_bits / 8);
         lens.push_back(payload_bits.front() / 8);
@@ -1400,6 +1417,7 @@ try {
 GR4PM_ABI_CATCH_VOID
 
 size_t gr4pm_packet_receiver_inflight(const gr4pm_packet_receiver* h) { return h ? h->inflight : 0; }
+size_t gr4pm_packet_receiver_max_inflight(void) { return kSlots - 1; }
 
 gr4pm_status gr4pm_packet_receiver_submit(gr4pm_packet_receiver* h, const gr4pm_c64* in, size_t n_in,
                                           const gr4pm_c64* delayed, const gr4pm_c64* next_in, size_t next_n,
@@ -1413,7 +1431,7 @@ try {
                   gr4pm_packet_receiver::kW + gr4pm_packet_receiver::kPre + 2048);
         return GR4PM_ERR_INVALID;
     }
-    if (h->inflight >= static_cast<size_t>(kSlots - 1)) {
+    if (h->inflight >= gr4pm_packet_receiver_max_inflight()) {
         set_error("%zu batches in flight: collect one first", h->inflight);
         return GR4PM_ERR_INVALID;
     }

@@ -764,6 +764,9 @@ gr4pm_status gr4pm_packet_receiver_announce(gr4pm_packet_receiver* h, const gr4p
 /* waits for the oldest batch; returns its status (the error text of a failed stage included) */
 gr4pm_status gr4pm_packet_receiver_collect(gr4pm_packet_receiver* h, gr4pm_packet_receiver_result* result);
 size_t gr4pm_packet_receiver_inflight(const gr4pm_packet_receiver* h);
+/* the most batches _submit accepts in flight (a further _submit fails until one is collected): a caller that recycles
+ * its output buffers needs more sets than this */
+size_t gr4pm_packet_receiver_max_inflight(void);
 /* soft_bits receivers: fn == NULL removes the callback */
 gr4pm_status gr4pm_packet_receiver_set_symbol_pdu_callback(gr4pm_packet_receiver* h, gr4pm_symbol_pdu_fn fn, void* user);
 

@@ -771,11 +771,45 @@ static void tail_compose(std::mt19937_64& rng)
     CHECK(wrong == 0, "%zu of %zu packed bytes differ", wrong, pay_ref.size() / 8);
 }
 
+// compose_tail refuses a payload table that k_tail_fused could not write: the kernel completes a partial byte with a plain
+// read-modify-write, one run per block row, so two payload runs that meet inside a byte would race.  Only the batch's first
+// run may begin inside a byte (behind the bits carried from the batch before); payload_bit0 must be even.  Cutting a run
+// into 2^30-symbol pieces is no boundary between runs and must not trip the rule.
+static void tail_refusals()
+{
+    const std::vector<CopySpan> sr{ { 0, 0, 100 } };          // 100 symbols: 200 LLRs, one descrambler run
+    const std::vector<ScrambleRun> runs{ { 0, 200, 0 } };
+    auto compose = [&](std::vector<CopySpan> pay, unsigned long long bit0, std::vector<TailSpan>& out) {
+        HpsReplay hp;
+        hp.header_spans = { { 24, 0, 16 } };
+        hp.payload_spans = std::move(pay);
+        return compose_tail(sr, runs, hp, 0, bit0, out);
+    };
+    std::vector<TailSpan> out;
+    // two packets of 12 and 20 bits behind each other: the second starts at bit 12, inside byte 1
+    CHECK(!compose({ { 0, 0, 12 }, { 40, 12, 20 } }, 0, out), "two payload runs that meet inside a byte were composed");
+    CHECK(!compose({ { 0, 0, 12 }, { 40, 12, 20 } }, 2, out), "a run at bit 14 behind the first was composed");
+    // the same boundary on a byte, and a first run that starts inside one: composed, and where they were put
+    CHECK(compose({ { 0, 0, 16 }, { 40, 16, 20 } }, 0, out) && out.size() == 3 && out[1].dst == 0 && out[2].dst == 16,
+          "byte-aligned payload runs were refused");
+    CHECK(compose({ { 0, 0, 12 }, { 40, 12, 20 } }, 4, out) && out.size() == 3 && out[1].dst == 4 && out[2].dst == 16,
+          "a first run inside a byte was refused");
+    CHECK(!compose({ { 0, 0, 16 } }, 3, out), "an odd payload_bit0 was composed");
+    // a single run longer than 2^30 symbols behind bit 6: the second piece starts at bit 6 + 2^31, not on a byte
+    const unsigned long long n = (1ull << 30) + 10;
+    HpsReplay hp;
+    hp.payload_spans = { { 0, 0, 2 * n } };
+    const bool long_ok = compose_tail({ { 0, 0, n } }, { { 0, 2 * n, 0 } }, hp, 0, 6, out);
+    CHECK(long_ok && out.size() == 2 && out[1].dst == 6 + (2ull << 30) && out[1].n_sym == 10,
+          "a run cut into 2^30-symbol pieces was refused or cut wrongly (%zu pieces)", out.size());
+}
+
 int main(int argc, char** argv)
 {
     const int cases = argc > 1 ? atoi(argv[1]) : 20;
     const unsigned long long seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 4;
     std::mt19937_64 rng(seed);
+    tail_refusals();
     for (int c = 0; c < cases; ++c) {
         sdf_calls(rng);
         sdf_gate_vs_block(rng);

@@ -3151,16 +3151,27 @@ def test_native_packet_receiver_goes_on_after_a_batch_whose_packets_did_not_fit(
     failed = [i for i, r in enumerate(out) if r["status"] != 0]
     assert failed and failed[0] > 0 and failed[-1] < len(out) - 5 and all("packets_cap" in out[i]["error"] for i in failed), \
         [r["status"] for r in out]
+    # every packet of `ok`: its start in the payload LLR stream (counted from the first batch) and its end
+    starts, ends, pay_end = [], [], []
+    for b in ref:
+        P = pay_end[-1] if pay_end else 0
+        starts += [P + int(t["index"]) for t in b["payload_tags"]]
+        ends += [P + int(t["index"]) + int(t["payload_bits"]) for t in b["payload_tags"]]
+        pay_end.append(P + b["n_payload_llr"])
     good_after = 0
     for i, (a, b) in enumerate(zip(out, ref)):
         if a["status"] != 0:
             continue
         assert a["consumed"] == b["consumed"]
         if i and out[i - 1]["status"] != 0:
-            # the first batch behind a failed one: the packet that the failed batch cut is lost, the others are intact
-            mine = a["packets"].cpu().numpy().tobytes()
-            want = b["packets"].cpu().numpy().tobytes()
-            assert len(mine) % 200 == 0 and all(mine[k:k + 200] in want for k in range(0, len(mine), 200))
+            # the first batch behind a failed one: `ok`'s packets, less the one the end of the failed batch cut (which
+            # started before that end and ends in this batch); all the others intact
+            lost = sum(1 for s, e in zip(starts, ends) if s < pay_end[i - 1] < e <= pay_end[i])
+            want_len = [int(v) for v in b["packet_lengths"]][lost:]
+            assert [int(v) for v in a["packet_lengths"]] == want_len, (i, lost)
+            skip = int(np.sum(b["packet_lengths"][:lost]))
+            assert np.array_equal(a["packets"].cpu().numpy(), b["packets"].cpu().numpy()[skip:]), i
+            assert a["packet_lengths"].size or not want_len
             continue
         assert np.array_equal(a["packet_lengths"], b["packet_lengths"])
         assert np.array_equal(a["packets"].cpu().numpy(), b["packets"].cpu().numpy())

@@ -19,7 +19,8 @@ SIG = re.compile(r'^(extern "C" )?([A-Za-z_][\w \*]*?[\s\*])(gr4pm_\w+)\(')
 # cannot throw: plain loads / stores / arithmetic on the arguments, no allocation, no C++ library call
 NOTHROW_ONE_LINERS = {
     "gr4pm_last_error", "gr4pm_set_deferred_sync", "gr4pm_version", "gr4pm_multichannel_receiver_in_flight",
-    "gr4pm_packet_receiver_inflight", "gr4pm_syncword_detection_syncword_samples_size",
+    "gr4pm_packet_receiver_inflight", "gr4pm_packet_receiver_max_inflight",
+    "gr4pm_syncword_detection_syncword_samples_size",
     "gr4pm_syncword_detection_self_corr", "gr4pm_test_allocation_count",
 }
 
