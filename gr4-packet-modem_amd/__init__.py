@@ -9,12 +9,12 @@ import numpy as np
 
 from ._abi import (EXPORTS, LIB_PATH, PACKET_TAG_DTYPE, PKT_HEADER_START, PKT_PAYLOAD, PKT_SYNCWORD,  # noqa: F401
                    TAG_DTYPE, TAG_OTHER, TAG_SYNCWORD, Gr4pmError, lib)
-from .blocks import (SYNCWORD, ZmqPduPubSink, AdditiveScrambler, BurstGenerator, PacketTransmitter, CrcCheck, burst_shaper, mapper, binary_slicer, pack_bits, slice_pack, CoarseFrequencyCorrection, ConstellationLLRDecoder,  # noqa: F401
+from .blocks import (SYNCWORD, ZmqPduPubSink, NoiseSource, Channel, NOISE_TYPES, AdditiveScrambler, BurstGenerator, PacketTransmitter, CrcCheck, burst_shaper, mapper, binary_slicer, pack_bits, slice_pack, CoarseFrequencyCorrection, ConstellationLLRDecoder,  # noqa: F401
                      CostasLoop, HeaderDecoder, HeaderFecDecoder, HeaderPayloadSplit, InterpolatingFirFilter, MultiChannelPacketReceiver, NativeMultiChannelReceiver, NativePacketReceiver, PacketReceiver,
                      PayloadMetadataInsert, PfbArbResampler, Rotator, SymbolFilter, SyncwordDetection,
                      SyncwordDetectionFilter, SyncwordRemove, SyncwordWipeoff, cfc_symbol_filter, cfc_symbol_filter_plan, cfc_symbol_filter_run,
                      header_ldpc_alist,
-                     header_parse, packet_transmitter_rrc_taps, root_raised_cosine, sincosf, costas_phase_wrap)
+                     header_parse, packet_transmitter_rrc_taps, root_raised_cosine, sincosf, costas_phase_wrap, logf)
 
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 

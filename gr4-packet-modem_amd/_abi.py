@@ -187,6 +187,11 @@ class PfbArbParams(C.Structure):
                 ("n_taps", C.c_size_t), ("filter_size", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class NoiseSourceParams(C.Structure):
+    _fields_ = [("item_kind", C.c_int), ("noise_type", C.c_int), ("amplitude", C.c_float), ("seed", C.c_uint64),
+                ("max_items", C.c_size_t), ("stream", C.c_void_p)]
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -247,6 +252,8 @@ EXPORTS = [
     "gr4pm_packet_receiver_collect", "gr4pm_packet_receiver_inflight", "gr4pm_packet_receiver_max_inflight",
     "gr4pm_packet_transmitter_create", "gr4pm_packet_transmitter_destroy", "gr4pm_packet_transmitter_reset",
     "gr4pm_packet_transmitter_output_items", "gr4pm_packet_transmitter_process",
+    "gr4pm_noise_source_create", "gr4pm_noise_source_destroy", "gr4pm_noise_source_reset",
+    "gr4pm_noise_source_set_amplitude", "gr4pm_noise_source_process", "gr4pm_logf",
 ]
 
 _lib = None
@@ -430,6 +437,13 @@ def lib():
     L.gr4pm_packet_transmitter_reset.argtypes = [vp]
     L.gr4pm_packet_transmitter_output_items.argtypes = [vp, vp, vp, vp, sz, szp]
     L.gr4pm_packet_transmitter_process.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, szp]
+    L.gr4pm_noise_source_create.argtypes = [C.POINTER(NoiseSourceParams), C.POINTER(vp)]
+    L.gr4pm_noise_source_destroy.argtypes = [vp]
+    L.gr4pm_noise_source_destroy.restype = None
+    L.gr4pm_noise_source_reset.argtypes = [vp]
+    L.gr4pm_noise_source_set_amplitude.argtypes = [vp, C.c_float]
+    L.gr4pm_noise_source_process.argtypes = [vp, vp, vp, sz]
+    L.gr4pm_logf.argtypes = [vp, sz, vp]
     _lib = L
     return L
 

@@ -105,6 +105,19 @@ def sincosf(x):
     return s.cpu().numpy(), c.cpu().numpy()
 
 
+def logf(x):
+    """glibc's logf as the NoiseSource kernels evaluate it (csrc/noise_source.hip), for the parity suite.  x: a CUDA
+    float32 tensor (returns one) or anything numpy takes (returns a numpy array)"""
+    torch = _torch()
+    on_dev = isinstance(x, torch.Tensor) and x.is_cuda
+    xd = x.contiguous() if on_dev else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    if xd.dtype != torch.float32:
+        raise TypeError("logf: float32 input")
+    out = torch.empty_like(xd)
+    check(lib().gr4pm_logf(xd.data_ptr(), xd.numel(), out.data_ptr()), "logf")
+    return out if on_dev else out.cpu().numpy()
+
+
 def costas_phase_wrap(x):
     """the phase wrap of a CostasLoop iteration (costas_loop.hpp:141-145) as the kernels evaluate it, for the parity suite"""
     torch = _torch()
@@ -1573,6 +1586,97 @@ def _hip_memcpy_d2d(dst, src, nbytes):
         _hiprt = C.CDLL("libamdhip64.so")
         _hiprt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     return 0 if _hiprt.hipMemcpy(dst, src, nbytes, 3) == 0 else -3
+
+
+NOISE_TYPES = {"UNIFORM": 0, "GAUSSIAN": 1, "LAPLACIAN": 2, "IMPULSE": 3}
+
+
+class NoiseSource:
+    """gr4pm_noise_source: NoiseSource<T> (noise_source.hpp:45-110) on the device, bit-exact with the reference's
+    sequential stream (ROCm clang++ against libstdc++) for any call size and chain of calls.  item: "c64" (UNIFORM,
+    GAUSSIAN) or "float" (all four types).  The stream position stays on the device; reset() returns to start()."""
+
+    def __init__(self, noise_type="gaussian", amplitude=1.0, seed=0, item="c64", max_items=1 << 24):
+        t = NOISE_TYPES.get(str(noise_type).upper())
+        if t is None:
+            raise Gr4pmError(f"NoiseSource: unknown noise_type {noise_type}")  # enum_cast(...).value() throws
+        if item not in ("c64", "float"):
+            raise Gr4pmError(f"NoiseSource: item must be 'c64' or 'float', not {item!r}")
+        self.noise_type, self.item, self.seed, self.max_items = str(noise_type).upper(), item, int(seed), max_items
+        self._amplitude = float(np.float32(amplitude))
+        p = _abi.NoiseSourceParams(0 if item == "c64" else 1, t, self._amplitude, self.seed, max_items, _stream_handle())
+        self._h = C.c_void_p()
+        check(lib().gr4pm_noise_source_create(C.byref(p), C.byref(self._h)), "NoiseSource")
+
+    @property
+    def amplitude(self):
+        return self._amplitude
+
+    @amplitude.setter
+    def amplitude(self, value):
+        """settingsChanged(): later items take the new amplitude, the stream position is kept"""
+        self._amplitude = float(np.float32(value))
+        check(lib().gr4pm_noise_source_set_amplitude(self._h, self._amplitude), "NoiseSource.amplitude")
+
+    def reset(self):
+        check(lib().gr4pm_noise_source_reset(self._h), "NoiseSource.reset")
+
+    start = reset
+
+    def process_bulk(self, n, add_to=None, out=None):
+        """the next n items; add_to (a CUDA tensor of n items of the handle's kind): returns add_to + noise (Add's
+        processOne(signal, noise)).  out: optional CUDA tensor to write into (may be add_to)."""
+        torch = _torch()
+        dt = torch.complex64 if self.item == "c64" else torch.float32
+        if add_to is not None:
+            if not add_to.is_cuda or add_to.dtype != dt or add_to.numel() != n:
+                raise Gr4pmError(f"NoiseSource: add_to must be a CUDA {dt} tensor of {n} items")
+            add_to = add_to.contiguous()
+        if out is None:
+            out = torch.empty(n, dtype=dt, device="cuda")
+        elif not out.is_cuda or out.dtype != dt or out.numel() != n or not out.is_contiguous():
+            raise Gr4pmError(f"NoiseSource: out must be a contiguous CUDA {dt} tensor of {n} items")
+        check(lib().gr4pm_noise_source_process(self._h, None if add_to is None else add_to.data_ptr(), out.data_ptr(), n),
+              "NoiseSource.processBulk")
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _release("gr4pm_noise_source_destroy", self._h)
+                self._h = None
+        except Exception:  # interpreter shutdown
+            pass
+
+
+class Channel:
+    """The channel of apps/packet_transceiver.cpp:48-78: PfbArbResampler (SFO) -> Rotator (CFO) -> Add with a
+    Gaussian NoiseSource<c64> (AWGN at Es/N0 for the transmitter's measured power of 0.32).  n0 = 0.32 sps
+    10^(-esn0/10) in double, amplitude float(sqrt(n0)), resampling rate 1.0f + 1e-6f sfo_ppm in float.  Input the
+    resampler leaves unconsumed is carried into the next call."""
+
+    TX_POWER = 0.32
+
+    def __init__(self, samples_per_symbol=4, esn0_db=20.0, cfo=0.0, sfo_ppm=0.0, seed=0, max_items=1 << 24):
+        import math
+        self.samples_per_symbol, self.esn0_db = samples_per_symbol, float(esn0_db)
+        self.n0 = self.TX_POWER * float(samples_per_symbol) * math.pow(10.0, -0.1 * self.esn0_db)
+        self.noise_amplitude = float(np.float32(math.sqrt(self.n0)))
+        self.rate = float(np.float32(1.0) + np.float32(1e-6) * np.float32(sfo_ppm))
+        self.resampler = PfbArbResampler(rate=self.rate)
+        self.rotator = Rotator(cfo)
+        self.noise = NoiseSource("gaussian", self.noise_amplitude, seed, "c64", max_items)
+        self._carry = None
+
+    def process_bulk(self, x):
+        torch = _torch()
+        x = _dev_c64(x)
+        if self._carry is not None and self._carry.numel():
+            x = torch.cat([self._carry, x])
+        y, consumed = self.resampler.process_bulk(x)
+        self._carry = x[consumed:].clone()
+        y = self.rotator.process_bulk(y.contiguous())
+        return self.noise.process_bulk(y.numel(), add_to=y, out=y)
 
 
 class MultiChannelPacketReceiver:

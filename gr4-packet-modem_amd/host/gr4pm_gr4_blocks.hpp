@@ -1615,6 +1615,80 @@ public:
     }
 };
 
+// replaces gr::packet_modem::NoiseSource<T> (noise_source.hpp:45-110) for T = std::complex<float> and T = float: the
+// reference's stream bit for bit (ROCm clang++ against libstdc++), generated on the device.
+// settingsChanged() parses and records the settings only -- it never touches the device, so a graph is built exactly
+// as with the reference's block; the handle is made in start() (random(seed), :59) or by the first processBulk().
+// An amplitude change keeps the stream position (:49-56).  A noise_type change after start() restarts the stream at
+// its seed: the reference carries its generator across the change, which the handle's position (counted in the old
+// type's draws) cannot express.
+enum class NoiseType { UNIFORM, GAUSSIAN, LAPLACIAN, IMPULSE };
+namespace detail {
+inline int noise_type_id(const std::string& name)
+{
+    std::string s;
+    for (char c : name) s += static_cast<char>(std::toupper(static_cast<unsigned char>(c)));
+    if (s == "UNIFORM") return GR4PM_NOISE_UNIFORM;
+    if (s == "GAUSSIAN") return GR4PM_NOISE_GAUSSIAN;
+    if (s == "LAPLACIAN") return GR4PM_NOISE_LAPLACIAN;
+    if (s == "IMPULSE") return GR4PM_NOISE_IMPULSE;
+    throw gr::exception("unknown noise_type " + name); // enum_cast(...).value() throws, noise_source.hpp:51-53
+}
+} // namespace detail
+
+template <typename T>
+class NoiseSource : public gr::Block<NoiseSource<T>>
+{
+    static constexpr bool is_complex = std::is_same_v<T, std::complex<float>>;
+    static_assert(is_complex || std::is_same_v<T, float>, "gr4pm: NoiseSource is built for std::complex<float> and float");
+    using D = std::conditional_t<is_complex, gr4pm_c64, float>;
+    gr4pm_noise_source* _h = nullptr;
+    detail::DeviceStage<D> _dout;
+    int _type = GR4PM_NOISE_UNIFORM; // the handle's noise type
+
+public:
+    gr::PortOut<T> out;
+    std::string noise_type = "UNIFORM";
+    float amplitude = 1.0f;
+    uint64_t seed = 0;
+    bool host_output = true;
+    NoiseSource() = default;
+    NoiseSource(const NoiseSource&) = delete;
+    ~NoiseSource() { gr4pm_noise_source_destroy(_h); }
+    void settingsChanged(const gr::property_map&, const gr::property_map&) // :49-56: host only
+    {
+        const int t = detail::noise_type_id(noise_type);
+        if (_h && t != _type) {
+            gr4pm_noise_source_destroy(_h);
+            _h = nullptr;
+        }
+        if (_h) detail::check(gr4pm_noise_source_set_amplitude(_h, amplitude), "NoiseSource::settingsChanged");
+    }
+    void start() // :59: _rng = random(seed)
+    {
+        gr4pm_noise_source_destroy(_h);
+        _h = nullptr;
+        _type = detail::noise_type_id(noise_type);
+        if (is_complex && _type != GR4PM_NOISE_UNIFORM && _type != GR4PM_NOISE_GAUSSIAN)
+            throw gr::exception("invalid noise_type"); // :88, the complex forms take UNIFORM and GAUSSIAN only
+        gr4pm_noise_source_params p{ is_complex ? GR4PM_NOISE_C64 : GR4PM_NOISE_FLOAT, _type, amplitude, seed,
+                                     detail::max_items(), nullptr };
+        detail::check(gr4pm_noise_source_create(&p, &_h), "NoiseSource::start");
+    }
+    gr::work::Status processBulk(gr::PublishableSpan auto& outSpan)
+    {
+        GR4PM_TRACE_ENTRY(size_t{ 0 }, outSpan.size());
+        if (!_h) start();
+        const size_t n = std::min(outSpan.size(), detail::max_items());
+        D* dout = _dout.out(n);
+        detail::check(gr4pm_noise_source_process(_h, nullptr, dout, n), "NoiseSource");
+        _dout.publish(std::to_address(outSpan.begin()), n, host_output);
+        outSpan.publish(n);
+        GR4PM_TRACE_EXIT(size_t{ 0 }, n);
+        return gr::work::Status::OK;
+    }
+};
+
 // firdes::root_raised_cosine<T> (firdes.hpp:29-76): same signature, the library's design routine
 namespace firdes {
 template <typename T = float>
@@ -1653,3 +1727,4 @@ ENABLE_REFLECTION_FOR_TEMPLATE(gr::packet_modem::hip::HeaderPayloadSplit, in, he
                                packet_len_tag_key, payload_length_key);
 ENABLE_REFLECTION(gr::packet_modem::hip::HeaderFecDecoder, in, out);
 ENABLE_REFLECTION_FOR_TEMPLATE(gr::packet_modem::hip::ZmqPduPubSink, in, endpoint);
+ENABLE_REFLECTION_FOR_TEMPLATE(gr::packet_modem::hip::NoiseSource, out, noise_type, amplitude, seed, host_output);

@@ -925,6 +925,42 @@ gr4pm_status gr4pm_packet_transmitter_process(gr4pm_packet_transmitter* h, const
                                               size_t out_cap, uint64_t* burst_offsets, uint64_t* burst_lengths,
                                               size_t* n_out);
 
+/* ====================================================================================
+ * NoiseSource<T> -- noise_source.hpp:45-110 over random.hpp / xoroshiro128p.h: the reference's
+ * sequential stream bit for bit (ROCm clang++ against libstdc++: generate_canonical<float, 24>
+ * with the clamp of 1.0, std::complex(gasdev(), gasdev()) evaluated left to right), generated in
+ * parallel for any call size and any chain of calls.  Seed 0 is an ordinary seed.  Complex items
+ * take UNIFORM and GAUSSIAN only.  The stream position stays on the device: process() enqueues on
+ * the handle's stream and does not wait.
+ * ================================================================================== */
+#define GR4PM_NOISE_C64 0
+#define GR4PM_NOISE_FLOAT 1
+#define GR4PM_NOISE_UNIFORM 0
+#define GR4PM_NOISE_GAUSSIAN 1
+#define GR4PM_NOISE_LAPLACIAN 2
+#define GR4PM_NOISE_IMPULSE 3
+typedef struct gr4pm_noise_source gr4pm_noise_source;
+typedef struct {
+    int item_kind;      /* GR4PM_NOISE_C64 (gr4pm_c64 items) or GR4PM_NOISE_FLOAT */
+    int noise_type;     /* GR4PM_NOISE_UNIFORM / GAUSSIAN / LAPLACIAN / IMPULSE (the reference's NoiseType) */
+    float amplitude;    /* complex items: amplitude / sqrt2_v<float> per component */
+    uint64_t seed;      /* random(seed) at start() */
+    size_t max_items;   /* per process() call; 1..2^31 */
+    void* stream;       /* hipStream_t (NULL: the default stream) */
+} gr4pm_noise_source_params;
+gr4pm_status gr4pm_noise_source_create(const gr4pm_noise_source_params* params, gr4pm_noise_source** out);
+void gr4pm_noise_source_destroy(gr4pm_noise_source* h);
+/* back to the start of the stream (start(): random(seed)) */
+gr4pm_status gr4pm_noise_source_reset(gr4pm_noise_source* h);
+/* settingsChanged: the amplitude of later items; the stream position is kept */
+gr4pm_status gr4pm_noise_source_set_amplitude(gr4pm_noise_source* h, float amplitude);
+/* the next n items into out (DEVICE, gr4pm_c64 or float as the handle's item_kind).  add_in: NULL for
+ * the noise alone, or DEVICE items of the same kind: out = add_in + noise (Add::processOne(signal,
+ * noise)); add_in may be out.  More than max_items is refused before anything is written. */
+gr4pm_status gr4pm_noise_source_process(gr4pm_noise_source* h, const void* add_in, void* out, size_t n);
+/* glibc's logf as the noise kernels compute it (DEVICE x, out; synchronous) */
+gr4pm_status gr4pm_logf(const float* x, size_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif
