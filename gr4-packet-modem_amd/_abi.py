@@ -192,6 +192,11 @@ class NoiseSourceParams(C.Structure):
                 ("max_items", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class ChannelizerParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("taps_per_branch", C.c_size_t), ("taps", C.c_void_p),
+                ("n_select", C.c_size_t), ("select", C.c_void_p), ("max_frames", C.c_size_t), ("stream", C.c_void_p)]
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -254,6 +259,8 @@ EXPORTS = [
     "gr4pm_packet_transmitter_output_items", "gr4pm_packet_transmitter_process",
     "gr4pm_noise_source_create", "gr4pm_noise_source_destroy", "gr4pm_noise_source_reset",
     "gr4pm_noise_source_set_amplitude", "gr4pm_noise_source_process", "gr4pm_logf",
+    "gr4pm_channelizer_taps", "gr4pm_channelizer_create", "gr4pm_channelizer_destroy", "gr4pm_channelizer_reset",
+    "gr4pm_channelizer_output_items", "gr4pm_channelizer_process",
 ]
 
 _lib = None
@@ -444,6 +451,13 @@ def lib():
     L.gr4pm_noise_source_set_amplitude.argtypes = [vp, C.c_float]
     L.gr4pm_noise_source_process.argtypes = [vp, vp, vp, sz]
     L.gr4pm_logf.argtypes = [vp, sz, vp]
+    L.gr4pm_channelizer_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
+    L.gr4pm_channelizer_create.argtypes = [C.POINTER(ChannelizerParams), C.POINTER(vp)]
+    L.gr4pm_channelizer_destroy.argtypes = [vp]
+    L.gr4pm_channelizer_destroy.restype = None
+    L.gr4pm_channelizer_reset.argtypes = [vp]
+    L.gr4pm_channelizer_output_items.argtypes = [vp, sz, szp]
+    L.gr4pm_channelizer_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
     _lib = L
     return L
 

@@ -1679,6 +1679,92 @@ class Channel:
         return self.noise.process_bulk(y.numel(), add_to=y, out=y)
 
 
+def channelizer_taps(n_channels, taps_per_branch=12, passband=0.25, stopband=0.75):
+    """gr4pm_channelizer_taps: the Channelizer's prototype low-pass, a Kaiser-windowed sinc of taps_per_branch *
+    n_channels float32 taps with DC gain 1 (host only: works without a GPU).  passband / stopband: the band edges in
+    units of the channel spacing.  The defaults suit the transmitter's RRC at 4 samples per symbol (occupied to 0.169
+    of the spacing; the neighbour's band starts at 0.831)."""
+    n = int(n_channels) * int(taps_per_branch)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_channelizer_taps(int(n_channels), int(taps_per_branch), float(passband), float(stopband),
+                                       _np_ptr(out)), "channelizer_taps")
+    return out[:n]
+
+
+class Channelizer:
+    """gr4pm_channelizer: critically sampled polyphase analysis bank.  One wideband complex64 stream at fs becomes
+    n_channels (a power of two, 2 .. 1024) channels at fs / n_channels: row k is the band at +k fs / n_channels
+    (k > n_channels / 2: negative frequencies, as an FFT orders them), so that
+    NativeMultiChannelReceiver.submit(Channelizer(...).process_bulk(x)) is a wideband receiver.
+    taps: taps_per_branch * n_channels float32 prototype taps (None: channelizer_taps(n_channels, taps_per_branch)).
+    select: channel numbers to deliver, in this order (None: all).  process_bulk() takes any number of samples; the
+    filter history and the samples of an incomplete frame stay on the device.  The handle works on the stream that is
+    current when it is made."""
+
+    def __init__(self, n_channels, taps=None, taps_per_branch=12, select=None, max_frames=1 << 22):
+        self.n_channels = int(n_channels)
+        if taps is not None:
+            self.taps = np.ascontiguousarray(taps, dtype=np.float32)
+            if self.n_channels < 1 or self.taps.size % self.n_channels or not self.taps.size:
+                raise Gr4pmError(f"Channelizer: {self.taps.size} taps are not a multiple of {self.n_channels} channels")
+            taps_per_branch = self.taps.size // self.n_channels
+        else:
+            self.taps = channelizer_taps(self.n_channels, taps_per_branch)
+        self.taps_per_branch = int(taps_per_branch)
+        self.select = None if select is None else [int(k) for k in select]
+        if self.select is not None and (not self.select or min(self.select) < 0):
+            raise Gr4pmError("Channelizer: select must be a non-empty list of channel numbers")
+        sel = np.ascontiguousarray(self.select if self.select is not None else [], dtype=np.uint32)
+        self.n_rows = sel.size if self.select is not None else self.n_channels
+        self.max_frames = int(max_frames)
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.ChannelizerParams(self.n_channels, self.taps_per_branch, _np_ptr(self.taps), sel.size,
+                                   _np_ptr(sel) if sel.size else None, self.max_frames, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_channelizer_create(C.byref(p), C.byref(self._h)), "Channelizer")
+
+    def output_items(self, n_in):
+        """frames (items per row) the next process_bulk() of n_in samples produces"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_channelizer_output_items(self._h, int(n_in), C.byref(n)), "Channelizer.output_items")
+        return n.value
+
+    def reset(self):
+        """back to the fresh stream: zero history, no carried samples"""
+        check(lib().gr4pm_channelizer_reset(self._h), "Channelizer.reset")
+
+    def process_bulk(self, x, out=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed).  Returns y[n_rows, frames];
+        out: an optional CUDA complex64 [n_rows, >= frames] tensor with contiguous rows and any row stride (a window
+        of a receiver's ring) to write into."""
+        torch = _torch()
+        x = _dev_c64(x, "x")
+        if x.dim() != 1:
+            raise TypeError("x must be one-dimensional")
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        frames = self.output_items(x.numel())
+        if out is None:
+            out = torch.empty((self.n_rows, frames), dtype=torch.complex64, device=x.device)
+        else:
+            out = _dev_c64_rows(out, "out")
+            if out.shape[0] != self.n_rows or out.shape[1] < frames:
+                raise Gr4pmError(f"Channelizer: out is {tuple(out.shape)}, the call makes [{self.n_rows}, {frames}]")
+        n = C.c_size_t(0)
+        check(lib().gr4pm_channelizer_process(self._h, x.data_ptr(), x.numel(), out.data_ptr(), out.stride(0),
+                                              out.shape[1], C.byref(n)), "Channelizer.process")
+        return out[:, : n.value]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _release("gr4pm_channelizer_destroy", self._h)
+                self._h = None
+        except Exception:  # interpreter shutdown
+            pass
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

@@ -1,0 +1,434 @@
+// channelizer.hip -- critically sampled polyphase analysis bank: one wideband c64 stream to M baseband channels at
+// 1/M of the rate, channel-major (out[k][n], the layout gr4pm_multichannel_receiver_submit takes).  The project's own
+// block (the reference is a one-channel modem).  Definition (include/gr4pm_hip.h):
+//     y_k[n] = sum_t h[t] x[n M + M - 1 - t] exp(-2 pi j k (n M + M - 1 - t) / M),   x[i] = 0 for i < 0
+// With t = p M + M - 1 - m the phase depends on m alone, so
+//     u_n[m] = sum_p h[p M + M - 1 - m] x[(n - p) M + m]      (branch sums, p = 0 .. P-1 in that order)
+//     y_k[n] = sum_m u_n[m] exp(-2 pi j k m / M)              (one forward M-point DFT per frame)
+//
+// k_channelize: a workgroup owns T = 4096 / M consecutive frames.
+//   fast form (M = 16, 64, 256; LDS within 64 KiB): the (T + P - 1) M samples it needs go to LDS once (rows of M + 1 items:
+//     the odd row stride keeps the transposed read at the end free of bank conflicts); every thread holds one branch
+//     m and 16 frames, so a tap is loaded once per 16 products; the branch sums replace the staged rows in place.
+//   generic form (any M up to 1024, any P up to 32, or GR4PM_CHANNELIZER=generic at create): the branch sums read the
+//     samples from global memory and only the T frames live in LDS.
+//   Both: decimation-in-frequency radix-2 levels in place in LDS (the fast form does two levels per pass on four
+//   points in registers -- the same butterflies with the same operands, so the two forms agree bit for bit), twiddles
+//   from a table made in double at create; then channel k's T items leave as one contiguous run, lanes on consecutive
+//   items of the row, read from LDS at the bit-reversed column.
+// Every product and sum rounds on its own (EXACT_FLAGS) in an order that depends on (frame, branch) only: a result
+// does not depend on how the stream is cut into calls.
+// k_chan_history: the last (P - 1) M samples plus the incomplete frame move to the handle's other history buffer.
+#include "common.hpp"
+
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+constexpr int kNt = 256;              // threads of a workgroup
+constexpr int kPoints = 4096;         // frame samples a workgroup transforms: T = kPoints / M frames
+constexpr int kPer = kPoints / kNt;   // branch sums per thread
+constexpr size_t kFastSmem = 64 * 1024;
+constexpr size_t kMaxM = 1024, kMaxP = 32;
+
+struct ChanArgs {
+    const float2* hist;     // the H samples in front of in[0]: (P - 1) M of history, then the carried partial frame
+    const float2* in;
+    float2* out;
+    const float* taps_r;    // [P][M]: taps_r[p M + m] = h[p M + M - 1 - m]
+    const float2* twiddle;  // [M / 2]: exp(-2 pi j i / M)
+    const unsigned* select; // rows to write, or null: all M in order
+    size_t H;
+    size_t out_stride;
+    size_t n_frames;
+    unsigned n_rows;
+    unsigned P;
+    unsigned lm;            // log2 M
+};
+
+__device__ __forceinline__ float2 vsample(const ChanArgs& a, size_t v) { return v < a.H ? a.hist[v] : a.in[v - a.H]; }
+
+__device__ __forceinline__ void tap(float2& acc, float h, float2 x)
+{
+    acc.x = acc.x + h * x.x;
+    acc.y = acc.y + h * x.y;
+}
+
+// a, b -> a + b, (a - b) w
+__device__ __forceinline__ void bfly(float2& a, float2& b, float2 w)
+{
+    const float2 s = {a.x + b.x, a.y + b.y};
+    const float2 d = {a.x - b.x, a.y - b.y};
+    a = s;
+    b = float2{d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x};
+}
+
+// LM: log2 M of the fast form (even), 0: the generic form (a.lm)
+template <int LM>
+__global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
+{
+    extern __shared__ float2 s_ch[];
+    const unsigned lm = LM ? LM : a.lm;
+    const unsigned M = 1u << lm, T = kPoints >> lm, RS = M + 1, P = a.P;
+    const unsigned t = threadIdx.x;
+    const size_t f0 = static_cast<size_t>(blockIdx.x) * T;
+    const unsigned Tw = a.n_frames - f0 < T ? static_cast<unsigned>(a.n_frames - f0) : T;
+    float2* s_tw = s_ch;                       // M / 2 twiddles
+    float2* s = s_ch + M / 2;                  // rows of RS items
+    for (unsigned i = t; i < M / 2; i += kNt) s_tw[i] = a.twiddle[i];
+
+    float2 acc[kPer];
+#pragma unroll
+    for (int o = 0; o < kPer; ++o) acc[o] = float2{0.0f, 0.0f};
+    if constexpr (LM != 0) {
+        // row r of the stage: frame f0 + r of the stream that starts (P - 1) frames before this call's first frame
+        const unsigned rows = Tw + P - 1;
+        for (unsigned i = t; i < (T + P - 1) * M; i += kNt) {
+            const unsigned r = i >> lm, m = i & (M - 1);
+            s[r * RS + m] = r < rows ? vsample(a, (f0 + r) * M + m) : float2{0.0f, 0.0f};
+        }
+        __syncthreads();
+        const unsigned m = t & (M - 1), n0 = t >> lm; // kNt is a multiple of M: one branch per thread
+        for (unsigned p = 0; p < P; ++p) {
+            const float h = a.taps_r[p * M + m];
+            const float2* col = s + (n0 + P - 1 - p) * RS + m;
+#pragma unroll
+            for (int o = 0; o < kPer; ++o) tap(acc[o], h, col[o * (kNt >> LM) * RS]);
+        }
+        __syncthreads(); // the stage has been read: the branch sums take its place
+#pragma unroll
+        for (int o = 0; o < kPer; ++o) s[(n0 + o * (kNt >> LM)) * RS + m] = acc[o];
+    } else {
+#pragma unroll
+        for (int o = 0; o < kPer; ++o) {
+            const unsigned idx = o * kNt + t, n = idx >> lm, m = idx & (M - 1);
+            if (n < Tw)
+                for (unsigned p = 0; p < P; ++p)
+                    tap(acc[o], a.taps_r[p * M + m], vsample(a, (f0 + n + P - 1 - p) * M + m));
+            s[n * RS + m] = acc[o];
+        }
+    }
+    __syncthreads();
+
+    if constexpr (LM != 0) {
+#pragma unroll
+        for (int lvl = 0; lvl < LM; lvl += 2) {
+            const unsigned lh = LM - 1 - lvl, h = 1u << lh, hh = h >> 1;
+#pragma unroll
+            for (int e = 0; e < kPoints / 4 / kNt; ++e) {
+                const unsigned q = e * kNt + t, n = q >> (LM - 2), r = q & (M / 4 - 1);
+                const unsigned g = r >> (lh - 1), j = r & (hh - 1);
+                float2* v = s + n * RS + (g << (lh + 1)) + j;
+                float2 a0 = v[0], a1 = v[hh], a2 = v[h], a3 = v[h + hh];
+                const float2 w2 = s_tw[j << (lvl + 1)];
+                bfly(a0, a2, s_tw[j << lvl]);
+                bfly(a1, a3, s_tw[(j + hh) << lvl]);
+                bfly(a0, a1, w2);
+                bfly(a2, a3, w2);
+                v[0] = a0, v[hh] = a1, v[h] = a2, v[h + hh] = a3;
+            }
+            __syncthreads();
+        }
+    } else {
+        for (unsigned lvl = 0; lvl < lm; ++lvl) {
+            const unsigned lh = lm - 1 - lvl, h = 1u << lh;
+#pragma unroll
+            for (int e = 0; e < kPoints / 2 / kNt; ++e) {
+                const unsigned q = e * kNt + t, n = q >> (lm - 1), r = q & (M / 2 - 1);
+                const unsigned g = r >> lh, j = r & (h - 1);
+                float2* v = s + n * RS + (g << (lh + 1)) + j;
+                float2 a0 = v[0], a1 = v[h];
+                bfly(a0, a1, s_tw[j << lvl]);
+                v[0] = a0, v[h] = a1;
+            }
+            __syncthreads();
+        }
+    }
+
+    // X[k] of frame n sits at column bitrev(k); consecutive lanes take consecutive items of one output row
+    const unsigned lt = 12 - lm; // log2 T
+    for (unsigned idx = t; idx < a.n_rows * T; idx += kNt) {
+        const unsigned n = idx & (T - 1), ks = idx >> lt;
+        if (n >= Tw) continue;
+        const unsigned k = a.select ? a.select[ks] : ks;
+        const unsigned rev = __brev(k) >> (32 - lm);
+        a.out[static_cast<size_t>(ks) * a.out_stride + f0 + n] = s[n * RS + rev];
+    }
+}
+
+// the stream's last H_new samples (of hist[0 .. H) followed by in[0 .. n_in)) into the other history buffer
+__global__ __launch_bounds__(256) void k_chan_history(const float2* hist, size_t H, const float2* in, size_t n_in,
+                                                      float2* hist_new, size_t H_new)
+{
+    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= H_new) return;
+    const size_t v = H + n_in - H_new + i;
+    hist_new[i] = v < H ? hist[v] : in[v - H];
+}
+
+bool power_of_two_in_range(size_t M) { return M >= 2 && M <= kMaxM && (M & (M - 1)) == 0; }
+
+size_t smem_fast(size_t M, size_t P) { return (M / 2 + (kPoints / M + P - 1) * (M + 1)) * sizeof(float2); }
+size_t smem_generic(size_t M) { return (M / 2 + (kPoints / M) * (M + 1)) * sizeof(float2); }
+
+// Kaiser-windowed sinc in double: cutoff midway between the band edges, the window's beta from the attenuation that
+// Kaiser's length rule gives for L taps over the transition width; DC gain 1
+gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, std::vector<double>& h)
+{
+    using gr4pm::set_error;
+    if (!power_of_two_in_range(M)) {
+        set_error("channelizer: M must be a power of two in [2, %zu], not %zu", kMaxM, M);
+        return GR4PM_ERR_INVALID;
+    }
+    if (P < 1 || P > kMaxP) {
+        set_error("channelizer: taps per branch must be in [1, %zu], not %zu", kMaxP, P);
+        return GR4PM_ERR_INVALID;
+    }
+    if (!(passband >= 0.0) || !(passband < stopband) || !(passband + stopband < static_cast<double>(M))) {
+        set_error("channelizer: need 0 <= passband < stopband (units of the channel spacing) and a cutoff below fs / 2");
+        return GR4PM_ERR_INVALID;
+    }
+    const size_t L = P * M;
+    const double pi = 3.14159265358979323846;
+    const double dw = 2.0 * pi * (stopband - passband) / static_cast<double>(M);
+    const double A = 2.285 * dw * static_cast<double>(L - 1) + 7.95;
+    const double beta = A > 50.0 ? 0.1102 * (A - 8.7)
+                                 : (A >= 21.0 ? 0.5842 * std::pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
+    const double fc = 0.5 * (passband + stopband) / static_cast<double>(M); // cycles per input sample
+    const double centre = 0.5 * static_cast<double>(L - 1);
+    const double i0b = std::cyl_bessel_i(0.0, beta);
+    h.assign(L, 0.0);
+    double sum = 0.0;
+    for (size_t t = 0; t < L; ++t) {
+        const double u = 2.0 * static_cast<double>(t) / static_cast<double>(L - 1) - 1.0;
+        const double w = std::cyl_bessel_i(0.0, beta * std::sqrt(std::fmax(0.0, 1.0 - u * u))) / i0b;
+        const double x = 2.0 * fc * (static_cast<double>(t) - centre);
+        const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+        h[t] = 2.0 * fc * sinc * w;
+        sum += h[t];
+    }
+    for (double& v : h) v /= sum;
+    return GR4PM_OK;
+}
+
+} // namespace
+
+struct gr4pm_channelizer {
+    size_t M = 0, P = 0, max_frames = 0;
+    unsigned lm = 0, n_rows = 0;
+    bool fast = false, selected = false;
+    size_t carried = 0; // samples of the incomplete frame, < M
+    int cur = 0;        // which history buffer holds the stream's tail
+    hipStream_t stream = nullptr;
+    gr4pm::DevBuf<float> d_taps;
+    gr4pm::DevBuf<float2> d_twiddle, d_hist[2];
+    gr4pm::DevBuf<unsigned> d_select;
+};
+
+using namespace gr4pm;
+
+extern "C" {
+
+gr4pm_status gr4pm_channelizer_taps(size_t n_channels, size_t taps_per_branch, double passband, double stopband, float* out)
+try {
+    if (!out) return GR4PM_ERR_INVALID;
+    std::vector<double> h;
+    GR4PM_TRY(design_taps(n_channels, taps_per_branch, passband, stopband, h));
+    for (size_t t = 0; t < h.size(); ++t) out[t] = static_cast<float>(h[t]);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_channelizer_create(const gr4pm_channelizer_params* p, gr4pm_channelizer** out)
+try {
+    if (!p || !out) return GR4PM_ERR_INVALID;
+    *out = nullptr;
+    const size_t M = p->n_channels, P = p->taps_per_branch;
+    if (!power_of_two_in_range(M)) {
+        set_error("channelizer: M must be a power of two in [2, %zu], not %zu", kMaxM, M);
+        return GR4PM_ERR_INVALID;
+    }
+    if (P < 1 || P > kMaxP) {
+        set_error("channelizer: taps per branch must be in [1, %zu], not %zu", kMaxP, P);
+        return GR4PM_ERR_INVALID;
+    }
+    if (p->max_frames == 0 || p->max_frames > (size_t(1) << 31)) {
+        set_error("channelizer: max_frames must be in [1, 2^31]");
+        return GR4PM_ERR_INVALID;
+    }
+    if (p->n_select > M || (p->n_select && !p->select)) {
+        set_error("channelizer: %zu selected rows of %zu channels", p->n_select, M);
+        return GR4PM_ERR_INVALID;
+    }
+    std::vector<unsigned> sel(p->n_select);
+    {
+        std::vector<char> seen(M, 0);
+        for (size_t i = 0; i < p->n_select; ++i) {
+            const uint32_t k = p->select[i];
+            if (k >= M || seen[k]) {
+                set_error("channelizer: select[%zu] = %u is %s", i, k, k >= M ? "not a channel" : "a duplicate");
+                return GR4PM_ERR_INVALID;
+            }
+            seen[k] = 1;
+            sel[i] = k;
+        }
+    }
+    std::vector<float> taps(P * M);
+    if (p->taps) {
+        for (size_t t = 0; t < P * M; ++t) taps[t] = p->taps[t];
+    } else {
+        std::vector<double> h;
+        GR4PM_TRY(design_taps(M, P, 0.25, 0.75, h));
+        for (size_t t = 0; t < P * M; ++t) taps[t] = static_cast<float>(h[t]);
+    }
+    GR4PM_TRY(require_device());
+    auto* h = new (std::nothrow) gr4pm_channelizer;
+    if (!h) return GR4PM_ERR_NOMEM;
+    auto bail = [&](gr4pm_status st) {
+        delete h;
+        return st;
+    };
+    h->M = M;
+    h->P = P;
+    h->max_frames = p->max_frames;
+    while ((size_t(1) << h->lm) < M) ++h->lm;
+    h->selected = p->n_select != 0;
+    h->n_rows = static_cast<unsigned>(h->selected ? p->n_select : M);
+    h->stream = static_cast<hipStream_t>(p->stream);
+    const char* form = std::getenv("GR4PM_CHANNELIZER"); // "generic": the generic form also where the fast one is built
+    h->fast = (M == 16 || M == 64 || M == 256) && smem_fast(M, P) <= kFastSmem && !(form && !strcmp(form, "generic"));
+    if (form && *form && strcmp(form, "generic") && strcmp(form, "fast")) {
+        set_error("channelizer: GR4PM_CHANNELIZER=%s (generic or fast)", form);
+        return bail(GR4PM_ERR_INVALID);
+    }
+
+    std::vector<float> taps_r(P * M);
+    for (size_t q = 0; q < P; ++q)
+        for (size_t m = 0; m < M; ++m) taps_r[q * M + m] = taps[q * M + M - 1 - m];
+    std::vector<float2> tw(M / 2);
+    for (size_t i = 0; i < M / 2; ++i) {
+        const double ang = -2.0 * 3.14159265358979323846 * static_cast<double>(i) / static_cast<double>(M);
+        tw[i] = float2{static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang))};
+    }
+    // exact where the angle is a multiple of pi / 2 (cos(pi / 2) in double is 6e-17, not 0)
+    tw[0] = float2{1.0f, 0.0f};
+    if (M >= 4) tw[M / 4] = float2{0.0f, -1.0f};
+    gr4pm_status st;
+    if ((st = h->d_taps.alloc(P * M)) != GR4PM_OK || (st = h->d_twiddle.alloc(M / 2)) != GR4PM_OK ||
+        (st = h->d_hist[0].alloc(P * M)) != GR4PM_OK || (st = h->d_hist[1].alloc(P * M)) != GR4PM_OK ||
+        (st = h->d_select.alloc(sel.size())) != GR4PM_OK)
+        return bail(st);
+    if ((st = h->d_taps.upload(taps_r.data(), taps_r.size(), h->stream)) != GR4PM_OK ||
+        (st = h->d_twiddle.upload(tw.data(), tw.size(), h->stream)) != GR4PM_OK ||
+        (st = h->d_hist[0].zero(h->stream)) != GR4PM_OK || (st = h->d_hist[1].zero(h->stream)) != GR4PM_OK)
+        return bail(st);
+    if (!sel.empty() && (st = h->d_select.upload(sel.data(), sel.size(), h->stream)) != GR4PM_OK) return bail(st);
+    const size_t smem = h->fast ? smem_fast(M, P) : smem_generic(M);
+    if (smem > 48 * 1024) { // beyond the default dynamic-LDS window
+        const void* fn = !h->fast ? reinterpret_cast<const void*>(&k_channelize<0>)
+                                  : (M == 16 ? reinterpret_cast<const void*>(&k_channelize<4>)
+                                             : (M == 64 ? reinterpret_cast<const void*>(&k_channelize<6>)
+                                                        : reinterpret_cast<const void*>(&k_channelize<8>)));
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFastSmem)) != hipSuccess) {
+            set_error("channelizer: hipFuncSetAttribute(%zu bytes of LDS) failed", kFastSmem);
+            return bail(GR4PM_ERR_HIP);
+        }
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
+        set_error("channelizer: hipStreamSynchronize failed at create");
+        return bail(GR4PM_ERR_HIP);
+    }
+    *out = h;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+void gr4pm_channelizer_destroy(gr4pm_channelizer* h)
+try {
+    if (!h) return;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+GR4PM_ABI_CATCH_VOID
+
+gr4pm_status gr4pm_channelizer_reset(gr4pm_channelizer* h)
+try {
+    if (!h) return GR4PM_ERR_INVALID;
+    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
+    h->carried = 0;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_channelizer_output_items(const gr4pm_channelizer* h, size_t n_in, size_t* n_frames)
+try {
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    *n_frames = (h->carried + n_in) / h->M;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_channelizer_process(gr4pm_channelizer* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out,
+                                       size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+try {
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    *n_frames = 0;
+    if (n_in > h->max_frames * h->M) {
+        set_error("channelizer: %zu items, the handle was made for %zu frames of %zu", n_in, h->max_frames, h->M);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (n_in == 0) return GR4PM_OK;
+    if (!in) return GR4PM_ERR_INVALID;
+    const size_t M = h->M, P = h->P;
+    const size_t F = (h->carried + n_in) / M;
+    if (F > out_cap_frames) {
+        set_error("channelizer: %zu frames, room for %zu", F, out_cap_frames);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (F && (!out || (h->n_rows > 1 && out_stride < F))) {
+        set_error("channelizer: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
+        return GR4PM_ERR_INVALID;
+    }
+    const size_t H = (P - 1) * M + h->carried;
+    const size_t carried_new = (h->carried + n_in) % M;
+    const size_t H_new = (P - 1) * M + carried_new;
+    const float2* hist = h->d_hist[h->cur].p;
+    const float2* x = reinterpret_cast<const float2*>(in);
+    if (F) {
+        ChanArgs a;
+        a.hist = hist;
+        a.in = x;
+        a.out = reinterpret_cast<float2*>(out);
+        a.taps_r = h->d_taps.p;
+        a.twiddle = h->d_twiddle.p;
+        a.select = h->selected ? h->d_select.p : nullptr;
+        a.H = H;
+        a.out_stride = out_stride;
+        a.n_frames = F;
+        a.n_rows = h->n_rows;
+        a.P = static_cast<unsigned>(P);
+        a.lm = h->lm;
+        const size_t T = kPoints / M;
+        const dim3 grid(static_cast<unsigned>((F + T - 1) / T));
+        if (!h->fast)
+            hipLaunchKernelGGL(k_channelize<0>, grid, dim3(kNt), smem_generic(M), h->stream, a);
+        else if (M == 16)
+            hipLaunchKernelGGL(k_channelize<4>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
+        else if (M == 64)
+            hipLaunchKernelGGL(k_channelize<6>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
+        else
+            hipLaunchKernelGGL(k_channelize<8>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
+    }
+    if (H_new)
+        hipLaunchKernelGGL(k_chan_history, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, h->stream, hist,
+                           H, x, n_in, h->d_hist[1 - h->cur].p, H_new);
+    GR4PM_HIP_TRY(hipGetLastError());
+    h->cur = 1 - h->cur;
+    h->carried = carried_new;
+    *n_frames = F;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+} // extern "C"

@@ -961,6 +961,48 @@ gr4pm_status gr4pm_noise_source_process(gr4pm_noise_source* h, const void* add_i
 /* glibc's logf as the noise kernels compute it (DEVICE x, out; synchronous) */
 gr4pm_status gr4pm_logf(const float* x, size_t n, float* out);
 
+/* ====================================================================================
+ * Channelizer -- critically sampled polyphase analysis bank (the project's own block: the reference
+ * is a one-channel modem).  One wideband c64 stream at fs becomes M channels at fs / M, channel-major,
+ * in the layout gr4pm_multichannel_receiver_submit takes.  With a real prototype h[0 .. P M - 1] and
+ * x[i] = 0 for i < 0 (a fresh handle, or after reset()):
+ *     z_k[i] = x[i] exp(-2 pi j k i / M),   w_k = h * z_k,   y_k[n] = w_k[n M + M - 1]
+ * Channel k sits at +k fs / M (k > M / 2: negative frequencies, as an FFT orders them).  Plain float32,
+ * every product and sum rounded on its own in an order that does not depend on how the stream is cut
+ * into calls.  M: a power of two in [2, 1024]; P: 1 .. 32.  The last (P - 1) M samples and the samples
+ * of an incomplete frame stay in the handle on the device: process() takes any n_in, enqueues on the
+ * handle's stream and does not wait.
+ * ================================================================================== */
+typedef struct gr4pm_channelizer gr4pm_channelizer;
+typedef struct {
+    size_t n_channels;       /* M */
+    size_t taps_per_branch;  /* P */
+    const float* taps;       /* host: P M prototype taps, copied at create (NULL: the default design,
+                                gr4pm_channelizer_taps(M, P, 0.25, 0.75)) */
+    size_t n_select;         /* 0: all M rows in order; else the rows to write, in this order */
+    const uint32_t* select;  /* host: n_select channel numbers, each < M, no duplicates */
+    size_t max_frames;       /* per process() call: n_in <= max_frames M; 1..2^31 */
+    void* stream;            /* hipStream_t (NULL: the default stream) */
+} gr4pm_channelizer_params;
+/* Kaiser-windowed sinc designed in double and rounded to float once, DC gain 1 (host only: no device
+ * needed).  passband / stopband: the band edges in units of the channel spacing fs / M; the cutoff is
+ * midway, the window's beta follows from the attenuation Kaiser's length rule gives P M taps over that
+ * transition.  out: P M floats. */
+gr4pm_status gr4pm_channelizer_taps(size_t n_channels, size_t taps_per_branch, double passband, double stopband,
+                                    float* out);
+gr4pm_status gr4pm_channelizer_create(const gr4pm_channelizer_params* params, gr4pm_channelizer** out);
+void gr4pm_channelizer_destroy(gr4pm_channelizer* h);
+/* back to the fresh stream: zero history, no carried samples */
+gr4pm_status gr4pm_channelizer_reset(gr4pm_channelizer* h);
+/* frames the next process() of n_in samples produces; the state is unchanged */
+gr4pm_status gr4pm_channelizer_output_items(const gr4pm_channelizer* h, size_t n_in, size_t* n_frames);
+/* in: DEVICE, n_in samples (any number; all are consumed).  out: DEVICE, row r (channel r, or
+ * select[r]) at out + r out_stride, out_cap_frames items of room per row.  *n_frames =
+ * floor((carried + n_in) / M) items are written to every row.  More than max_frames M samples or
+ * fewer than *n_frames items of room (GR4PM_ERR_OVERFLOW) are refused before anything is written. */
+gr4pm_status gr4pm_channelizer_process(gr4pm_channelizer* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out,
+                                       size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+
 #ifdef __cplusplus
 }
 #endif
