@@ -2,6 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_receiver_file.cpp (apps/README.md:5-24):
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
+                            [--format {cf32,sc16,sc8,cu8}] [--scale S]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
 FileSource<c64> freads, file_source.hpp:32,53) at 4 samples/symbol, runs the whole receiver on
@@ -14,6 +15,10 @@ followed by the bytes, or are just counted.
 header symbols of every packet are published as one ZeroMQ message of raw complex64 on tcp port 5000 and the payload
 symbols on 5001 (`--zmq-ports H P` for others), where scripts/plot_symbols.py of the reference connects its SUB sockets;
 the library speaks the ZeroMQ wire protocol itself (gr4pm_zmq_pub_*), libzmq is not needed.
+
+`--format sc16 | sc8 | cu8`: the file holds interleaved little-endian int16, int8 or uint8 (I, Q) instead (an SDR
+driver's buffers, SigMF ci16_le / ci8, rtl_sdr's cu8).  It crosses the host link as it is, 4 or 2 bytes per sample, and
+becomes complex64 on the device (gr4pm_iq_unpack, `--scale`: per component, default 2^-15 or 2^-7).
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -36,10 +41,17 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 
-def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None):
+FILE_DTYPES = {"cf32": torch.complex64, "sc16": torch.int16, "sc8": torch.int8, "cu8": torch.uint8}
+
+
+def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
+                 fmt="cf32", scale=None):
     """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures)"""
     pkg = pkg or ge.load_package()
-    n_file = os.path.getsize(path) // 8
+    file_dtype = FILE_DTYPES[fmt]
+    shape = (chunk_items,) if fmt == "cf32" else (chunk_items, 2)  # integer IQ: [items, (I, Q)]
+    item_bytes = 8 if fmt == "cf32" else 2 * file_dtype.itemsize
+    n_file = os.path.getsize(path) // item_bytes
     dev = torch.device("cuda", torch.cuda.current_device())
     # packets_only: nothing between the Costas loop and the packer is written to memory (the app delivers packets); the
     # symbol tap of --zmq needs SyncwordRemove's output stream, i.e. the full form
@@ -48,8 +60,8 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
     if zmq_ports is not None:  # packet_receiver.hpp:163-168
         rx.publish_symbol_pdus(f"tcp://*:{zmq_ports[0]}", f"tcp://*:{zmq_ports[1]}")
     fft = 3072  # smallest batch the receiver takes in this mode (one header window + one FFT block)
-    pinned = [torch.empty(chunk_items, dtype=torch.complex64).pin_memory() for _ in range(2)]
-    staged = [torch.empty(chunk_items, dtype=torch.complex64, device=dev) for _ in range(2)]
+    pinned = [torch.empty(shape, dtype=file_dtype).pin_memory() for _ in range(2)]
+    staged = [torch.empty(shape, dtype=file_dtype, device=dev) for _ in range(2)]
     work = torch.empty(chunk_items + 4096, dtype=torch.complex64, device=dev)
     copy_stream = torch.cuda.Stream()
     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -59,7 +71,7 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
     def load(slot):
         """file -> pinned -> device (asynchronously on the copy stream); returns items read"""
         view = pinned[slot].numpy().view(np.uint8)
-        got = fh.readinto(memoryview(view)) // 8
+        got = fh.readinto(memoryview(view)) // item_bytes
         if got:
             with torch.cuda.stream(copy_stream):
                 staged[slot][:got].copy_(pinned[slot][:got], non_blocking=True)
@@ -86,7 +98,10 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
         nxt = 0
         if got:
             torch.cuda.current_stream().wait_event(events[slot])
-            work[left:left + got].copy_(staged[slot][:got])
+            if fmt == "cf32":
+                work[left:left + got].copy_(staged[slot][:got])
+            else:
+                pkg.iq_unpack(staged[slot][:got], scale, out=work[left:left + got])
             nxt = load(slot ^ 1)          # the next chunk travels while this one is processed
         n = left + got
         if n < fft:
@@ -122,9 +137,12 @@ def main():
     ap.add_argument("--chunk-items", type=int, default=1 << 24)
     ap.add_argument("--zmq", action="store_true", help="publish header / payload symbol PDUs on ZeroMQ PUB sockets (tcp 5000 / 5001)")
     ap.add_argument("--zmq-ports", type=int, nargs=2, metavar=("HEADER", "PAYLOAD"), help="... on these ports instead")
+    ap.add_argument("--format", choices=list(FILE_DTYPES), default="cf32", help="the file's items (default: complex64)")
+    ap.add_argument("--scale", type=float, help="of an integer format's components (default: 2^-15 for sc16, else 2^-7)")
     a = ap.parse_args()
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
-    r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports)
+    r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
+                     fmt=a.format, scale=a.scale)
     print(f"{r['items']} of {r['file_items']} samples in {r['seconds']:.3f} s = {r['items'] / r['seconds'] / 1e6:.1f} Msps "
           f"(file and PCIe included); headers {r['headers']} ({r['invalid_headers']} invalid), packets "
           f"{len(r['packets'])} ({r['crc_failures']} CRC failures), {sum(len(p) for p in r['packets'])} bytes")

@@ -2,6 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_transmitter_pdu.cpp:
 
     packet_transmitter_file.py output_file (--in packets.bin | --random COUNT SIZE) [--stream-mode] [--gap N]
+                               [--format {cf32,sc16,sc8,cu8}] [--gain G]
 
 makes the IQ of PacketTransmitterPdu (packet_transmitter_pdu.hpp:40-355) on the GPU (gr4pm_packet_transmitter) at
 4 samples/symbol and writes it to `output_file` as raw little-endian complex64 (what packet_receiver_file.py reads).
@@ -10,7 +11,11 @@ length followed by the bytes (the format packet_receiver_file.py --out writes), 
 packets of SIZE random bytes (`--seed`).
 
 Burst mode (the default) writes `--gap` samples of silence in front of every burst; `--stream-mode` sends the packets
-back to back through one continuous filter, without ramp-down, flush or burst shaping."""
+back to back through one continuous filter, without ramp-down, flush or burst shaping.
+
+`--format sc16 | sc8 | cu8` writes interleaved little-endian int16, int8 or uint8 (I, Q) instead, what a DAC or
+packet_receiver_file.py --format takes: packed on the device (gr4pm_iq_pack: rint(x * gain), cu8 around 127.5,
+clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is printed at the end."""
 import argparse
 import os
 import sys
@@ -35,9 +40,11 @@ def read_packets(path):
     return packets
 
 
-def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None):
-    """writes the IQ of `packets` to out_path; returns the number of samples written"""
+def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, fmt="cf32", gain=None, stats=None):
+    """writes the IQ of `packets` to out_path; returns the number of samples written.  stats: an optional dict that
+    receives "clipped", the number of components an integer format clipped"""
     pkg = pkg or ge.load_package()
+    clipped = None if fmt == "cf32" else torch.zeros(1, dtype=torch.int64, device="cuda")
     empty = [k for k, p in enumerate(packets) if len(p) == 0]
     if empty:  # PacketIngress refuses them (packet_ingress.hpp:171-172)
         raise ValueError(f"packets of length 0 at {empty[:5]}")
@@ -50,8 +57,12 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None):
             chunk = packets[i:i + batch]
             gaps = None if stream_mode else [gap] * len(chunk)
             x, _, _ = tx.process_bulk(chunk, gaps=gaps)
-            f.write(x.cpu().numpy().tobytes())
             written += x.numel()
+            if fmt != "cf32":
+                x = pkg.iq_pack(x, fmt, gain, clipped=clipped)
+            f.write(x.cpu().numpy().tobytes())
+    if stats is not None and clipped is not None:
+        stats["clipped"] = int(clipped.item())
     return written
 
 
@@ -64,6 +75,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1, help="of --random")
     ap.add_argument("--stream-mode", action="store_true", help="packets back to back, no bursts")
     ap.add_argument("--gap", type=int, default=0, help="samples of silence before each burst (burst mode)")
+    ap.add_argument("--format", choices=["cf32", "sc16", "sc8", "cu8"], default="cf32", help="the file's items (default: complex64)")
+    ap.add_argument("--gain", type=float, help="of an integer format's components (default: 2^15 for sc16, else 2^7)")
     a = ap.parse_args()
     if a.stream_mode and a.gap:
         ap.error("--gap is a burst mode option")
@@ -77,8 +90,10 @@ def main():
         packets = read_packets(a.input_file)
     if not torch.cuda.is_available():
         sys.exit("packet_transmitter_file.py needs a GPU")
-    n = transmit(packets, a.output_file, a.stream_mode, a.gap)
-    print(f"{len(packets)} packets, {n} samples -> {a.output_file}")
+    stats = {}
+    n = transmit(packets, a.output_file, a.stream_mode, a.gap, fmt=a.format, gain=a.gain, stats=stats)
+    print(f"{len(packets)} packets, {n} samples -> {a.output_file}" +
+          (f" ({a.format}, {stats['clipped']} clipped components)" if "clipped" in stats else ""))
 
 
 if __name__ == "__main__":

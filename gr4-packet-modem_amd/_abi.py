@@ -192,6 +192,10 @@ class NoiseSourceParams(C.Structure):
                 ("max_items", C.c_size_t), ("stream", C.c_void_p)]
 
 
+# gr4pm_iq_format: integer IQ items (I then Q, little-endian)
+IQ_SC16, IQ_SC8, IQ_CU8 = 1, 2, 3
+
+
 class ChannelizerParams(C.Structure):
     _fields_ = [("n_channels", C.c_size_t), ("taps_per_branch", C.c_size_t), ("taps", C.c_void_p),
                 ("n_select", C.c_size_t), ("select", C.c_void_p), ("max_frames", C.c_size_t), ("stream", C.c_void_p)]
@@ -260,7 +264,8 @@ EXPORTS = [
     "gr4pm_noise_source_create", "gr4pm_noise_source_destroy", "gr4pm_noise_source_reset",
     "gr4pm_noise_source_set_amplitude", "gr4pm_noise_source_process", "gr4pm_logf",
     "gr4pm_channelizer_taps", "gr4pm_channelizer_create", "gr4pm_channelizer_destroy", "gr4pm_channelizer_reset",
-    "gr4pm_channelizer_output_items", "gr4pm_channelizer_process",
+    "gr4pm_channelizer_output_items", "gr4pm_channelizer_process", "gr4pm_channelizer_process_iq",
+    "gr4pm_iq_unpack", "gr4pm_iq_pack",
 ]
 
 _lib = None
@@ -458,6 +463,9 @@ def lib():
     L.gr4pm_channelizer_reset.argtypes = [vp]
     L.gr4pm_channelizer_output_items.argtypes = [vp, sz, szp]
     L.gr4pm_channelizer_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
+    L.gr4pm_channelizer_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
+    L.gr4pm_iq_unpack.argtypes = [vp, sz, C.c_int, C.c_float, sz, sz, vp, sz, vp]
+    L.gr4pm_iq_pack.argtypes = [vp, sz, sz, sz, C.c_int, C.c_float, vp, sz, vp, vp]
     _lib = L
     return L
 

@@ -1679,6 +1679,86 @@ class Channel:
         return self.noise.process_bulk(y.numel(), add_to=y, out=y)
 
 
+IQ_FORMATS = {"sc16": _abi.IQ_SC16, "sc8": _abi.IQ_SC8, "cu8": _abi.IQ_CU8}
+
+
+def _iq_dtypes():
+    torch = _torch()
+    return {torch.int16: _abi.IQ_SC16, torch.int8: _abi.IQ_SC8, torch.uint8: _abi.IQ_CU8}
+
+
+def _dev_iq(x, what="x"):
+    """integer IQ: a CUDA tensor of dtype int16 (sc16), int8 (sc8) or uint8 (cu8), [n, 2] or [rows, n, 2] with (I, Q)
+    adjacent and the items of a row contiguous; the row stride is free.  Returns (format, rows, n, row stride in items)."""
+    torch = _torch()
+    fmt = _iq_dtypes().get(x.dtype) if isinstance(x, torch.Tensor) else None
+    if fmt is None or not x.is_cuda or x.dim() not in (2, 3) or x.shape[-1] != 2:
+        raise TypeError(f"{what} must be a CUDA int16 / int8 / uint8 tensor of shape [n, 2] or [rows, n, 2]")
+    n = x.shape[-2]
+    if x.numel() and (x.stride(-1) != 1 or (n > 1 and x.stride(-2) != 2)):
+        raise TypeError(f"{what}: the items of a row must be contiguous")
+    if x.dim() == 2:
+        return fmt, 1, n, n
+    if x.shape[0] > 1 and (x.stride(0) % 2 or x.stride(0) < 2 * n):
+        raise TypeError(f"{what}: a row stride of {x.stride(0)} components for rows of {n} items")
+    return fmt, x.shape[0], n, (x.stride(0) // 2 if x.shape[0] > 1 else n)
+
+
+def _dev_c64_iq(x, what):
+    """the complex64 side of a conversion: [n], or [rows, n] with contiguous rows.  Returns (rows, n, row stride)"""
+    torch = _torch()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() in (1, 2)):
+        raise TypeError(f"{what} must be a CUDA complex64 tensor of shape [n] or [rows, n]")
+    if x.dim() == 1:
+        if x.numel() > 1 and x.stride(0) != 1:
+            raise TypeError(f"{what} must be contiguous")
+        return 1, x.shape[0], x.shape[0]
+    x = _dev_c64_rows(x, what)
+    return x.shape[0], x.shape[1], (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+
+
+def iq_unpack(x, scale=None, out=None):
+    """gr4pm_iq_unpack: integer IQ (see _dev_iq: the format follows from the dtype) to complex64 on the device, on the
+    current stream.  Per component float(v) * scale, cu8: (float(v) - 127.5) * scale; scale None: 2^-15 (sc16) or 2^-7.
+    Returns complex64 [n] or [rows, n]; out: an optional tensor of that shape (rows contiguous, any row stride)."""
+    torch = _torch()
+    fmt, rows, n, stride = _dev_iq(x)
+    shape = (n,) if x.dim() == 2 else (rows, n)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.complex64, device=x.device)
+    orows, on, ostride = _dev_c64_iq(out, "out")
+    if tuple(out.shape) != shape:
+        raise Gr4pmError(f"iq_unpack: out is {tuple(out.shape)}, the call makes {shape}")
+    check(lib().gr4pm_iq_unpack(x.data_ptr(), stride, fmt, 0.0 if scale is None else float(scale), rows, n, out.data_ptr(),
+                                ostride, _stream_handle()), "iq_unpack")
+    return out
+
+
+def iq_pack(x, fmt, gain=None, out=None, clipped=None):
+    """gr4pm_iq_pack: complex64 [n] or [rows, n] to integer IQ [n, 2] or [rows, n, 2] on the device, on the current
+    stream.  fmt: "sc16", "sc8" or "cu8".  Per component rint(x * gain) (cu8: rint(x * gain + 127.5)), ties to even,
+    clamped to the type's range, NaN: 0 (cu8: 128); gain None: 2^15 (sc16) or 2^7.  clipped: an optional one-element
+    int64 CUDA tensor the call adds the number of clamped or NaN components to.  out: an optional tensor to write into."""
+    torch = _torch()
+    f = IQ_FORMATS.get(str(fmt).lower())
+    if f is None:
+        raise Gr4pmError(f"iq_pack: unknown format {fmt!r} (sc16, sc8 or cu8)")
+    dtype = {v: k for k, v in _iq_dtypes().items()}[f]
+    rows, n, stride = _dev_c64_iq(x, "x")
+    shape = (n, 2) if x.dim() == 1 else (rows, n, 2)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=x.device)
+    ofmt, orows, on, ostride = _dev_iq(out, "out")
+    if ofmt != f or tuple(out.shape) != shape:
+        raise Gr4pmError(f"iq_pack: out is {out.dtype} {tuple(out.shape)}, the call makes {dtype} {shape}")
+    if clipped is not None and not (isinstance(clipped, torch.Tensor) and clipped.is_cuda and clipped.dtype == torch.int64
+                                    and clipped.numel() == 1):
+        raise TypeError("clipped must be a one-element int64 CUDA tensor")
+    check(lib().gr4pm_iq_pack(x.data_ptr(), stride, rows, n, f, 0.0 if gain is None else float(gain), out.data_ptr(), ostride,
+                              None if clipped is None else clipped.data_ptr(), _stream_handle()), "iq_pack")
+    return out
+
+
 def channelizer_taps(n_channels, taps_per_branch=12, passband=0.25, stopband=0.75):
     """gr4pm_channelizer_taps: the Channelizer's prototype low-pass, a Kaiser-windowed sinc of taps_per_branch *
     n_channels float32 taps with DC gain 1 (host only: works without a GPU).  passband / stopband: the band edges in
@@ -1734,17 +1814,28 @@ class Channelizer:
         """back to the fresh stream: zero history, no carried samples"""
         check(lib().gr4pm_channelizer_reset(self._h), "Channelizer.reset")
 
-    def process_bulk(self, x, out=None):
-        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed).  Returns y[n_rows, frames];
-        out: an optional CUDA complex64 [n_rows, >= frames] tensor with contiguous rows and any row stride (a window
-        of a receiver's ring) to write into."""
+    def process_bulk(self, x, out=None, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ: an int16 (sc16),
+        int8 (sc8) or uint8 (cu8) CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it
+        (gr4pm_channelizer_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns
+        y[n_rows, frames]; out: an optional CUDA complex64 [n_rows, >= frames] tensor with contiguous rows and any row
+        stride (a window of a receiver's ring) to write into."""
         torch = _torch()
-        x = _dev_c64(x, "x")
-        if x.dim() != 1:
-            raise TypeError("x must be one-dimensional")
+        fmt = None
+        if isinstance(x, torch.Tensor) and x.dtype in _iq_dtypes():
+            fmt, rows, n_in, _ = _dev_iq(x)
+            if x.dim() != 2:
+                raise TypeError("x must be [n, 2]")
+        else:
+            if scale is not None:
+                raise TypeError("scale applies to integer IQ only")
+            x = _dev_c64(x, "x")
+            if x.dim() != 1:
+                raise TypeError("x must be one-dimensional")
+            n_in = x.numel()
         if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
             _inputs_ready(x)  # made on another stream than the handle's
-        frames = self.output_items(x.numel())
+        frames = self.output_items(n_in)
         if out is None:
             out = torch.empty((self.n_rows, frames), dtype=torch.complex64, device=x.device)
         else:
@@ -1752,8 +1843,13 @@ class Channelizer:
             if out.shape[0] != self.n_rows or out.shape[1] < frames:
                 raise Gr4pmError(f"Channelizer: out is {tuple(out.shape)}, the call makes [{self.n_rows}, {frames}]")
         n = C.c_size_t(0)
-        check(lib().gr4pm_channelizer_process(self._h, x.data_ptr(), x.numel(), out.data_ptr(), out.stride(0),
-                                              out.shape[1], C.byref(n)), "Channelizer.process")
+        if fmt is None:
+            check(lib().gr4pm_channelizer_process(self._h, x.data_ptr(), n_in, out.data_ptr(), out.stride(0),
+                                                  out.shape[1], C.byref(n)), "Channelizer.process")
+        else:
+            check(lib().gr4pm_channelizer_process_iq(self._h, x.data_ptr(), fmt, 0.0 if scale is None else float(scale), n_in,
+                                                     out.data_ptr(), out.stride(0), out.shape[1], C.byref(n)),
+                  "Channelizer.process_iq")
         return out[:, : n.value]
 
     def __del__(self):

@@ -19,12 +19,18 @@
 // Every product and sum rounds on its own (EXACT_FLAGS) in an order that depends on (frame, branch) only: a result
 // does not depend on how the stream is cut into calls.
 // k_chan_history: the last (P - 1) M samples plus the incomplete frame move to the handle's other history buffer.
-#include "common.hpp"
+// Integer input (gr4pm_channelizer_process_iq): both kernels are templated on the input format and convert where a
+// sample enters them -- the load into the stage, vsample(), the history's tail -- with iq_format.hpp's unpack_item(),
+// the very expression gr4pm_iq_unpack evaluates.  The stage, the history and everything behind them stay complex64, so
+// the result is that of process() on the unpacked samples bit for bit, and calls of any format mix on one handle.
+#include "iq_format.hpp"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace {
+
+namespace iq = gr4pm::iq;
 
 constexpr int kNt = 256;              // threads of a workgroup
 constexpr int kPoints = 4096;         // frame samples a workgroup transforms: T = kPoints / M frames
@@ -34,7 +40,7 @@ constexpr size_t kMaxM = 1024, kMaxP = 32;
 
 struct ChanArgs {
     const float2* hist;     // the H samples in front of in[0]: (P - 1) M of history, then the carried partial frame
-    const float2* in;
+    const void* in;         // complex64, or items of the kernel's integer format
     float2* out;
     const float* taps_r;    // [P][M]: taps_r[p M + m] = h[p M + M - 1 - m]
     const float2* twiddle;  // [M / 2]: exp(-2 pi j i / M)
@@ -45,9 +51,17 @@ struct ChanArgs {
     unsigned n_rows;
     unsigned P;
     unsigned lm;            // log2 M
+    float scale;            // of an integer format's unpack
 };
 
-__device__ __forceinline__ float2 vsample(const ChanArgs& a, size_t v) { return v < a.H ? a.hist[v] : a.in[v - a.H]; }
+template <int F>
+__device__ __forceinline__ float2 vsample(const ChanArgs& a, size_t v)
+{
+    if constexpr (F == iq::kC64)
+        return v < a.H ? a.hist[v] : static_cast<const float2*>(a.in)[v - a.H];
+    else
+        return v < a.H ? a.hist[v] : iq::unpack_item<F>(iq::load_item<F>(a.in, v - a.H), a.scale);
+}
 
 __device__ __forceinline__ void tap(float2& acc, float h, float2 x)
 {
@@ -64,8 +78,8 @@ __device__ __forceinline__ void bfly(float2& a, float2& b, float2 w)
     b = float2{d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x};
 }
 
-// LM: log2 M of the fast form (even), 0: the generic form (a.lm)
-template <int LM>
+// LM: log2 M of the fast form (even), 0: the generic form (a.lm); F: the input's format (iq::kC64: complex64)
+template <int LM, int F>
 __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
 {
     extern __shared__ float2 s_ch[];
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
         const unsigned rows = Tw + P - 1;
         for (unsigned i = t; i < (T + P - 1) * M; i += kNt) {
             const unsigned r = i >> lm, m = i & (M - 1);
-            s[r * RS + m] = r < rows ? vsample(a, (f0 + r) * M + m) : float2{0.0f, 0.0f};
+            s[r * RS + m] = r < rows ? vsample<F>(a, (f0 + r) * M + m) : float2{0.0f, 0.0f};
         }
         __syncthreads();
         const unsigned m = t & (M - 1), n0 = t >> lm; // kNt is a multiple of M: one branch per thread
@@ -105,7 +119,7 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
             const unsigned idx = o * kNt + t, n = idx >> lm, m = idx & (M - 1);
             if (n < Tw)
                 for (unsigned p = 0; p < P; ++p)
-                    tap(acc[o], a.taps_r[p * M + m], vsample(a, (f0 + n + P - 1 - p) * M + m));
+                    tap(acc[o], a.taps_r[p * M + m], vsample<F>(a, (f0 + n + P - 1 - p) * M + m));
             s[n * RS + m] = acc[o];
         }
     }
@@ -158,13 +172,17 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
 }
 
 // the stream's last H_new samples (of hist[0 .. H) followed by in[0 .. n_in)) into the other history buffer
-__global__ __launch_bounds__(256) void k_chan_history(const float2* hist, size_t H, const float2* in, size_t n_in,
+template <int F>
+__global__ __launch_bounds__(256) void k_chan_history(const float2* hist, size_t H, const void* in, size_t n_in, float scale,
                                                       float2* hist_new, size_t H_new)
 {
     const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= H_new) return;
     const size_t v = H + n_in - H_new + i;
-    hist_new[i] = v < H ? hist[v] : in[v - H];
+    if constexpr (F == iq::kC64)
+        hist_new[i] = v < H ? hist[v] : static_cast<const float2*>(in)[v - H];
+    else
+        hist_new[i] = v < H ? hist[v] : iq::unpack_item<F>(iq::load_item<F>(in, v - H), scale);
 }
 
 bool power_of_two_in_range(size_t M) { return M >= 2 && M <= kMaxM && (M & (M - 1)) == 0; }
@@ -212,6 +230,28 @@ gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, s
     return GR4PM_OK;
 }
 
+template <int F>
+const void* channelize_fn(bool fast, size_t M)
+{
+    return !fast ? reinterpret_cast<const void*>(&k_channelize<0, F>)
+                 : (M == 16 ? reinterpret_cast<const void*>(&k_channelize<4, F>)
+                            : (M == 64 ? reinterpret_cast<const void*>(&k_channelize<6, F>)
+                                       : reinterpret_cast<const void*>(&k_channelize<8, F>)));
+}
+
+// (channelize_fn() is the one place that maps a form and a size to an instantiation)
+template <int F>
+void launch(bool fast, size_t M, size_t P, dim3 grid, hipStream_t s, const ChanArgs& a, size_t n_in, float2* hist_new, size_t H_new)
+{
+    if (a.n_frames) {
+        void* args[] = {const_cast<ChanArgs*>(&a)};
+        (void)hipLaunchKernel(channelize_fn<F>(fast, M), grid, dim3(kNt), args, fast ? smem_fast(M, P) : smem_generic(M), s);
+    }
+    if (H_new)
+        hipLaunchKernelGGL(k_chan_history<F>, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, s, a.hist, a.H, a.in,
+                           n_in, a.scale, hist_new, H_new);
+}
+
 } // namespace
 
 struct gr4pm_channelizer {
@@ -227,6 +267,64 @@ struct gr4pm_channelizer {
 };
 
 using namespace gr4pm;
+
+// process() and process_iq(): format iq::kC64 for complex64 samples
+static gr4pm_status process_any(gr4pm_channelizer* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+{
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    *n_frames = 0;
+    if (n_in > h->max_frames * h->M) {
+        set_error("channelizer: %zu items, the handle was made for %zu frames of %zu", n_in, h->max_frames, h->M);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (n_in == 0) return GR4PM_OK;
+    if (!in) return GR4PM_ERR_INVALID;
+    const size_t M = h->M, P = h->P;
+    const size_t F = (h->carried + n_in) / M;
+    if (F > out_cap_frames) {
+        set_error("channelizer: %zu frames, room for %zu", F, out_cap_frames);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (F && (!out || (h->n_rows > 1 && out_stride < F))) {
+        set_error("channelizer: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
+        return GR4PM_ERR_INVALID;
+    }
+    const size_t H = (P - 1) * M + h->carried;
+    const size_t carried_new = (h->carried + n_in) % M;
+    const size_t H_new = (P - 1) * M + carried_new;
+    const float2* hist = h->d_hist[h->cur].p;
+    ChanArgs a;
+    a.hist = hist;
+    a.in = in;
+    a.out = reinterpret_cast<float2*>(out);
+    a.taps_r = h->d_taps.p;
+    a.twiddle = h->d_twiddle.p;
+    a.select = h->selected ? h->d_select.p : nullptr;
+    a.H = H;
+    a.out_stride = out_stride;
+    a.n_frames = F;
+    a.n_rows = h->n_rows;
+    a.P = static_cast<unsigned>(P);
+    a.lm = h->lm;
+    a.scale = scale;
+    const size_t T = kPoints / M;
+    const dim3 grid(static_cast<unsigned>((F + T - 1) / T));
+    float2* hist_new = h->d_hist[1 - h->cur].p;
+    if (format == GR4PM_IQ_SC16)
+        launch<GR4PM_IQ_SC16>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
+    else if (format == GR4PM_IQ_SC8)
+        launch<GR4PM_IQ_SC8>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
+    else if (format == GR4PM_IQ_CU8)
+        launch<GR4PM_IQ_CU8>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
+    else
+        launch<iq::kC64>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
+    GR4PM_HIP_TRY(hipGetLastError());
+    h->cur = 1 - h->cur;
+    h->carried = carried_new;
+    *n_frames = F;
+    return GR4PM_OK;
+}
 
 extern "C" {
 
@@ -326,14 +424,13 @@ try {
     if (!sel.empty() && (st = h->d_select.upload(sel.data(), sel.size(), h->stream)) != GR4PM_OK) return bail(st);
     const size_t smem = h->fast ? smem_fast(M, P) : smem_generic(M);
     if (smem > 48 * 1024) { // beyond the default dynamic-LDS window
-        const void* fn = !h->fast ? reinterpret_cast<const void*>(&k_channelize<0>)
-                                  : (M == 16 ? reinterpret_cast<const void*>(&k_channelize<4>)
-                                             : (M == 64 ? reinterpret_cast<const void*>(&k_channelize<6>)
-                                                        : reinterpret_cast<const void*>(&k_channelize<8>)));
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFastSmem)) != hipSuccess) {
-            set_error("channelizer: hipFuncSetAttribute(%zu bytes of LDS) failed", kFastSmem);
-            return bail(GR4PM_ERR_HIP);
-        }
+        const void* fns[] = {channelize_fn<iq::kC64>(h->fast, M), channelize_fn<GR4PM_IQ_SC16>(h->fast, M),
+                             channelize_fn<GR4PM_IQ_SC8>(h->fast, M), channelize_fn<GR4PM_IQ_CU8>(h->fast, M)};
+        for (const void* fn : fns)
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFastSmem)) != hipSuccess) {
+                set_error("channelizer: hipFuncSetAttribute(%zu bytes of LDS) failed", kFastSmem);
+                return bail(GR4PM_ERR_HIP);
+            }
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
         set_error("channelizer: hipStreamSynchronize failed at create");
@@ -372,62 +469,19 @@ GR4PM_ABI_CATCH
 gr4pm_status gr4pm_channelizer_process(gr4pm_channelizer* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out,
                                        size_t out_stride, size_t out_cap_frames, size_t* n_frames)
 try {
-    if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    *n_frames = 0;
-    if (n_in > h->max_frames * h->M) {
-        set_error("channelizer: %zu items, the handle was made for %zu frames of %zu", n_in, h->max_frames, h->M);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (n_in == 0) return GR4PM_OK;
-    if (!in) return GR4PM_ERR_INVALID;
-    const size_t M = h->M, P = h->P;
-    const size_t F = (h->carried + n_in) / M;
-    if (F > out_cap_frames) {
-        set_error("channelizer: %zu frames, room for %zu", F, out_cap_frames);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (F && (!out || (h->n_rows > 1 && out_stride < F))) {
-        set_error("channelizer: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
+    return process_any(h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_channelizer_process_iq(gr4pm_channelizer* h, const void* in, int format, float scale, size_t n_in,
+                                          gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+try {
+    if (!iq::valid(format)) {
+        set_error("channelizer: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
         return GR4PM_ERR_INVALID;
     }
-    const size_t H = (P - 1) * M + h->carried;
-    const size_t carried_new = (h->carried + n_in) % M;
-    const size_t H_new = (P - 1) * M + carried_new;
-    const float2* hist = h->d_hist[h->cur].p;
-    const float2* x = reinterpret_cast<const float2*>(in);
-    if (F) {
-        ChanArgs a;
-        a.hist = hist;
-        a.in = x;
-        a.out = reinterpret_cast<float2*>(out);
-        a.taps_r = h->d_taps.p;
-        a.twiddle = h->d_twiddle.p;
-        a.select = h->selected ? h->d_select.p : nullptr;
-        a.H = H;
-        a.out_stride = out_stride;
-        a.n_frames = F;
-        a.n_rows = h->n_rows;
-        a.P = static_cast<unsigned>(P);
-        a.lm = h->lm;
-        const size_t T = kPoints / M;
-        const dim3 grid(static_cast<unsigned>((F + T - 1) / T));
-        if (!h->fast)
-            hipLaunchKernelGGL(k_channelize<0>, grid, dim3(kNt), smem_generic(M), h->stream, a);
-        else if (M == 16)
-            hipLaunchKernelGGL(k_channelize<4>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
-        else if (M == 64)
-            hipLaunchKernelGGL(k_channelize<6>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
-        else
-            hipLaunchKernelGGL(k_channelize<8>, grid, dim3(kNt), smem_fast(M, P), h->stream, a);
-    }
-    if (H_new)
-        hipLaunchKernelGGL(k_chan_history, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, h->stream, hist,
-                           H, x, n_in, h->d_hist[1 - h->cur].p, H_new);
-    GR4PM_HIP_TRY(hipGetLastError());
-    h->cur = 1 - h->cur;
-    h->carried = carried_new;
-    *n_frames = F;
-    return GR4PM_OK;
+    return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
+                       n_frames);
 }
 GR4PM_ABI_CATCH
 

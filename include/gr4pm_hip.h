@@ -1002,6 +1002,42 @@ gr4pm_status gr4pm_channelizer_output_items(const gr4pm_channelizer* h, size_t n
  * fewer than *n_frames items of room (GR4PM_ERR_OVERFLOW) are refused before anything is written. */
 gr4pm_status gr4pm_channelizer_process(gr4pm_channelizer* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out,
                                        size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+/* in: DEVICE, n_in items of an integer IQ format (gr4pm_iq_format below; scale 0: the format's default).
+ * The same contract as gr4pm_channelizer_process, and its result on gr4pm_iq_unpack(in) bit for bit: the
+ * samples are converted where they enter the kernel, the handle's history stays complex64, so calls of
+ * any format may be mixed on one handle. */
+gr4pm_status gr4pm_channelizer_process_iq(gr4pm_channelizer* h, const void* in, int format, float scale, size_t n_in,
+                                          gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+
+/* ====================================================================================
+ * Integer IQ formats (the project's own block: the reference moves complex64 only).  An item is one
+ * complex sample, I then Q, little-endian integers.
+ *     format          item         unpack, per component            default scale   default gain
+ *     GR4PM_IQ_SC16   2 x int16    float(v) * scale                 2^-15           2^15
+ *     GR4PM_IQ_SC8    2 x int8     float(v) * scale                 2^-7            2^7
+ *     GR4PM_IQ_CU8    2 x uint8    (float(v) - 127.5f) * scale      2^-7            2^7
+ * Every float operation rounds on its own; the conversion and the offset are exact, so unpack is one
+ * rounding.  pack, per component: t = x * gain (cu8: then t = t + 127.5f), r = rintf(t) (ties to even),
+ * r clamped to the type's range; NaN gives 0 (cu8: 128).  A component that was clamped or was NaN counts
+ * as clipped.  A scale or gain of 0 means the default.
+ * ================================================================================== */
+typedef enum {
+    GR4PM_IQ_SC16 = 1,
+    GR4PM_IQ_SC8 = 2,
+    GR4PM_IQ_CU8 = 3
+} gr4pm_iq_format;
+/* in, out: DEVICE, `rows` rows of n items at strides (in items) of in_stride and out_stride; rows == 1 is
+ * the plain stream, [rows][stride] the multi-channel receiver's layout.  Pointers need the alignment of
+ * their item only (2 or 4 bytes; 8 for complex64).  in and out must not overlap (not checked).
+ * Stateless: enqueues on `stream` (hipStream_t, NULL: the default stream) and does not wait.  An unknown
+ * format, a NULL pointer with n > 0 or a stride below n (GR4PM_ERR_INVALID) are refused before any HIP
+ * call. */
+gr4pm_status gr4pm_iq_unpack(const void* in, size_t in_stride, int format, float scale, size_t rows, size_t n,
+                             gr4pm_c64* out, size_t out_stride, void* stream);
+/* clipped: NULL, or a DEVICE counter the call ADDS the number of clipped components to (one atomic per
+ * workgroup that clipped anything). */
+gr4pm_status gr4pm_iq_pack(const gr4pm_c64* in, size_t in_stride, size_t rows, size_t n, int format, float gain,
+                           void* out, size_t out_stride, unsigned long long* clipped, void* stream);
 
 #ifdef __cplusplus
 }
