@@ -2,7 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_receiver_file.cpp (apps/README.md:5-24):
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
-                            [--format {cf32,sc16,sc8,cu8}] [--scale S]
+                            [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE --decimate D]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
 FileSource<c64> freads, file_source.hpp:32,53) at 4 samples/symbol, runs the whole receiver on
@@ -19,6 +19,11 @@ the library speaks the ZeroMQ wire protocol itself (gr4pm_zmq_pub_*), libzmq is 
 `--format sc16 | sc8 | cu8`: the file holds interleaved little-endian int16, int8 or uint8 (I, Q) instead (an SDR
 driver's buffers, SigMF ci16_le / ci8, rtl_sdr's cu8).  It crosses the host link as it is, 4 or 2 bytes per sample, and
 becomes complex64 on the device (gr4pm_iq_unpack, `--scale`: per component, default 2^-15 or 2^-7).
+
+`--tune F --decimate D`: the file is a wideband recording with the modem's carrier F cycles per file sample off centre
+and D times the modem's rate: it goes through a one-channel `Ddc` (gr4pm_ddc: mix by -F, low-pass, keep every D-th
+sample) in front of the receiver.  Combines with `--format` (the Ddc reads the integers itself).  The
+counts are then in samples at the receiver's rate.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -45,7 +50,7 @@ FILE_DTYPES = {"cf32": torch.complex64, "sc16": torch.int16, "sc8": torch.int8, 
 
 
 def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
-                 fmt="cf32", scale=None):
+                 fmt="cf32", scale=None, tune=None, decimate=None):
     """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures)"""
     pkg = pkg or ge.load_package()
     file_dtype = FILE_DTYPES[fmt]
@@ -59,6 +64,9 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
                                   tags_cap=chunk_items // 768 + 64, decode_headers=True, packets_only=zmq_ports is None)
     if zmq_ports is not None:  # packet_receiver.hpp:163-168
         rx.publish_symbol_pdus(f"tcp://*:{zmq_ports[0]}", f"tcp://*:{zmq_ports[1]}")
+    ddc = None
+    if tune is not None or decimate is not None:
+        ddc = pkg.Ddc([0.0 if tune is None else tune], 1 if decimate is None else decimate, max_frames=chunk_items)
     fft = 3072  # smallest batch the receiver takes in this mode (one header window + one FFT block)
     pinned = [torch.empty(shape, dtype=file_dtype).pin_memory() for _ in range(2)]
     staged = [torch.empty(shape, dtype=file_dtype, device=dev) for _ in range(2)]
@@ -98,7 +106,10 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
         nxt = 0
         if got:
             torch.cuda.current_stream().wait_event(events[slot])
-            if fmt == "cf32":
+            if ddc is not None:
+                got = ddc.process_bulk(staged[slot][:got], out=work[left:left + got].unsqueeze(0),
+                                       scale=None if fmt == "cf32" else scale).shape[1]
+            elif fmt == "cf32":
                 work[left:left + got].copy_(staged[slot][:got])
             else:
                 pkg.iq_unpack(staged[slot][:got], scale, out=work[left:left + got])
@@ -139,10 +150,12 @@ def main():
     ap.add_argument("--zmq-ports", type=int, nargs=2, metavar=("HEADER", "PAYLOAD"), help="... on these ports instead")
     ap.add_argument("--format", choices=list(FILE_DTYPES), default="cf32", help="the file's items (default: complex64)")
     ap.add_argument("--scale", type=float, help="of an integer format's components (default: 2^-15 for sc16, else 2^-7)")
+    ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Ddc in front)")
+    ap.add_argument("--decimate", type=int, metavar="D", help="file samples per receiver sample (a Ddc in front)")
     a = ap.parse_args()
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
-                     fmt=a.format, scale=a.scale)
+                     fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate)
     print(f"{r['items']} of {r['file_items']} samples in {r['seconds']:.3f} s = {r['items'] / r['seconds'] / 1e6:.1f} Msps "
           f"(file and PCIe included); headers {r['headers']} ({r['invalid_headers']} invalid), packets "
           f"{len(r['packets'])} ({r['crc_failures']} CRC failures), {sum(len(p) for p in r['packets'])} bytes")

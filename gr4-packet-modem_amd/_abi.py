@@ -201,6 +201,11 @@ class ChannelizerParams(C.Structure):
                 ("n_select", C.c_size_t), ("select", C.c_void_p), ("max_frames", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class DdcParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("decimation", C.c_size_t), ("frequencies", C.c_void_p), ("taps", C.c_void_p),
+                ("n_taps", C.c_size_t), ("max_frames", C.c_size_t), ("start_index", C.c_uint64), ("stream", C.c_void_p)]
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -266,6 +271,8 @@ EXPORTS = [
     "gr4pm_channelizer_taps", "gr4pm_channelizer_create", "gr4pm_channelizer_destroy", "gr4pm_channelizer_reset",
     "gr4pm_channelizer_output_items", "gr4pm_channelizer_process", "gr4pm_channelizer_process_iq",
     "gr4pm_iq_unpack", "gr4pm_iq_pack",
+    "gr4pm_ddc_taps", "gr4pm_ddc_create", "gr4pm_ddc_destroy", "gr4pm_ddc_reset", "gr4pm_ddc_output_items",
+    "gr4pm_ddc_frequencies", "gr4pm_ddc_process", "gr4pm_ddc_process_iq",
 ]
 
 _lib = None
@@ -464,6 +471,15 @@ def lib():
     L.gr4pm_channelizer_output_items.argtypes = [vp, sz, szp]
     L.gr4pm_channelizer_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
     L.gr4pm_channelizer_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
+    L.gr4pm_ddc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
+    L.gr4pm_ddc_create.argtypes = [C.POINTER(DdcParams), C.POINTER(vp)]
+    L.gr4pm_ddc_destroy.argtypes = [vp]
+    L.gr4pm_ddc_destroy.restype = None
+    L.gr4pm_ddc_reset.argtypes = [vp]
+    L.gr4pm_ddc_output_items.argtypes = [vp, sz, szp]
+    L.gr4pm_ddc_frequencies.argtypes = [vp, vp]
+    L.gr4pm_ddc_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
+    L.gr4pm_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
     L.gr4pm_iq_unpack.argtypes = [vp, sz, C.c_int, C.c_float, sz, sz, vp, sz, vp]
     L.gr4pm_iq_pack.argtypes = [vp, sz, sz, sz, C.c_int, C.c_float, vp, sz, vp, vp]
     _lib = L

@@ -1861,6 +1861,112 @@ class Channelizer:
             pass
 
 
+def ddc_taps(decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
+    """gr4pm_ddc_taps: the Ddc's prototype low-pass, the Kaiser design of channelizer_taps with taps_per_phase *
+    decimation float32 taps for any integer decimation, DC gain 1 (host only: works without a GPU).  passband /
+    stopband: the band edges in units of the output rate.  For a power-of-two decimation the floats are those of
+    channelizer_taps."""
+    n = int(decimation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_ddc_taps(int(decimation), int(taps_per_phase), float(passband), float(stopband), _np_ptr(out)),
+          "ddc_taps")
+    return out[:n]
+
+
+class Ddc:
+    """gr4pm_ddc: tunable down-converter.  One wideband complex64 stream at fs becomes len(frequencies) channels at
+    fs / decimation: row k is the band centred on frequencies[k] (cycles per input sample, any real value, quantised to
+    fs / 2^32: .frequencies holds the values in use, folded to [-0.5, 0.5)), mixed to 0, low-pass filtered and
+    decimated by any integer 1 .. 1024, so that NativeMultiChannelReceiver.submit(Ddc(...).process_bulk(x)) receives
+    carriers that sit on no grid.  taps: 1 .. 8192 float32 prototype taps of any length (None: ddc_taps(decimation,
+    taps_per_phase)).  start_index: the absolute index of the first sample (the phase of a channel follows from the
+    absolute index in integer arithmetic, exactly, at any stream position).  process_bulk() takes any number of
+    samples; the filter history and the samples of an incomplete frame stay on the device.  Frequencies are fixed: make
+    another Ddc to retune.  The handle works on the stream that is current when it is made."""
+
+    def __init__(self, frequencies, decimation, taps=None, taps_per_phase=12, start_index=0, max_frames=1 << 22):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
+        if f.ndim != 1:
+            raise Gr4pmError("Ddc: frequencies must be a list of numbers")
+        self.n_channels = self.n_rows = int(f.size)
+        self.decimation = int(decimation)
+        if taps is not None:
+            self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            if not self.taps.size:
+                raise Gr4pmError("Ddc: the prototype has 1 .. 8192 taps, not 0")
+        else:
+            self.taps = ddc_taps(self.decimation, taps_per_phase)
+        self.start_index = int(start_index)
+        if not 0 <= self.start_index < 1 << 64:
+            raise Gr4pmError("Ddc: start_index must fit 64 unsigned bits")
+        self.max_frames = int(max_frames)
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.DdcParams(self.n_channels, self.decimation, _np_ptr(f) if f.size else None, _np_ptr(self.taps),
+                           self.taps.size, self.max_frames, self.start_index, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_ddc_create(C.byref(p), C.byref(self._h)), "Ddc")
+        q = np.zeros(self.n_channels, dtype=np.float64)
+        check(lib().gr4pm_ddc_frequencies(self._h, _np_ptr(q)), "Ddc.frequencies")
+        self.frequencies = q
+
+    def output_items(self, n_in):
+        """frames (items per row) the next process_bulk() of n_in samples produces"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_ddc_output_items(self._h, int(n_in), C.byref(n)), "Ddc.output_items")
+        return n.value
+
+    def reset(self):
+        """back to start_index: zero history, no carried samples"""
+        check(lib().gr4pm_ddc_reset(self._h), "Ddc.reset")
+
+    def process_bulk(self, x, out=None, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ: an int16 (sc16),
+        int8 (sc8) or uint8 (cu8) CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it
+        (gr4pm_ddc_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns
+        y[n_channels, frames]; out: an optional CUDA complex64 [n_channels, >= frames] tensor with contiguous rows and
+        any row stride (a window of a receiver's ring) to write into."""
+        torch = _torch()
+        fmt = None
+        if isinstance(x, torch.Tensor) and x.dtype in _iq_dtypes():
+            fmt, rows, n_in, _ = _dev_iq(x)
+            if x.dim() != 2:
+                raise TypeError("x must be [n, 2]")
+        else:
+            if scale is not None:
+                raise TypeError("scale applies to integer IQ only")
+            x = _dev_c64(x, "x")
+            if x.dim() != 1:
+                raise TypeError("x must be one-dimensional")
+            n_in = x.numel()
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        frames = self.output_items(n_in)
+        if out is None:
+            out = torch.empty((self.n_channels, frames), dtype=torch.complex64, device=x.device)
+        else:
+            out = _dev_c64_rows(out, "out")
+            if out.shape[0] != self.n_channels or out.shape[1] < frames:
+                raise Gr4pmError(f"Ddc: out is {tuple(out.shape)}, the call makes [{self.n_channels}, {frames}]")
+        n = C.c_size_t(0)
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        if fmt is None:
+            check(lib().gr4pm_ddc_process(self._h, x.data_ptr(), n_in, out.data_ptr(), stride, out.shape[1], C.byref(n)),
+                  "Ddc.process")
+        else:
+            check(lib().gr4pm_ddc_process_iq(self._h, x.data_ptr(), fmt, 0.0 if scale is None else float(scale), n_in,
+                                             out.data_ptr(), stride, out.shape[1], C.byref(n)), "Ddc.process_iq")
+        return out[:, : n.value]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _release("gr4pm_ddc_destroy", self._h)
+                self._h = None
+        except Exception:  # interpreter shutdown
+            pass
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

@@ -24,6 +24,7 @@
 // the very expression gr4pm_iq_unpack evaluates.  The stage, the history and everything behind them stay complex64, so
 // the result is that of process() on the unpacked samples bit for bit, and calls of any format mix on one handle.
 #include "iq_format.hpp"
+#include "kaiser_design.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -190,8 +191,7 @@ bool power_of_two_in_range(size_t M) { return M >= 2 && M <= kMaxM && (M & (M - 
 size_t smem_fast(size_t M, size_t P) { return (M / 2 + (kPoints / M + P - 1) * (M + 1)) * sizeof(float2); }
 size_t smem_generic(size_t M) { return (M / 2 + (kPoints / M) * (M + 1)) * sizeof(float2); }
 
-// Kaiser-windowed sinc in double: cutoff midway between the band edges, the window's beta from the attenuation that
-// Kaiser's length rule gives for L taps over the transition width; DC gain 1
+// the checks of the channelizer's design; the design itself is kaiser_design.hpp's (shared with ddc.hip)
 gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, std::vector<double>& h)
 {
     using gr4pm::set_error;
@@ -207,26 +207,7 @@ gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, s
         set_error("channelizer: need 0 <= passband < stopband (units of the channel spacing) and a cutoff below fs / 2");
         return GR4PM_ERR_INVALID;
     }
-    const size_t L = P * M;
-    const double pi = 3.14159265358979323846;
-    const double dw = 2.0 * pi * (stopband - passband) / static_cast<double>(M);
-    const double A = 2.285 * dw * static_cast<double>(L - 1) + 7.95;
-    const double beta = A > 50.0 ? 0.1102 * (A - 8.7)
-                                 : (A >= 21.0 ? 0.5842 * std::pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
-    const double fc = 0.5 * (passband + stopband) / static_cast<double>(M); // cycles per input sample
-    const double centre = 0.5 * static_cast<double>(L - 1);
-    const double i0b = std::cyl_bessel_i(0.0, beta);
-    h.assign(L, 0.0);
-    double sum = 0.0;
-    for (size_t t = 0; t < L; ++t) {
-        const double u = 2.0 * static_cast<double>(t) / static_cast<double>(L - 1) - 1.0;
-        const double w = std::cyl_bessel_i(0.0, beta * std::sqrt(std::fmax(0.0, 1.0 - u * u))) / i0b;
-        const double x = 2.0 * fc * (static_cast<double>(t) - centre);
-        const double sinc = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
-        h[t] = 2.0 * fc * sinc * w;
-        sum += h[t];
-    }
-    for (double& v : h) v /= sum;
+    gr4pm::kaiser_lowpass(P * M, M, passband, stopband, h);
     return GR4PM_OK;
 }
 

@@ -1,0 +1,478 @@
+// ddc.hip -- tunable down-converter: K frequency-translating decimating FIRs over one wideband c64 stream, any integer
+// decimation D, channel-major output (out[k][n], the layout gr4pm_multichannel_receiver_submit takes).  The project's
+// own block (the reference is a one-channel modem).  Definition (include/gr4pm_hip.h):
+//     w_k = llrint(f_k 2^32) mod 2^32,   phi_k(i) = (w_k i) mod 2^32  (wrapping unsigned arithmetic, exact anywhere)
+//     y_k[n] = sum_t h[t] x[i - t] exp(-2 pi j phi_k(i - t) / 2^32),   i = start_index + n D + D - 1,   x = 0 before the start
+// evaluated in the rotated-taps form
+//     g_k[t] = h[t] exp(+2 pi j phi_k(t) / 2^32)     (host, double, rounded to float once, a K x L table on the device)
+//     r_k[n] = exp(-2 pi j phi_k(i) / 2^32)          (device, double sincospi of -phi / 2^31, rounded to float)
+//     y_k[n] = r_k[n] sum_t g_k[t] x[i - t]          (one accumulator per channel, t ascending, four fmaf per product)
+//
+// k_ddc: a workgroup owns T consecutive frames (T <= 256: a lane owns one frame) and up to 8 channels (blockIdx.y).
+//   The (T - 1) D + Lc samples the tile needs for Lc taps go to LDS once, converted on the way in and laid out by
+//   phase: sample j of the stage at row j mod D, column j div D, rows of an odd number of items.  Lanes on consecutive
+//   frames then read consecutive items of one row for every tap (no stride-D bank conflicts), and the 16 consecutive
+//   samples of a staging store fall on 16 different rows, so on different banks.  One LDS read of a sample feeds the
+//   group's complex MACs in registers; g_k[t] is the same address in every lane, and the table holds a group's taps
+//   interleaved by channel, so the taps of one t sit side by side.  The host picks T and Lc so that the stage stays
+//   within 64 KiB: L > Lc runs the t loop over re-staged chunks, still ascending in t, so chunking changes no bit.  Each channel's T items leave as one contiguous run, lanes on consecutive items.
+//   One form serves every size: a tile shrinks to T >= 3 frames at D = 1024, which wastes lanes but not correctness.
+// Every result is a function of (channel, frame, stream) only: it does not depend on how the stream is cut into calls.
+// k_ddc_history: the last L - 1 samples plus the incomplete frame move to the handle's other history buffer.
+// Integer input (gr4pm_ddc_process_iq): both kernels are templated on the input format and convert where a sample
+// enters them with iq_format.hpp's unpack_item(), the very expression gr4pm_iq_unpack evaluates; the stage and the
+// history stay complex64, so the result is that of process() on the unpacked samples bit for bit.
+#include "iq_format.hpp"
+#include "kaiser_design.hpp"
+
+#include <cmath>
+
+namespace {
+
+namespace iq = gr4pm::iq;
+
+constexpr int kNt = 256;             // threads of a workgroup, and the most frames of a tile
+constexpr int kGroup = 8;            // channels of a workgroup
+constexpr size_t kStageItems = 8192; // complex64 items of the stage: 64 KiB
+constexpr size_t kMaxK = 64, kMaxD = 1024, kMaxL = 8192;
+
+struct DdcArgs {
+    const float2* hist;   // the H samples in front of in[0]: L - 1 of history, then the carried partial frame
+    const void* in;       // complex64, or items of the kernel's integer format
+    float2* out;
+    const float2* g;      // rotated taps, K L items: group by group, a group's as [L][its channels]
+    const uint32_t* w;    // [K] frequency words
+    size_t H;
+    size_t total;         // H + n_in: samples of the virtual stream hist ++ in
+    size_t out_stride;
+    size_t n_frames;
+    uint64_t pos;         // absolute index of the virtual stream's sample L - 1 (the first one not yet in a frame)
+    unsigned K, D, L;
+    unsigned T;           // frames of a tile
+    unsigned Lc;          // taps of a chunk
+    unsigned RS;          // items of a stage row (odd)
+    unsigned rcpD;        // ceil(2^32 / D) for D >= 2: j div D = umulhi(j, rcpD) for j < 2^13
+    float scale;          // of an integer format's unpack
+};
+
+template <int F>
+__device__ __forceinline__ float2 vsample(const DdcArgs& a, size_t v)
+{
+    if constexpr (F == iq::kC64)
+        return v < a.H ? a.hist[v] : static_cast<const float2*>(a.in)[v - a.H];
+    else
+        return v < a.H ? a.hist[v] : iq::unpack_item<F>(iq::load_item<F>(a.in, v - a.H), a.scale);
+}
+
+// acc += g x, each product and sum one fmaf, in this order
+__device__ __forceinline__ void cmac(float2& acc, float2 g, float2 x)
+{
+    acc.x = fmaf(g.x, x.x, acc.x);
+    acc.x = fmaf(-g.y, x.y, acc.x);
+    acc.y = fmaf(g.x, x.y, acc.y);
+    acc.y = fmaf(g.y, x.x, acc.y);
+}
+
+// NC: channels of this workgroup's group; F: the input's format (iq::kC64: complex64)
+template <int NC, int F>
+__device__ __forceinline__ void ddc_tile(const DdcArgs& a, float2* s)
+{
+    const unsigned tid = threadIdx.x;
+    const unsigned D = a.D, L = a.L, T = a.T, RS = a.RS;
+    const size_t f0 = static_cast<size_t>(blockIdx.x) * T;
+    const unsigned k0 = blockIdx.y * kGroup;
+    const float2* __restrict__ g = a.g + static_cast<size_t>(k0) * L;
+
+    float2 acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = float2{0.0f, 0.0f};
+
+    for (unsigned t0 = 0; t0 < L; t0 += a.Lc) {
+        const unsigned lc = L - t0 < a.Lc ? L - t0 : a.Lc;
+        // stage item j: virtual sample vb + j; frame f0 + n takes tap t from item n D + (t0 + lc - 1 - t)
+        const size_t vb = static_cast<size_t>(L - 1) + f0 * D + (D - 1) - (t0 + lc - 1);
+        const unsigned S = (T - 1) * D + lc;
+        if (t0) __syncthreads(); // the previous chunk has been read
+        for (unsigned j = tid; j < S; j += kNt) {
+            const unsigned col = D == 1 ? j : __umulhi(j, a.rcpD);
+            const unsigned row = j - col * D;
+            const size_t v = vb + j;
+            s[row * RS + col] = v < a.total ? vsample<F>(a, v) : float2{0.0f, 0.0f};
+        }
+        __syncthreads();
+        if (tid < T) {
+            unsigned t = t0;
+            unsigned col = (lc - 1) / D, row = (lc - 1) - col * D;
+            for (;;) {
+                const float2* sp = s + row * RS + col + tid;
+#pragma unroll 4
+                for (unsigned r = 0; r <= row; ++r, sp -= RS, ++t) {
+                    const float2 x = *sp;
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) cmac(acc[c], g[t * NC + c], x);
+                }
+                if (col == 0) break;
+                --col;
+                row = D - 1;
+            }
+        }
+    }
+
+    const size_t f = f0 + tid;
+    if (tid < T && f < a.n_frames) {
+        const uint32_t i = static_cast<uint32_t>(a.pos + f * D + (D - 1)); // the low 32 bits are all the phase needs
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const uint32_t phi = a.w[k0 + c] * i;
+            double sn, cs;
+            sincospi(-static_cast<double>(phi) * (1.0 / 2147483648.0), &sn, &cs); // the argument is exact
+            const float2 r = {static_cast<float>(cs), static_cast<float>(sn)};
+            float2 y = {0.0f, 0.0f};
+            cmac(y, r, acc[c]);
+            a.out[static_cast<size_t>(k0 + c) * a.out_stride + f] = y;
+        }
+    }
+}
+
+template <int F>
+__global__ __launch_bounds__(kNt) void k_ddc(DdcArgs a)
+{
+    extern __shared__ float2 s_ddc[];
+    const unsigned left = a.K - blockIdx.y * kGroup;
+    switch (left < kGroup ? left : kGroup) {
+    case 1: ddc_tile<1, F>(a, s_ddc); break;
+    case 2: ddc_tile<2, F>(a, s_ddc); break;
+    case 3: ddc_tile<3, F>(a, s_ddc); break;
+    case 4: ddc_tile<4, F>(a, s_ddc); break;
+    case 5: ddc_tile<5, F>(a, s_ddc); break;
+    case 6: ddc_tile<6, F>(a, s_ddc); break;
+    case 7: ddc_tile<7, F>(a, s_ddc); break;
+    default: ddc_tile<8, F>(a, s_ddc); break;
+    }
+}
+
+// the stream's last H_new samples (of hist[0 .. H) followed by in[0 .. n_in)) into the other history buffer
+template <int F>
+__global__ __launch_bounds__(256) void k_ddc_history(const float2* hist, size_t H, const void* in, size_t n_in, float scale,
+                                                     float2* hist_new, size_t H_new)
+{
+    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= H_new) return;
+    const size_t v = H + n_in - H_new + i;
+    if constexpr (F == iq::kC64)
+        hist_new[i] = v < H ? hist[v] : static_cast<const float2*>(in)[v - H];
+    else
+        hist_new[i] = v < H ? hist[v] : iq::unpack_item<F>(iq::load_item<F>(in, v - H), scale);
+}
+
+template <int F>
+void launch(dim3 grid, size_t smem, hipStream_t s, const DdcArgs& a, size_t n_in, float2* hist_new, size_t H_new)
+{
+    if (a.n_frames) hipLaunchKernelGGL(k_ddc<F>, grid, dim3(kNt), smem, s, a);
+    if (H_new)
+        hipLaunchKernelGGL(k_ddc_history<F>, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, s, a.hist, a.H, a.in,
+                           n_in, a.scale, hist_new, H_new);
+}
+
+gr4pm_status design_taps(size_t D, size_t P, double passband, double stopband, std::vector<double>& h)
+{
+    using gr4pm::set_error;
+    if (D < 1 || D > kMaxD) {
+        set_error("ddc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
+        return GR4PM_ERR_INVALID;
+    }
+    if (P < 1 || P * D > kMaxL) {
+        set_error("ddc: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", P, D, kMaxL);
+        return GR4PM_ERR_INVALID;
+    }
+    if (!(passband >= 0.0) || !(passband < stopband) || !(passband + stopband <= static_cast<double>(D))) {
+        set_error("ddc: need 0 <= passband < stopband (units of the output rate) and a cutoff of at most fs / 2");
+        return GR4PM_ERR_INVALID;
+    }
+    gr4pm::kaiser_lowpass(P * D, D, passband, stopband, h);
+    return GR4PM_OK;
+}
+
+// llrint(f 2^32) mod 2^32: f = trunc(f) + m exactly, and trunc(f) 2^32 is a multiple of 2^32 that moves no tie
+uint32_t frequency_word(double f)
+{
+    const double m = std::fmod(f, 1.0);
+    return static_cast<uint32_t>(static_cast<uint64_t>(std::llrint(m * 4294967296.0)));
+}
+
+// exp(2 pi j phi / 2^32) in double, exact at the multiples of pi / 2 (cos(pi / 2) in double is 6e-17, not 0)
+void unit_phasor(uint32_t phi, double& c, double& s)
+{
+    const double ang = 0.5 * 3.14159265358979323846 * static_cast<double>(phi & 0x3FFFFFFFu) / 1073741824.0;
+    const double c0 = std::cos(ang), s0 = std::sin(ang);
+    switch (phi >> 30) {
+    case 0: c = c0, s = s0; break;
+    case 1: c = -s0, s = c0; break;
+    case 2: c = -c0, s = -s0; break;
+    default: c = s0, s = -c0; break;
+    }
+}
+
+} // namespace
+
+struct gr4pm_ddc {
+    size_t K = 0, D = 0, L = 0, max_frames = 0;
+    unsigned T = 0, Lc = 0, RS = 0, rcpD = 0;
+    size_t smem = 0;
+    uint64_t start_index = 0;
+    uint64_t pos = 0;   // absolute index of the first sample that is not yet part of a produced frame
+    size_t carried = 0; // samples of the incomplete frame, < D
+    int cur = 0;        // which history buffer holds the stream's tail
+    hipStream_t stream = nullptr;
+    std::vector<uint32_t> words;
+    gr4pm::DevBuf<float2> d_g, d_hist[2];
+    gr4pm::DevBuf<uint32_t> d_w;
+};
+
+using namespace gr4pm;
+
+// process() and process_iq(): format iq::kC64 for complex64 samples
+static gr4pm_status process_any(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+{
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    *n_frames = 0;
+    if (n_in > h->max_frames * h->D) {
+        set_error("ddc: %zu items, the handle was made for %zu frames of %zu", n_in, h->max_frames, h->D);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (n_in == 0) return GR4PM_OK;
+    if (!in) {
+        set_error("ddc: no input array");
+        return GR4PM_ERR_INVALID;
+    }
+    const size_t D = h->D, L = h->L;
+    const size_t F = (h->carried + n_in) / D;
+    if (F > out_cap_frames) {
+        set_error("ddc: %zu frames, room for %zu", F, out_cap_frames);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (F && (!out || (h->K > 1 && out_stride < F))) {
+        set_error("ddc: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
+        return GR4PM_ERR_INVALID;
+    }
+    const size_t H = (L - 1) + h->carried;
+    const size_t carried_new = (h->carried + n_in) % D;
+    const size_t H_new = (L - 1) + carried_new;
+    DdcArgs a;
+    a.hist = h->d_hist[h->cur].p;
+    a.in = in;
+    a.out = reinterpret_cast<float2*>(out);
+    a.g = h->d_g.p;
+    a.w = h->d_w.p;
+    a.H = H;
+    a.total = H + n_in;
+    a.out_stride = out_stride;
+    a.n_frames = F;
+    a.pos = h->pos;
+    a.K = static_cast<unsigned>(h->K);
+    a.D = static_cast<unsigned>(D);
+    a.L = static_cast<unsigned>(L);
+    a.T = h->T;
+    a.Lc = h->Lc;
+    a.RS = h->RS;
+    a.rcpD = h->rcpD;
+    a.scale = scale;
+    const dim3 grid(static_cast<unsigned>((F + h->T - 1) / h->T), static_cast<unsigned>((h->K + kGroup - 1) / kGroup));
+    float2* hist_new = h->d_hist[1 - h->cur].p;
+    if (format == GR4PM_IQ_SC16)
+        launch<GR4PM_IQ_SC16>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
+    else if (format == GR4PM_IQ_SC8)
+        launch<GR4PM_IQ_SC8>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
+    else if (format == GR4PM_IQ_CU8)
+        launch<GR4PM_IQ_CU8>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
+    else
+        launch<iq::kC64>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
+    GR4PM_HIP_TRY(hipGetLastError());
+    if (H_new) h->cur = 1 - h->cur;
+    h->carried = carried_new;
+    h->pos += static_cast<uint64_t>(F) * D;
+    *n_frames = F;
+    return GR4PM_OK;
+}
+
+extern "C" {
+
+gr4pm_status gr4pm_ddc_taps(size_t decimation, size_t taps_per_phase, double passband, double stopband, float* out)
+try {
+    if (!out) return GR4PM_ERR_INVALID;
+    std::vector<double> h;
+    GR4PM_TRY(design_taps(decimation, taps_per_phase, passband, stopband, h));
+    for (size_t t = 0; t < h.size(); ++t) out[t] = static_cast<float>(h[t]);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_create(const gr4pm_ddc_params* p, gr4pm_ddc** out)
+try {
+    if (!p || !out) return GR4PM_ERR_INVALID;
+    *out = nullptr;
+    const size_t K = p->n_channels, D = p->decimation;
+    if (K < 1 || K > kMaxK) {
+        set_error("ddc: the number of channels must be in [1, %zu], not %zu", kMaxK, K);
+        return GR4PM_ERR_INVALID;
+    }
+    if (D < 1 || D > kMaxD) {
+        set_error("ddc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
+        return GR4PM_ERR_INVALID;
+    }
+    if (!p->frequencies) {
+        set_error("ddc: no frequencies");
+        return GR4PM_ERR_INVALID;
+    }
+    for (size_t k = 0; k < K; ++k)
+        if (!std::isfinite(p->frequencies[k])) {
+            set_error("ddc: frequencies[%zu] is not finite", k);
+            return GR4PM_ERR_INVALID;
+        }
+    if (p->max_frames == 0 || p->max_frames > (size_t(1) << 31)) {
+        set_error("ddc: max_frames must be in [1, 2^31]");
+        return GR4PM_ERR_INVALID;
+    }
+    std::vector<float> taps;
+    if (p->taps) {
+        if (p->n_taps < 1 || p->n_taps > kMaxL) {
+            set_error("ddc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
+            return GR4PM_ERR_INVALID;
+        }
+        taps.assign(p->taps, p->taps + p->n_taps);
+    } else {
+        std::vector<double> hd;
+        GR4PM_TRY(design_taps(D, 12, 0.25, 0.75, hd));
+        taps.resize(hd.size());
+        for (size_t t = 0; t < hd.size(); ++t) taps[t] = static_cast<float>(hd[t]);
+    }
+    const size_t L = taps.size();
+    GR4PM_TRY(require_device());
+    auto* h = new (std::nothrow) gr4pm_ddc;
+    if (!h) return GR4PM_ERR_NOMEM;
+    auto bail = [&](gr4pm_status st) {
+        delete h;
+        return st;
+    };
+    h->K = K;
+    h->D = D;
+    h->L = L;
+    h->max_frames = p->max_frames;
+    h->start_index = h->pos = p->start_index;
+    h->stream = static_cast<hipStream_t>(p->stream);
+    // the tile: rows of `cols` items (made odd), D rows within the stage; a tile of T frames and a chunk of Lc taps
+    // use T + (Lc - 1) div D columns.  All of L in one chunk where 256 frames leave room for it, else half the columns
+    // go to frames and the rest to taps.
+    size_t cols = kStageItems / D;
+    if (cols % 2 == 0) --cols; // >= 7
+    const size_t extra_all = (L - 1) / D;
+    size_t T = kNt, extra = extra_all;
+    if (T + extra_all > cols) {
+        T = cols / 2 < static_cast<size_t>(kNt) ? cols / 2 : static_cast<size_t>(kNt);
+        extra = cols - T < extra_all ? cols - T : extra_all;
+    }
+    h->T = static_cast<unsigned>(T);
+    h->Lc = static_cast<unsigned>((extra + 1) * D < L ? (extra + 1) * D : L);
+    h->RS = static_cast<unsigned>((T + extra) | 1);
+    h->rcpD = D >= 2 ? static_cast<unsigned>(((uint64_t(1) << 32) + D - 1) / D) : 0u;
+    h->smem = static_cast<size_t>(h->RS) * D * sizeof(float2);
+
+    h->words.resize(K);
+    std::vector<float2> g(K * L);
+    for (size_t k = 0; k < K; ++k) {
+        const uint32_t w = h->words[k] = frequency_word(p->frequencies[k]);
+        // a group's taps interleaved by channel: tap t of all its channels side by side
+        const size_t k0 = k / kGroup * kGroup, nc = K - k0 < static_cast<size_t>(kGroup) ? K - k0 : static_cast<size_t>(kGroup);
+        for (size_t t = 0; t < L; ++t) {
+            double c, s;
+            unit_phasor(w * static_cast<uint32_t>(t), c, s);
+            g[k0 * L + t * nc + (k - k0)] = float2{static_cast<float>(static_cast<double>(taps[t]) * c),
+                                  static_cast<float>(static_cast<double>(taps[t]) * s)};
+        }
+    }
+    gr4pm_status st;
+    if ((st = h->d_g.alloc(K * L)) != GR4PM_OK || (st = h->d_w.alloc(K)) != GR4PM_OK ||
+        (st = h->d_hist[0].alloc(L - 1 + D)) != GR4PM_OK || (st = h->d_hist[1].alloc(L - 1 + D)) != GR4PM_OK)
+        return bail(st);
+    if ((st = h->d_g.upload(g.data(), g.size(), h->stream)) != GR4PM_OK ||
+        (st = h->d_w.upload(h->words.data(), K, h->stream)) != GR4PM_OK ||
+        (st = h->d_hist[0].zero(h->stream)) != GR4PM_OK || (st = h->d_hist[1].zero(h->stream)) != GR4PM_OK)
+        return bail(st);
+    if (h->smem > 48 * 1024) { // beyond the default dynamic-LDS window
+        const void* fns[] = {reinterpret_cast<const void*>(&k_ddc<iq::kC64>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC16>),
+                             reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC8>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_CU8>)};
+        for (const void* fn : fns)
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(kStageItems * sizeof(float2))) != hipSuccess) {
+                set_error("ddc: hipFuncSetAttribute(%zu bytes of LDS) failed", kStageItems * sizeof(float2));
+                return bail(GR4PM_ERR_HIP);
+            }
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
+        set_error("ddc: hipStreamSynchronize failed at create");
+        return bail(GR4PM_ERR_HIP);
+    }
+    *out = h;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+void gr4pm_ddc_destroy(gr4pm_ddc* h)
+try {
+    if (!h) return;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+GR4PM_ABI_CATCH_VOID
+
+gr4pm_status gr4pm_ddc_reset(gr4pm_ddc* h)
+try {
+    if (!h) return GR4PM_ERR_INVALID;
+    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
+    h->carried = 0;
+    h->pos = h->start_index;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_output_items(const gr4pm_ddc* h, size_t n_in, size_t* n_frames)
+try {
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    *n_frames = (h->carried + n_in) / h->D;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_frequencies(const gr4pm_ddc* h, double* out)
+try {
+    if (!h || !out) return GR4PM_ERR_INVALID;
+    for (size_t k = 0; k < h->K; ++k) {
+        const uint32_t w = h->words[k];
+        out[k] = (static_cast<double>(w) - (w >= 0x80000000u ? 4294967296.0 : 0.0)) / 4294967296.0;
+    }
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_process(gr4pm_ddc* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                               size_t out_cap_frames, size_t* n_frames)
+try {
+    return process_any(h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_process_iq(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                  size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+try {
+    if (n_frames) *n_frames = 0;
+    if (!iq::valid(format)) {
+        set_error("ddc: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
+        return GR4PM_ERR_INVALID;
+    }
+    return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
+                       n_frames);
+}
+GR4PM_ABI_CATCH
+
+} // extern "C"

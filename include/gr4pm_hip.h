@@ -1010,6 +1010,71 @@ gr4pm_status gr4pm_channelizer_process_iq(gr4pm_channelizer* h, const void* in, 
                                           gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames);
 
 /* ====================================================================================
+ * Ddc -- tunable down-converter: K frequency-translating decimating FIRs over one wideband c64 stream
+ * (the project's own block: the reference is a one-channel modem).  Any integer decimation D in
+ * [1, 1024], K in [1, 64] channels at arbitrary frequencies, a real prototype h[0 .. L - 1] with
+ * 1 <= L <= 8192 (L need not be a multiple of D).  Output: channel-major at fs / D, in the layout
+ * gr4pm_multichannel_receiver_submit takes.  With x[i] = 0 before the handle's first sample, whose
+ * absolute index is start_index:
+ *     w_k = llrint(f_k 2^32) mod 2^32 (uint32: the resolution is fs / 2^32)
+ *     phi_k(i) = (w_k i) mod 2^32, in wrapping unsigned arithmetic: exact at any stream position,
+ *                never accumulated in floating point
+ *     y_k[n] = sum_{t = 0}^{L - 1} h[t] x[i - t] exp(-2 pi j phi_k(i - t) / 2^32),  i = start_index + n D + D - 1
+ * (the D - 1 is the channelizer's w_k[n M + M - 1]: with D = M, f_k = k / M and the same taps this is the
+ * channelizer's row k).  Evaluated as
+ *     g_k[t] = h[t] exp(+2 pi j phi_k(t) / 2^32)   made at create on the host in double, each component
+ *                                                  rounded to float once
+ *     r_k[n] = exp(-2 pi j phi_k(i) / 2^32)        on the device: double sincospi of -phi / 2^31 (exact
+ *                                                  argument), each component rounded to float
+ *     y_k[n] = r_k[n] sum_t g_k[t] x[i - t]
+ * with one complex accumulator per channel, t ascending, every complex multiply-accumulate four fmaf:
+ *     re = fmaf(gr, xr, re); re = fmaf(-gi, xi, re); im = fmaf(gr, xi, im); im = fmaf(gi, xr, im)
+ * and the product with r_k[n] the same four fmaf from zero.  A result is a function of (k, n, stream)
+ * only: it does not depend on how the stream is cut into calls.  The last L - 1 samples and the
+ * samples of an incomplete frame stay in the handle on the device as complex64; the absolute index
+ * lives on the host.  process() takes any n_in, enqueues on the handle's stream and does not wait.
+ * Frequencies are fixed at create.
+ * ================================================================================== */
+typedef struct gr4pm_ddc gr4pm_ddc;
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t decimation;          /* D: 1 .. 1024 */
+    const double* frequencies;  /* host: K frequencies in cycles per input sample, any finite value */
+    const float* taps;          /* host: n_taps prototype taps, copied at create (NULL: the default design,
+                                   gr4pm_ddc_taps(D, 12, 0.25, 0.75)) */
+    size_t n_taps;              /* L: 1 .. 8192 (ignored when taps is NULL) */
+    size_t max_frames;          /* per process() call: n_in <= max_frames D; 1..2^31 */
+    uint64_t start_index;       /* absolute index of the first sample the handle sees */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_ddc_params;
+/* The Kaiser design of gr4pm_channelizer_taps with L = taps_per_phase * decimation taps, for any integer
+ * decimation (host only).  passband / stopband: the band edges in units of the output rate fs / D;
+ * DC gain 1.  For a power-of-two decimation the floats are those of gr4pm_channelizer_taps.
+ * out: taps_per_phase * decimation floats. */
+gr4pm_status gr4pm_ddc_taps(size_t decimation, size_t taps_per_phase, double passband, double stopband, float* out);
+gr4pm_status gr4pm_ddc_create(const gr4pm_ddc_params* params, gr4pm_ddc** out);
+void gr4pm_ddc_destroy(gr4pm_ddc* h);
+/* back to start_index with zero history and no carried samples */
+gr4pm_status gr4pm_ddc_reset(gr4pm_ddc* h);
+/* frames the next process() of n_in samples produces (from lengths, on the host); the state is unchanged */
+gr4pm_status gr4pm_ddc_output_items(const gr4pm_ddc* h, size_t n_in, size_t* n_frames);
+/* out: K doubles (host), the quantised frequencies w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_ddc_frequencies(const gr4pm_ddc* h, double* out);
+/* in: DEVICE, n_in samples (any number; all are consumed).  out: DEVICE, channel k at out + k out_stride,
+ * out_cap_frames items of room per row.  *n_frames = floor((carried + n_in) / D) items are written to
+ * every row.  A refused call -- a NULL pointer, out_stride < *n_frames with K > 1 (GR4PM_ERR_INVALID),
+ * more than max_frames D samples or fewer than *n_frames items of room (GR4PM_ERR_OVERFLOW) -- sets
+ * gr4pm_last_error and *n_frames = 0, writes nothing and does not move the stream. */
+gr4pm_status gr4pm_ddc_process(gr4pm_ddc* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                               size_t out_cap_frames, size_t* n_frames);
+/* in: DEVICE, n_in items of an integer IQ format (gr4pm_iq_format below; scale 0: the format's default).
+ * The same contract as gr4pm_ddc_process, and its result on gr4pm_iq_unpack(in) bit for bit: the samples
+ * are converted where they enter the kernel, the handle's history stays complex64, so calls of any format
+ * may be mixed on one handle. */
+gr4pm_status gr4pm_ddc_process_iq(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                  size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+
+/* ====================================================================================
  * Integer IQ formats (the project's own block: the reference moves complex64 only).  An item is one
  * complex sample, I then Q, little-endian integers.
  *     format          item         unpack, per component            default scale   default gain

@@ -111,6 +111,8 @@ BUDGETS = [
     (r"k_symbol_filter_fast", dict(vgpr=64)),
     (r"k_correlate_w64_oneILi0E", dict(vgpr=168, scratch=0)),  # three waves per SIMD
     (r"k_correlate_4096ILi1E", dict(vgpr=128, scratch=0)),     # four waves per SIMD
+    # the down-converter: eight channel accumulators and the double-precision rotator, six waves per SIMD
+    (r"k_ddcILi", dict(vgpr=80, scratch=0)),
 ]
 
 
