@@ -2,7 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_transmitter_pdu.cpp:
 
     packet_transmitter_file.py output_file (--in packets.bin | --random COUNT SIZE) [--stream-mode] [--gap N]
-                               [--format {cf32,sc16,sc8,cu8}] [--gain G]
+                               [--format {cf32,sc16,sc8,cu8}] [--gain G] [--tune CYCLES_PER_SAMPLE --interpolate I]
 
 makes the IQ of PacketTransmitterPdu (packet_transmitter_pdu.hpp:40-355) on the GPU (gr4pm_packet_transmitter) at
 4 samples/symbol and writes it to `output_file` as raw little-endian complex64 (what packet_receiver_file.py reads).
@@ -15,7 +15,12 @@ back to back through one continuous filter, without ramp-down, flush or burst sh
 
 `--format sc16 | sc8 | cu8` writes interleaved little-endian int16, int8 or uint8 (I, Q) instead, what a DAC or
 packet_receiver_file.py --format takes: packed on the device (gr4pm_iq_pack: rint(x * gain), cu8 around 127.5,
-clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is printed at the end."""
+clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is printed at the end.
+
+`--tune F --interpolate I`: the file is a wideband stream at I times the modem's rate with the carrier F cycles per file
+sample off centre: a one-channel `Duc` (gr4pm_duc: interpolate by I, mix by +F) sits behind the
+transmitter, and packet_receiver_file.py --tune F --decimate I receives the file.  Combines with `--format`; the
+prototype's P - 1 items of tail are flushed, so the last burst's ramp-down is whole."""
 import argparse
 import os
 import sys
@@ -40,9 +45,11 @@ def read_packets(path):
     return packets
 
 
-def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, fmt="cf32", gain=None, stats=None):
+def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, fmt="cf32", gain=None, stats=None,
+             tune=None, interpolate=None):
     """writes the IQ of `packets` to out_path; returns the number of samples written.  stats: an optional dict that
-    receives "clipped", the number of components an integer format clipped"""
+    receives "clipped", the number of components an integer format clipped.  tune / interpolate: a Duc behind the
+    transmitter"""
     pkg = pkg or ge.load_package()
     clipped = None if fmt == "cf32" else torch.zeros(1, dtype=torch.int64, device="cuda")
     empty = [k for k, p in enumerate(packets) if len(p) == 0]
@@ -51,16 +58,33 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
     batch_bytes = max([sum(len(p) for p in packets[i:i + batch]) for i in range(0, len(packets), batch)] + [1])
     tx = pkg.PacketTransmitter(stream_mode=stream_mode, samples_per_symbol=4, max_packets=batch,
                                max_payload_bytes=batch_bytes)
+    duc = None
+    if tune is not None or interpolate is not None:
+        duc = pkg.Duc([0.0 if tune is None else tune], 1 if interpolate is None else interpolate)
     written = 0
+
+    def emit(f, x):
+        if duc is not None:
+            for lo in range(0, x.numel(), duc.max_items):
+                emit_wide(f, duc.process_bulk(x[lo:lo + duc.max_items]))
+        else:
+            emit_wide(f, x)
+
+    def emit_wide(f, x):
+        nonlocal written
+        written += x.numel()
+        if fmt != "cf32":
+            x = pkg.iq_pack(x, fmt, gain, clipped=clipped)
+        f.write(x.cpu().numpy().tobytes())
+
     with open(out_path, "wb") as f:
         for i in range(0, len(packets), batch):
             chunk = packets[i:i + batch]
             gaps = None if stream_mode else [gap] * len(chunk)
             x, _, _ = tx.process_bulk(chunk, gaps=gaps)
-            written += x.numel()
-            if fmt != "cf32":
-                x = pkg.iq_pack(x, fmt, gain, clipped=clipped)
-            f.write(x.cpu().numpy().tobytes())
+            emit(f, x)
+        if duc is not None:  # the filter's tail
+            emit(f, torch.zeros(len(duc.taps) // duc.interpolation + 1, dtype=torch.complex64, device="cuda"))
     if stats is not None and clipped is not None:
         stats["clipped"] = int(clipped.item())
     return written
@@ -68,7 +92,7 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("output_file", help="raw complex64 IQ at 4 samples/symbol")
+    ap.add_argument("output_file", help="raw complex64 IQ at 4 samples/symbol (times --interpolate)")
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--in", dest="input_file", help="packets: uint16 big-endian length + bytes each")
     src.add_argument("--random", nargs=2, type=int, metavar=("COUNT", "SIZE"), help="COUNT random packets of SIZE bytes")
@@ -77,6 +101,8 @@ def main():
     ap.add_argument("--gap", type=int, default=0, help="samples of silence before each burst (burst mode)")
     ap.add_argument("--format", choices=["cf32", "sc16", "sc8", "cu8"], default="cf32", help="the file's items (default: complex64)")
     ap.add_argument("--gain", type=float, help="of an integer format's components (default: 2^15 for sc16, else 2^7)")
+    ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Duc behind)")
+    ap.add_argument("--interpolate", type=int, metavar="I", help="file samples per transmitter sample (a Duc behind)")
     a = ap.parse_args()
     if a.stream_mode and a.gap:
         ap.error("--gap is a burst mode option")
@@ -91,7 +117,8 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("packet_transmitter_file.py needs a GPU")
     stats = {}
-    n = transmit(packets, a.output_file, a.stream_mode, a.gap, fmt=a.format, gain=a.gain, stats=stats)
+    n = transmit(packets, a.output_file, a.stream_mode, a.gap, fmt=a.format, gain=a.gain, stats=stats,
+                 tune=a.tune, interpolate=a.interpolate)
     print(f"{len(packets)} packets, {n} samples -> {a.output_file}" +
           (f" ({a.format}, {stats['clipped']} clipped components)" if "clipped" in stats else ""))
 

@@ -1967,6 +1967,108 @@ class Ddc:
             pass
 
 
+def duc_taps(interpolation, taps_per_phase=12, passband=0.25, stopband=0.75):
+    """gr4pm_duc_taps: the Duc's prototype low-pass, the Kaiser design of ddc_taps with taps_per_phase * interpolation
+    float32 taps and DC gain `interpolation`, scaled in double before the one rounding to float32 (host only: works
+    without a GPU).  passband / stopband: the band edges in units of the input rate."""
+    n = int(interpolation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_duc_taps(int(interpolation), int(taps_per_phase), float(passband), float(stopband), _np_ptr(out)),
+          "duc_taps")
+    return out[:n]
+
+
+class Duc:
+    """gr4pm_duc: tunable up-converter, the mirror of Ddc.  len(frequencies) complex64 rows at fs / interpolation become
+    one wideband stream at fs: row k is interpolated by any integer 1 .. 1024 through the prototype, scaled by gains[k]
+    (None: 1) and mixed to frequencies[k] (cycles per output sample, any real value, quantised to fs / 2^32:
+    .frequencies holds the values in use, folded to [-0.5, 0.5)); the rows are summed.  taps: 1 .. 8192 float32
+    prototype taps of any length (None: duc_taps(interpolation, taps_per_phase)).  start_index: the absolute index of
+    the first output sample (a row's phase follows from the absolute index in integer arithmetic, exactly, at any
+    stream position), so Ddc(frequencies, interpolation, start_index=...) on the result returns the rows.
+    process_bulk() takes any number of items per row; the filter history stays on the device.  Frequencies and gains
+    are fixed: make another Duc to retune.  The handle works on the stream that is current when it is made."""
+
+    def __init__(self, frequencies, interpolation, gains=None, taps=None, taps_per_phase=12, start_index=0,
+                 max_items=1 << 22):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
+        if f.ndim != 1:
+            raise Gr4pmError("Duc: frequencies must be a list of numbers")
+        self.n_channels = int(f.size)
+        self.interpolation = int(interpolation)
+        a = None
+        if gains is not None:
+            a = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, dtype=np.float64)))
+            if a.shape != f.shape:
+                raise Gr4pmError("Duc: one gain per frequency")
+        self.gains = np.ones(f.size) if a is None else a
+        if taps is not None:
+            self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+            if not self.taps.size:
+                raise Gr4pmError("Duc: the prototype has 1 .. 8192 taps, not 0")
+        else:
+            self.taps = duc_taps(self.interpolation, taps_per_phase)
+        self.start_index = int(start_index)
+        if not 0 <= self.start_index < 1 << 64:
+            raise Gr4pmError("Duc: start_index must fit 64 unsigned bits")
+        self.max_items = int(max_items)
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.DucParams(self.n_channels, self.interpolation, _np_ptr(f) if f.size else None,
+                           _np_ptr(a) if a is not None and a.size else None, _np_ptr(self.taps), self.taps.size,
+                           self.max_items, self.start_index, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_duc_create(C.byref(p), C.byref(self._h)), "Duc")
+        q = np.zeros(self.n_channels, dtype=np.float64)
+        check(lib().gr4pm_duc_frequencies(self._h, _np_ptr(q)), "Duc.frequencies")
+        self.frequencies = q
+
+    def output_items(self, n_in):
+        """samples the next process_bulk() of n_in items per row produces: n_in * interpolation"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_duc_output_items(self._h, int(n_in), C.byref(n)), "Duc.output_items")
+        return n.value
+
+    def reset(self):
+        """back to start_index: zero history"""
+        check(lib().gr4pm_duc_reset(self._h), "Duc.reset")
+
+    def process_bulk(self, v, out=None):
+        """v: a CUDA complex64 tensor [n_channels, n] with contiguous rows and any row stride (a window of a wider
+        tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[n * interpolation]; out: an optional
+        contiguous CUDA complex64 tensor of at least that many samples to write into."""
+        torch = _torch()
+        if isinstance(v, torch.Tensor) and self.n_channels == 1 and (v.dim() == 1 or (v.dim() == 2 and v.shape[0] == 1)):
+            v = _dev_c64(v.reshape(-1) if v.dim() == 2 else v, "v")  # one row: its stride means nothing
+            n_in, stride = v.numel(), v.numel()
+        else:
+            v = _dev_c64_rows(v, "v")
+            if v.shape[0] != self.n_channels:
+                raise Gr4pmError(f"Duc: v is {tuple(v.shape)}, the handle has {self.n_channels} rows")
+            n_in, stride = v.shape[1], (v.stride(0) if self.n_channels > 1 else v.shape[1])
+        if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
+            _inputs_ready(v)  # made on another stream than the handle's
+        samples = self.output_items(n_in)
+        if out is None:
+            out = torch.empty(samples, dtype=torch.complex64, device=v.device)
+        else:
+            out = _dev_c64(out, "out")
+            if out.dim() != 1 or out.numel() < samples:
+                raise Gr4pmError(f"Duc: out is {tuple(out.shape)}, the call makes [{samples}]")
+        n = C.c_size_t(0)
+        check(lib().gr4pm_duc_process(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), out.numel(), C.byref(n)),
+              "Duc.process")
+        return out[: n.value]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _release("gr4pm_duc_destroy", self._h)
+                self._h = None
+        except Exception:  # interpreter shutdown
+            pass
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

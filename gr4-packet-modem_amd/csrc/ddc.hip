@@ -23,6 +23,7 @@
 // enters them with iq_format.hpp's unpack_item(), the very expression gr4pm_iq_unpack evaluates; the stage and the
 // history stay complex64, so the result is that of process() on the unpacked samples bit for bit.
 #include "iq_format.hpp"
+#include "freq_xlate.hpp"
 #include "kaiser_design.hpp"
 
 #include <cmath>
@@ -30,6 +31,7 @@
 namespace {
 
 namespace iq = gr4pm::iq;
+using gr4pm::cmac;
 
 constexpr int kNt = 256;             // threads of a workgroup, and the most frames of a tile
 constexpr int kGroup = 8;            // channels of a workgroup
@@ -62,15 +64,6 @@ __device__ __forceinline__ float2 vsample(const DdcArgs& a, size_t v)
         return v < a.H ? a.hist[v] : static_cast<const float2*>(a.in)[v - a.H];
     else
         return v < a.H ? a.hist[v] : iq::unpack_item<F>(iq::load_item<F>(a.in, v - a.H), a.scale);
-}
-
-// acc += g x, each product and sum one fmaf, in this order
-__device__ __forceinline__ void cmac(float2& acc, float2 g, float2 x)
-{
-    acc.x = fmaf(g.x, x.x, acc.x);
-    acc.x = fmaf(-g.y, x.y, acc.x);
-    acc.y = fmaf(g.x, x.y, acc.y);
-    acc.y = fmaf(g.y, x.x, acc.y);
 }
 
 // NC: channels of this workgroup's group; F: the input's format (iq::kC64: complex64)
@@ -191,26 +184,6 @@ gr4pm_status design_taps(size_t D, size_t P, double passband, double stopband, s
     }
     gr4pm::kaiser_lowpass(P * D, D, passband, stopband, h);
     return GR4PM_OK;
-}
-
-// llrint(f 2^32) mod 2^32: f = trunc(f) + m exactly, and trunc(f) 2^32 is a multiple of 2^32 that moves no tie
-uint32_t frequency_word(double f)
-{
-    const double m = std::fmod(f, 1.0);
-    return static_cast<uint32_t>(static_cast<uint64_t>(std::llrint(m * 4294967296.0)));
-}
-
-// exp(2 pi j phi / 2^32) in double, exact at the multiples of pi / 2 (cos(pi / 2) in double is 6e-17, not 0)
-void unit_phasor(uint32_t phi, double& c, double& s)
-{
-    const double ang = 0.5 * 3.14159265358979323846 * static_cast<double>(phi & 0x3FFFFFFFu) / 1073741824.0;
-    const double c0 = std::cos(ang), s0 = std::sin(ang);
-    switch (phi >> 30) {
-    case 0: c = c0, s = s0; break;
-    case 1: c = -s0, s = c0; break;
-    case 2: c = -c0, s = -s0; break;
-    default: c = s0, s = -c0; break;
-    }
 }
 
 } // namespace
@@ -385,10 +358,7 @@ try {
         // a group's taps interleaved by channel: tap t of all its channels side by side
         const size_t k0 = k / kGroup * kGroup, nc = K - k0 < static_cast<size_t>(kGroup) ? K - k0 : static_cast<size_t>(kGroup);
         for (size_t t = 0; t < L; ++t) {
-            double c, s;
-            unit_phasor(w * static_cast<uint32_t>(t), c, s);
-            g[k0 * L + t * nc + (k - k0)] = float2{static_cast<float>(static_cast<double>(taps[t]) * c),
-                                  static_cast<float>(static_cast<double>(taps[t]) * s)};
+            g[k0 * L + t * nc + (k - k0)] = rotated_tap(static_cast<double>(taps[t]), w * static_cast<uint32_t>(t));
         }
     }
     gr4pm_status st;
@@ -447,10 +417,7 @@ GR4PM_ABI_CATCH
 gr4pm_status gr4pm_ddc_frequencies(const gr4pm_ddc* h, double* out)
 try {
     if (!h || !out) return GR4PM_ERR_INVALID;
-    for (size_t k = 0; k < h->K; ++k) {
-        const uint32_t w = h->words[k];
-        out[k] = (static_cast<double>(w) - (w >= 0x80000000u ? 4294967296.0 : 0.0)) / 4294967296.0;
-    }
+    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH

@@ -1,4 +1,5 @@
-// kaiser_design.hpp -- the prototype low-pass of the Channelizer (channelizer.hip) and of the Ddc (ddc.hip): host only.
+// kaiser_design.hpp -- the prototype low-pass of the Channelizer (channelizer.hip), the Ddc (ddc.hip) and the Duc
+// (duc.hip): host only.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -8,8 +9,9 @@ namespace gr4pm {
 
 // Kaiser-windowed sinc of L taps in double for a decimation by D: band edges in units of the output rate fs / D, the
 // cutoff midway between them, the window's beta from the attenuation that Kaiser's length rule gives for L taps over
-// the transition width; DC gain 1.  The caller has checked L >= 1, D >= 1 and 0 <= passband < stopband.
-inline void kaiser_lowpass(size_t L, size_t D, double passband, double stopband, std::vector<double>& h)
+// the transition width; DC gain 1, or `gain` (an interpolator's D), applied in double to the unit-gain taps.  The caller
+// has checked L >= 1, D >= 1 and 0 <= passband < stopband.
+inline void kaiser_lowpass(size_t L, size_t D, double passband, double stopband, std::vector<double>& h, double gain = 1.0)
 {
     const double pi = 3.14159265358979323846;
     const double dw = 2.0 * pi * (stopband - passband) / static_cast<double>(D);
@@ -31,6 +33,8 @@ inline void kaiser_lowpass(size_t L, size_t D, double passband, double stopband,
         sum += h[t];
     }
     for (double& v : h) v /= sum;
+    if (gain != 1.0)
+        for (double& v : h) v *= gain;
 }
 
 } // namespace gr4pm

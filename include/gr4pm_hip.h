@@ -1075,6 +1075,65 @@ gr4pm_status gr4pm_ddc_process_iq(gr4pm_ddc* h, const void* in, int format, floa
                                   size_t out_stride, size_t out_cap_frames, size_t* n_frames);
 
 /* ====================================================================================
+ * Duc -- tunable up-converter, the mirror of the Ddc: K complex64 rows at fs / I become ONE wideband
+ * stream at fs (the project's own block).  Any integer interpolation I in [1, 1024], K in [1, 64] rows
+ * at arbitrary frequencies, a real prototype h[0 .. L - 1] with 1 <= L <= 8192 (L need not be a multiple
+ * of I; P = ceil(L / I)), real gains a_k.  With v_k[m] = 0 before the handle's first item, output sample
+ * j = m I + r (0 <= r < I) at the absolute index i = start_index + j:
+ *     w_k = llrint(f_k 2^32) mod 2^32,  phi_k(i) = (w_k i) mod 2^32   (as in the Ddc: wrapping unsigned
+ *                                                                       arithmetic, exact anywhere)
+ *     x[i] = sum_k a_k exp(+2 pi j phi_k(i) / 2^32) sum_{p : p I + r < L} h[p I + r] v_k[m - p]
+ * (zero-stuff every row by I, filter with h, mix to f_k, sum).  Evaluated as
+ *     g_k[t] = a_k h[t] exp(+2 pi j phi_k(t) / 2^32)   made at create on the host in double (the Ddc's table
+ *                                                      times a_k), each component rounded to float once
+ *     q_k[m'] = exp(+2 pi j phi_k(start_index + m' I) / 2^32)   one per INPUT item, on the device: double
+ *                                                      sincospi of phi / 2^31 (exact argument), each
+ *                                                      component rounded to float
+ *     z_k[m'] = q_k[m'] v_k[m']                        four fmaf from zero
+ *     x[i] = sum_k sum_{p : p I + r < L} g_k[p I + r] z_k[m - p]
+ * with ONE complex accumulator per output sample that starts at zero, k ascending in the outer loop,
+ * p ascending in the inner one, every complex multiply-accumulate the Ddc's four fmaf:
+ *     re = fmaf(gr, zr, re); re = fmaf(-gi, zi, re); im = fmaf(gr, zi, im); im = fmaf(gi, zr, im)
+ * A result is a function of (absolute output index, the rows' streams) only: it does not depend on how
+ * the streams are cut into calls.  A call of n_in items per row writes exactly n_in I samples; the last
+ * P - 1 items of every row stay in the handle on the device, the absolute index lives on the host.
+ * process() enqueues on the handle's stream and does not wait.  Frequencies and gains are fixed at create.
+ * ================================================================================== */
+typedef struct gr4pm_duc gr4pm_duc;
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t interpolation;       /* I: 1 .. 1024 */
+    const double* frequencies;  /* host: K frequencies in cycles per output sample, any finite value */
+    const double* gains;        /* host: K finite real gains a_k (NULL: all 1) */
+    const float* taps;          /* host: n_taps prototype taps, copied at create (NULL: the default design,
+                                   gr4pm_duc_taps(I, 12, 0.25, 0.75)) */
+    size_t n_taps;              /* L: 1 .. 8192 (ignored when taps is NULL) */
+    size_t max_items;           /* per process() call: n_in <= max_items; 1..2^31 */
+    uint64_t start_index;       /* absolute index of the first output sample */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_duc_params;
+/* The Kaiser design of gr4pm_ddc_taps with L = taps_per_phase * interpolation taps and DC gain I (every
+ * polyphase branch has gain about 1), scaled in double before the one rounding to float (host only).
+ * passband / stopband: the band edges in units of the input rate fs / I.
+ * out: taps_per_phase * interpolation floats. */
+gr4pm_status gr4pm_duc_taps(size_t interpolation, size_t taps_per_phase, double passband, double stopband, float* out);
+gr4pm_status gr4pm_duc_create(const gr4pm_duc_params* params, gr4pm_duc** out);
+void gr4pm_duc_destroy(gr4pm_duc* h);
+/* back to start_index with zero history */
+gr4pm_status gr4pm_duc_reset(gr4pm_duc* h);
+/* samples the next process() of n_in items per row produces: n_in I; the state is unchanged */
+gr4pm_status gr4pm_duc_output_items(const gr4pm_duc* h, size_t n_in, size_t* n_out);
+/* out: K doubles (host), the quantised frequencies w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_duc_frequencies(const gr4pm_duc* h, double* out);
+/* in: DEVICE, row k at in + k in_stride, n_in items each (any number).  out: DEVICE, contiguous, out_cap
+ * samples of room; *n_out = n_in I samples are written.  A refused call -- a NULL pointer, in_stride < n_in
+ * with K > 1 (GR4PM_ERR_INVALID), more than max_items items or fewer than n_in I samples of room
+ * (GR4PM_ERR_OVERFLOW) -- sets gr4pm_last_error and *n_out = 0, writes nothing and does not move the
+ * stream. */
+gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
+                               size_t out_cap, size_t* n_out);
+
+/* ====================================================================================
  * Integer IQ formats (the project's own block: the reference moves complex64 only).  An item is one
  * complex sample, I then Q, little-endian integers.
  *     format          item         unpack, per component            default scale   default gain
