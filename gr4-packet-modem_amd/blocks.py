@@ -1759,16 +1759,79 @@ def iq_pack(x, fmt, gain=None, out=None, clipped=None):
     return out
 
 
+def _design_taps(entry, ratio, per, passband, stopband, what):
+    """a gr4pm_*_taps entry: the design of per * ratio float32 taps"""
+    n = int(ratio) * int(per)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(getattr(lib(), entry)(int(ratio), int(per), float(passband), float(stopband), _np_ptr(out)), what)
+    return out[:n]
+
+
+def _stream_input(x, scale, stream):
+    """What a front-end block's process_bulk() takes: a contiguous complex64 CUDA tensor [n], or integer IQ [n, 2] (see
+    _dev_iq) with an optional scale; handed over to the handle's stream.  Returns (x, n, the format or None for complex64,
+    the scale as the C entry takes it)."""
+    torch = _torch()
+    fmt = None
+    if isinstance(x, torch.Tensor) and x.dtype in _iq_dtypes():
+        fmt, _, n_in, _ = _dev_iq(x)
+        if x.dim() != 2:
+            raise TypeError("x must be [n, 2]")
+    else:
+        if scale is not None:
+            raise TypeError("scale applies to integer IQ only")
+        x = _dev_c64(x, "x")
+        if x.dim() != 1:
+            raise TypeError("x must be one-dimensional")
+        n_in = x.numel()
+    if torch.cuda.current_stream(x.device).cuda_stream != stream:
+        _inputs_ready(x)  # made on another stream than the handle's
+    return x, n_in, fmt, 0.0 if scale is None else float(scale)
+
+
+def _rows_output(out, rows, frames, device, what):
+    """the [rows, frames] complex64 result: a new tensor, or the caller's [rows, >= frames] with contiguous rows"""
+    if out is None:
+        return _torch().empty((rows, frames), dtype=_torch().complex64, device=device)
+    out = _dev_c64_rows(out, "out")
+    if out.shape[0] != rows or out.shape[1] < frames:
+        raise Gr4pmError(f"{what}: out is {tuple(out.shape)}, the call makes [{rows}, {frames}]")
+    return out
+
+
+def _xlate_settings(what, frequencies, ratio, taps, taps_per_phase, start_index, design):
+    """the settings Ddc and Duc share: (frequencies as float64, float32 taps, start_index)"""
+    f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
+    if f.ndim != 1:
+        raise Gr4pmError(f"{what}: frequencies must be a list of numbers")
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        if not taps.size:
+            raise Gr4pmError(f"{what}: the prototype has 1 .. 8192 taps, not 0")
+    else:
+        taps = design(ratio, taps_per_phase)
+    start_index = int(start_index)
+    if not 0 <= start_index < 1 << 64:
+        raise Gr4pmError(f"{what}: start_index must fit 64 unsigned bits")
+    return f, taps, start_index
+
+
+def _destroy(self, entry):
+    """a __del__: the handle goes once; silent at interpreter shutdown"""
+    try:
+        if getattr(self, "_h", None):
+            _release(entry, self._h)
+            self._h = None
+    except Exception:
+        pass
+
+
 def channelizer_taps(n_channels, taps_per_branch=12, passband=0.25, stopband=0.75):
     """gr4pm_channelizer_taps: the Channelizer's prototype low-pass, a Kaiser-windowed sinc of taps_per_branch *
     n_channels float32 taps with DC gain 1 (host only: works without a GPU).  passband / stopband: the band edges in
     units of the channel spacing.  The defaults suit the transmitter's RRC at 4 samples per symbol (occupied to 0.169
     of the spacing; the neighbour's band starts at 0.831)."""
-    n = int(n_channels) * int(taps_per_branch)
-    out = np.zeros(max(n, 1), dtype=np.float32)
-    check(lib().gr4pm_channelizer_taps(int(n_channels), int(taps_per_branch), float(passband), float(stopband),
-                                       _np_ptr(out)), "channelizer_taps")
-    return out[:n]
+    return _design_taps("gr4pm_channelizer_taps", n_channels, taps_per_branch, passband, stopband, "channelizer_taps")
 
 
 class Channelizer:
@@ -1820,45 +1883,19 @@ class Channelizer:
         (gr4pm_channelizer_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns
         y[n_rows, frames]; out: an optional CUDA complex64 [n_rows, >= frames] tensor with contiguous rows and any row
         stride (a window of a receiver's ring) to write into."""
-        torch = _torch()
-        fmt = None
-        if isinstance(x, torch.Tensor) and x.dtype in _iq_dtypes():
-            fmt, rows, n_in, _ = _dev_iq(x)
-            if x.dim() != 2:
-                raise TypeError("x must be [n, 2]")
-        else:
-            if scale is not None:
-                raise TypeError("scale applies to integer IQ only")
-            x = _dev_c64(x, "x")
-            if x.dim() != 1:
-                raise TypeError("x must be one-dimensional")
-            n_in = x.numel()
-        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
-            _inputs_ready(x)  # made on another stream than the handle's
-        frames = self.output_items(n_in)
-        if out is None:
-            out = torch.empty((self.n_rows, frames), dtype=torch.complex64, device=x.device)
-        else:
-            out = _dev_c64_rows(out, "out")
-            if out.shape[0] != self.n_rows or out.shape[1] < frames:
-                raise Gr4pmError(f"Channelizer: out is {tuple(out.shape)}, the call makes [{self.n_rows}, {frames}]")
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        out = _rows_output(out, self.n_rows, self.output_items(n_in), x.device, "Channelizer")
         n = C.c_size_t(0)
         if fmt is None:
             check(lib().gr4pm_channelizer_process(self._h, x.data_ptr(), n_in, out.data_ptr(), out.stride(0),
                                                   out.shape[1], C.byref(n)), "Channelizer.process")
         else:
-            check(lib().gr4pm_channelizer_process_iq(self._h, x.data_ptr(), fmt, 0.0 if scale is None else float(scale), n_in,
-                                                     out.data_ptr(), out.stride(0), out.shape[1], C.byref(n)),
-                  "Channelizer.process_iq")
+            check(lib().gr4pm_channelizer_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), out.stride(0),
+                                                     out.shape[1], C.byref(n)), "Channelizer.process_iq")
         return out[:, : n.value]
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _release("gr4pm_channelizer_destroy", self._h)
-                self._h = None
-        except Exception:  # interpreter shutdown
-            pass
+        _destroy(self, "gr4pm_channelizer_destroy")
 
 
 def ddc_taps(decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
@@ -1866,11 +1903,7 @@ def ddc_taps(decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
     decimation float32 taps for any integer decimation, DC gain 1 (host only: works without a GPU).  passband /
     stopband: the band edges in units of the output rate.  For a power-of-two decimation the floats are those of
     channelizer_taps."""
-    n = int(decimation) * int(taps_per_phase)
-    out = np.zeros(max(n, 1), dtype=np.float32)
-    check(lib().gr4pm_ddc_taps(int(decimation), int(taps_per_phase), float(passband), float(stopband), _np_ptr(out)),
-          "ddc_taps")
-    return out[:n]
+    return _design_taps("gr4pm_ddc_taps", decimation, taps_per_phase, passband, stopband, "ddc_taps")
 
 
 class Ddc:
@@ -1885,20 +1918,10 @@ class Ddc:
     another Ddc to retune.  The handle works on the stream that is current when it is made."""
 
     def __init__(self, frequencies, decimation, taps=None, taps_per_phase=12, start_index=0, max_frames=1 << 22):
-        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
-        if f.ndim != 1:
-            raise Gr4pmError("Ddc: frequencies must be a list of numbers")
-        self.n_channels = self.n_rows = int(f.size)
         self.decimation = int(decimation)
-        if taps is not None:
-            self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            if not self.taps.size:
-                raise Gr4pmError("Ddc: the prototype has 1 .. 8192 taps, not 0")
-        else:
-            self.taps = ddc_taps(self.decimation, taps_per_phase)
-        self.start_index = int(start_index)
-        if not 0 <= self.start_index < 1 << 64:
-            raise Gr4pmError("Ddc: start_index must fit 64 unsigned bits")
+        f, self.taps, self.start_index = _xlate_settings("Ddc", frequencies, self.decimation, taps, taps_per_phase,
+                                                         start_index, ddc_taps)
+        self.n_channels = self.n_rows = int(f.size)
         self.max_frames = int(max_frames)
         stream = _stream_handle()
         self._stream = stream.value
@@ -1926,56 +1949,27 @@ class Ddc:
         (gr4pm_ddc_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns
         y[n_channels, frames]; out: an optional CUDA complex64 [n_channels, >= frames] tensor with contiguous rows and
         any row stride (a window of a receiver's ring) to write into."""
-        torch = _torch()
-        fmt = None
-        if isinstance(x, torch.Tensor) and x.dtype in _iq_dtypes():
-            fmt, rows, n_in, _ = _dev_iq(x)
-            if x.dim() != 2:
-                raise TypeError("x must be [n, 2]")
-        else:
-            if scale is not None:
-                raise TypeError("scale applies to integer IQ only")
-            x = _dev_c64(x, "x")
-            if x.dim() != 1:
-                raise TypeError("x must be one-dimensional")
-            n_in = x.numel()
-        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
-            _inputs_ready(x)  # made on another stream than the handle's
-        frames = self.output_items(n_in)
-        if out is None:
-            out = torch.empty((self.n_channels, frames), dtype=torch.complex64, device=x.device)
-        else:
-            out = _dev_c64_rows(out, "out")
-            if out.shape[0] != self.n_channels or out.shape[1] < frames:
-                raise Gr4pmError(f"Ddc: out is {tuple(out.shape)}, the call makes [{self.n_channels}, {frames}]")
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        out = _rows_output(out, self.n_channels, self.output_items(n_in), x.device, "Ddc")
         n = C.c_size_t(0)
         stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
         if fmt is None:
             check(lib().gr4pm_ddc_process(self._h, x.data_ptr(), n_in, out.data_ptr(), stride, out.shape[1], C.byref(n)),
                   "Ddc.process")
         else:
-            check(lib().gr4pm_ddc_process_iq(self._h, x.data_ptr(), fmt, 0.0 if scale is None else float(scale), n_in,
-                                             out.data_ptr(), stride, out.shape[1], C.byref(n)), "Ddc.process_iq")
+            check(lib().gr4pm_ddc_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), stride, out.shape[1],
+                                             C.byref(n)), "Ddc.process_iq")
         return out[:, : n.value]
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _release("gr4pm_ddc_destroy", self._h)
-                self._h = None
-        except Exception:  # interpreter shutdown
-            pass
+        _destroy(self, "gr4pm_ddc_destroy")
 
 
 def duc_taps(interpolation, taps_per_phase=12, passband=0.25, stopband=0.75):
     """gr4pm_duc_taps: the Duc's prototype low-pass, the Kaiser design of ddc_taps with taps_per_phase * interpolation
     float32 taps and DC gain `interpolation`, scaled in double before the one rounding to float32 (host only: works
     without a GPU).  passband / stopband: the band edges in units of the input rate."""
-    n = int(interpolation) * int(taps_per_phase)
-    out = np.zeros(max(n, 1), dtype=np.float32)
-    check(lib().gr4pm_duc_taps(int(interpolation), int(taps_per_phase), float(passband), float(stopband), _np_ptr(out)),
-          "duc_taps")
-    return out[:n]
+    return _design_taps("gr4pm_duc_taps", interpolation, taps_per_phase, passband, stopband, "duc_taps")
 
 
 class Duc:
@@ -1991,26 +1985,16 @@ class Duc:
 
     def __init__(self, frequencies, interpolation, gains=None, taps=None, taps_per_phase=12, start_index=0,
                  max_items=1 << 22):
-        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
-        if f.ndim != 1:
-            raise Gr4pmError("Duc: frequencies must be a list of numbers")
-        self.n_channels = int(f.size)
         self.interpolation = int(interpolation)
+        f, self.taps, self.start_index = _xlate_settings("Duc", frequencies, self.interpolation, taps, taps_per_phase,
+                                                         start_index, duc_taps)
+        self.n_channels = int(f.size)
         a = None
         if gains is not None:
             a = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, dtype=np.float64)))
             if a.shape != f.shape:
                 raise Gr4pmError("Duc: one gain per frequency")
         self.gains = np.ones(f.size) if a is None else a
-        if taps is not None:
-            self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
-            if not self.taps.size:
-                raise Gr4pmError("Duc: the prototype has 1 .. 8192 taps, not 0")
-        else:
-            self.taps = duc_taps(self.interpolation, taps_per_phase)
-        self.start_index = int(start_index)
-        if not 0 <= self.start_index < 1 << 64:
-            raise Gr4pmError("Duc: start_index must fit 64 unsigned bits")
         self.max_items = int(max_items)
         stream = _stream_handle()
         self._stream = stream.value
@@ -2061,12 +2045,7 @@ class Duc:
         return out[: n.value]
 
     def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _release("gr4pm_duc_destroy", self._h)
-                self._h = None
-        except Exception:  # interpreter shutdown
-            pass
+        _destroy(self, "gr4pm_duc_destroy")
 
 
 class MultiChannelPacketReceiver:

@@ -18,13 +18,14 @@
 //   items of the row, read from LDS at the bit-reversed column.
 // Every product and sum rounds on its own (EXACT_FLAGS) in an order that depends on (frame, branch) only: a result
 // does not depend on how the stream is cut into calls.
-// k_chan_history: the last (P - 1) M samples plus the incomplete frame move to the handle's other history buffer.
+// The stream's tail -- the last (P - 1) M samples plus the incomplete frame -- is stream_tail.hpp's: its kernel moves it
+// to the handle's other history buffer.
 // Integer input (gr4pm_channelizer_process_iq): both kernels are templated on the input format and convert where a
 // sample enters them -- the load into the stage, vsample(), the history's tail -- with iq_format.hpp's unpack_item(),
 // the very expression gr4pm_iq_unpack evaluates.  The stage, the history and everything behind them stay complex64, so
 // the result is that of process() on the unpacked samples bit for bit, and calls of any format mix on one handle.
-#include "iq_format.hpp"
 #include "kaiser_design.hpp"
+#include "stream_tail.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -54,15 +55,6 @@ struct ChanArgs {
     unsigned lm;            // log2 M
     float scale;            // of an integer format's unpack
 };
-
-template <int F>
-__device__ __forceinline__ float2 vsample(const ChanArgs& a, size_t v)
-{
-    if constexpr (F == iq::kC64)
-        return v < a.H ? a.hist[v] : static_cast<const float2*>(a.in)[v - a.H];
-    else
-        return v < a.H ? a.hist[v] : iq::unpack_item<F>(iq::load_item<F>(a.in, v - a.H), a.scale);
-}
 
 __device__ __forceinline__ void tap(float2& acc, float h, float2 x)
 {
@@ -101,7 +93,7 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
         const unsigned rows = Tw + P - 1;
         for (unsigned i = t; i < (T + P - 1) * M; i += kNt) {
             const unsigned r = i >> lm, m = i & (M - 1);
-            s[r * RS + m] = r < rows ? vsample<F>(a, (f0 + r) * M + m) : float2{0.0f, 0.0f};
+            s[r * RS + m] = r < rows ? iq::vsample<F>(a.hist, a.H, a.in, a.scale, (f0 + r) * M + m) : float2{0.0f, 0.0f};
         }
         __syncthreads();
         const unsigned m = t & (M - 1), n0 = t >> lm; // kNt is a multiple of M: one branch per thread
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
             const unsigned idx = o * kNt + t, n = idx >> lm, m = idx & (M - 1);
             if (n < Tw)
                 for (unsigned p = 0; p < P; ++p)
-                    tap(acc[o], a.taps_r[p * M + m], vsample<F>(a, (f0 + n + P - 1 - p) * M + m));
+                    tap(acc[o], a.taps_r[p * M + m], iq::vsample<F>(a.hist, a.H, a.in, a.scale, (f0 + n + P - 1 - p) * M + m));
             s[n * RS + m] = acc[o];
         }
     }
@@ -172,27 +164,12 @@ __global__ __launch_bounds__(kNt) void k_channelize(ChanArgs a)
     }
 }
 
-// the stream's last H_new samples (of hist[0 .. H) followed by in[0 .. n_in)) into the other history buffer
-template <int F>
-__global__ __launch_bounds__(256) void k_chan_history(const float2* hist, size_t H, const void* in, size_t n_in, float scale,
-                                                      float2* hist_new, size_t H_new)
-{
-    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= H_new) return;
-    const size_t v = H + n_in - H_new + i;
-    if constexpr (F == iq::kC64)
-        hist_new[i] = v < H ? hist[v] : static_cast<const float2*>(in)[v - H];
-    else
-        hist_new[i] = v < H ? hist[v] : iq::unpack_item<F>(iq::load_item<F>(in, v - H), scale);
-}
-
 bool power_of_two_in_range(size_t M) { return M >= 2 && M <= kMaxM && (M & (M - 1)) == 0; }
 
 size_t smem_fast(size_t M, size_t P) { return (M / 2 + (kPoints / M + P - 1) * (M + 1)) * sizeof(float2); }
 size_t smem_generic(size_t M) { return (M / 2 + (kPoints / M) * (M + 1)) * sizeof(float2); }
 
-// the checks of the channelizer's design; the design itself is kaiser_design.hpp's (shared with ddc.hip)
-gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, std::vector<double>& h)
+gr4pm_status check_shape(size_t M, size_t P)
 {
     using gr4pm::set_error;
     if (!power_of_two_in_range(M)) {
@@ -203,8 +180,15 @@ gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, s
         set_error("channelizer: taps per branch must be in [1, %zu], not %zu", kMaxP, P);
         return GR4PM_ERR_INVALID;
     }
-    if (!(passband >= 0.0) || !(passband < stopband) || !(passband + stopband < static_cast<double>(M))) {
-        set_error("channelizer: need 0 <= passband < stopband (units of the channel spacing) and a cutoff below fs / 2");
+    return GR4PM_OK;
+}
+
+// the checks of the channelizer's design; the design itself is kaiser_design.hpp's (shared with ddc.hip)
+gr4pm_status design_taps(size_t M, size_t P, double passband, double stopband, std::vector<double>& h)
+{
+    GR4PM_TRY(check_shape(M, P));
+    if (!gr4pm::band_edges_valid(passband, stopband, M, false)) {
+        gr4pm::set_error("channelizer: need 0 <= passband < stopband (units of the channel spacing) and a cutoff below fs / 2");
         return GR4PM_ERR_INVALID;
     }
     gr4pm::kaiser_lowpass(P * M, M, passband, stopband, h);
@@ -220,30 +204,16 @@ const void* channelize_fn(bool fast, size_t M)
                                        : reinterpret_cast<const void*>(&k_channelize<8, F>)));
 }
 
-// (channelize_fn() is the one place that maps a form and a size to an instantiation)
-template <int F>
-void launch(bool fast, size_t M, size_t P, dim3 grid, hipStream_t s, const ChanArgs& a, size_t n_in, float2* hist_new, size_t H_new)
-{
-    if (a.n_frames) {
-        void* args[] = {const_cast<ChanArgs*>(&a)};
-        (void)hipLaunchKernel(channelize_fn<F>(fast, M), grid, dim3(kNt), args, fast ? smem_fast(M, P) : smem_generic(M), s);
-    }
-    if (H_new)
-        hipLaunchKernelGGL(k_chan_history<F>, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, s, a.hist, a.H, a.in,
-                           n_in, a.scale, hist_new, H_new);
-}
-
 } // namespace
 
 struct gr4pm_channelizer {
     size_t M = 0, P = 0, max_frames = 0;
     unsigned lm = 0, n_rows = 0;
     bool fast = false, selected = false;
-    size_t carried = 0; // samples of the incomplete frame, < M
-    int cur = 0;        // which history buffer holds the stream's tail
+    gr4pm::StreamTail tail; // (P - 1) M samples of history, then the incomplete frame
     hipStream_t stream = nullptr;
     gr4pm::DevBuf<float> d_taps;
-    gr4pm::DevBuf<float2> d_twiddle, d_hist[2];
+    gr4pm::DevBuf<float2> d_twiddle;
     gr4pm::DevBuf<unsigned> d_select;
 };
 
@@ -260,9 +230,13 @@ static gr4pm_status process_any(gr4pm_channelizer* h, const void* in, int format
         return GR4PM_ERR_OVERFLOW;
     }
     if (n_in == 0) return GR4PM_OK;
-    if (!in) return GR4PM_ERR_INVALID;
+    if (!in) {
+        set_error("channelizer: no input array");
+        return GR4PM_ERR_INVALID;
+    }
     const size_t M = h->M, P = h->P;
-    const size_t F = (h->carried + n_in) / M;
+    const StreamTail::Plan t = h->tail.plan(n_in);
+    const size_t F = t.n_frames;
     if (F > out_cap_frames) {
         set_error("channelizer: %zu frames, room for %zu", F, out_cap_frames);
         return GR4PM_ERR_OVERFLOW;
@@ -271,18 +245,14 @@ static gr4pm_status process_any(gr4pm_channelizer* h, const void* in, int format
         set_error("channelizer: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
         return GR4PM_ERR_INVALID;
     }
-    const size_t H = (P - 1) * M + h->carried;
-    const size_t carried_new = (h->carried + n_in) % M;
-    const size_t H_new = (P - 1) * M + carried_new;
-    const float2* hist = h->d_hist[h->cur].p;
     ChanArgs a;
-    a.hist = hist;
+    a.hist = t.hist;
     a.in = in;
     a.out = reinterpret_cast<float2*>(out);
     a.taps_r = h->d_taps.p;
     a.twiddle = h->d_twiddle.p;
     a.select = h->selected ? h->d_select.p : nullptr;
-    a.H = H;
+    a.H = t.H;
     a.out_stride = out_stride;
     a.n_frames = F;
     a.n_rows = h->n_rows;
@@ -291,18 +261,17 @@ static gr4pm_status process_any(gr4pm_channelizer* h, const void* in, int format
     a.scale = scale;
     const size_t T = kPoints / M;
     const dim3 grid(static_cast<unsigned>((F + T - 1) / T));
-    float2* hist_new = h->d_hist[1 - h->cur].p;
-    if (format == GR4PM_IQ_SC16)
-        launch<GR4PM_IQ_SC16>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
-    else if (format == GR4PM_IQ_SC8)
-        launch<GR4PM_IQ_SC8>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
-    else if (format == GR4PM_IQ_CU8)
-        launch<GR4PM_IQ_CU8>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
-    else
-        launch<iq::kC64>(h->fast, M, P, grid, h->stream, a, n_in, hist_new, H_new);
+    const size_t smem = h->fast ? smem_fast(M, P) : smem_generic(M);
+    iq::with_format(format, [&](auto f) {
+        constexpr int Fm = decltype(f)::value;
+        if (F) {
+            void* args[] = {&a};
+            (void)hipLaunchKernel(channelize_fn<Fm>(h->fast, M), grid, dim3(kNt), args, smem, h->stream);
+        }
+        h->tail.launch_history<Fm>(t, in, 0, n_in, scale, h->stream);
+    });
     GR4PM_HIP_TRY(hipGetLastError());
-    h->cur = 1 - h->cur;
-    h->carried = carried_new;
+    h->tail.commit(t);
     *n_frames = F;
     return GR4PM_OK;
 }
@@ -314,7 +283,7 @@ try {
     if (!out) return GR4PM_ERR_INVALID;
     std::vector<double> h;
     GR4PM_TRY(design_taps(n_channels, taps_per_branch, passband, stopband, h));
-    for (size_t t = 0; t < h.size(); ++t) out[t] = static_cast<float>(h[t]);
+    round_taps(h, out);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -324,14 +293,7 @@ try {
     if (!p || !out) return GR4PM_ERR_INVALID;
     *out = nullptr;
     const size_t M = p->n_channels, P = p->taps_per_branch;
-    if (!power_of_two_in_range(M)) {
-        set_error("channelizer: M must be a power of two in [2, %zu], not %zu", kMaxM, M);
-        return GR4PM_ERR_INVALID;
-    }
-    if (P < 1 || P > kMaxP) {
-        set_error("channelizer: taps per branch must be in [1, %zu], not %zu", kMaxP, P);
-        return GR4PM_ERR_INVALID;
-    }
+    GR4PM_TRY(check_shape(M, P));
     if (p->max_frames == 0 || p->max_frames > (size_t(1) << 31)) {
         set_error("channelizer: max_frames must be in [1, 2^31]");
         return GR4PM_ERR_INVALID;
@@ -353,21 +315,11 @@ try {
             sel[i] = k;
         }
     }
-    std::vector<float> taps(P * M);
-    if (p->taps) {
-        for (size_t t = 0; t < P * M; ++t) taps[t] = p->taps[t];
-    } else {
-        std::vector<double> h;
-        GR4PM_TRY(design_taps(M, P, 0.25, 0.75, h));
-        for (size_t t = 0; t < P * M; ++t) taps[t] = static_cast<float>(h[t]);
-    }
+    std::vector<float> taps;
+    GR4PM_TRY(taps_or_design(p->taps, P * M, [&](std::vector<double>& hd) { return design_taps(M, P, 0.25, 0.75, hd); }, taps));
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_channelizer;
+    std::unique_ptr<gr4pm_channelizer> h(new (std::nothrow) gr4pm_channelizer);
     if (!h) return GR4PM_ERR_NOMEM;
-    auto bail = [&](gr4pm_status st) {
-        delete h;
-        return st;
-    };
     h->M = M;
     h->P = P;
     h->max_frames = p->max_frames;
@@ -379,7 +331,7 @@ try {
     h->fast = (M == 16 || M == 64 || M == 256) && smem_fast(M, P) <= kFastSmem && !(form && !strcmp(form, "generic"));
     if (form && *form && strcmp(form, "generic") && strcmp(form, "fast")) {
         set_error("channelizer: GR4PM_CHANNELIZER=%s (generic or fast)", form);
-        return bail(GR4PM_ERR_INVALID);
+        return GR4PM_ERR_INVALID;
     }
 
     std::vector<float> taps_r(P * M);
@@ -393,32 +345,18 @@ try {
     // exact where the angle is a multiple of pi / 2 (cos(pi / 2) in double is 6e-17, not 0)
     tw[0] = float2{1.0f, 0.0f};
     if (M >= 4) tw[M / 4] = float2{0.0f, -1.0f};
-    gr4pm_status st;
-    if ((st = h->d_taps.alloc(P * M)) != GR4PM_OK || (st = h->d_twiddle.alloc(M / 2)) != GR4PM_OK ||
-        (st = h->d_hist[0].alloc(P * M)) != GR4PM_OK || (st = h->d_hist[1].alloc(P * M)) != GR4PM_OK ||
-        (st = h->d_select.alloc(sel.size())) != GR4PM_OK)
-        return bail(st);
-    if ((st = h->d_taps.upload(taps_r.data(), taps_r.size(), h->stream)) != GR4PM_OK ||
-        (st = h->d_twiddle.upload(tw.data(), tw.size(), h->stream)) != GR4PM_OK ||
-        (st = h->d_hist[0].zero(h->stream)) != GR4PM_OK || (st = h->d_hist[1].zero(h->stream)) != GR4PM_OK)
-        return bail(st);
-    if (!sel.empty() && (st = h->d_select.upload(sel.data(), sel.size(), h->stream)) != GR4PM_OK) return bail(st);
-    const size_t smem = h->fast ? smem_fast(M, P) : smem_generic(M);
-    if (smem > 48 * 1024) { // beyond the default dynamic-LDS window
-        const void* fns[] = {channelize_fn<iq::kC64>(h->fast, M), channelize_fn<GR4PM_IQ_SC16>(h->fast, M),
-                             channelize_fn<GR4PM_IQ_SC8>(h->fast, M), channelize_fn<GR4PM_IQ_CU8>(h->fast, M)};
-        for (const void* fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kFastSmem)) != hipSuccess) {
-                set_error("channelizer: hipFuncSetAttribute(%zu bytes of LDS) failed", kFastSmem);
-                return bail(GR4PM_ERR_HIP);
-            }
-    }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
-        set_error("channelizer: hipStreamSynchronize failed at create");
-        return bail(GR4PM_ERR_HIP);
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_taps.alloc(P * M));
+    GR4PM_TRY(h->d_twiddle.alloc(M / 2));
+    GR4PM_TRY(h->d_select.alloc(sel.size()));
+    GR4PM_TRY(h->tail.alloc((P - 1) * M, M, 1, h->stream));
+    GR4PM_TRY(h->d_taps.upload(taps_r.data(), taps_r.size(), h->stream));
+    GR4PM_TRY(h->d_twiddle.upload(tw.data(), tw.size(), h->stream));
+    if (!sel.empty()) GR4PM_TRY(h->d_select.upload(sel.data(), sel.size(), h->stream));
+    if ((h->fast ? smem_fast(M, P) : smem_generic(M)) > 48 * 1024)
+        GR4PM_TRY(raise_dynamic_lds({channelize_fn<iq::kC64>(h->fast, M), channelize_fn<GR4PM_IQ_SC16>(h->fast, M),
+                                     channelize_fn<GR4PM_IQ_SC8>(h->fast, M), channelize_fn<GR4PM_IQ_CU8>(h->fast, M)},
+                                    kFastSmem, "channelizer"));
+    return finish_create(h, out, "channelizer");
 }
 GR4PM_ABI_CATCH
 
@@ -433,16 +371,14 @@ GR4PM_ABI_CATCH_VOID
 gr4pm_status gr4pm_channelizer_reset(gr4pm_channelizer* h)
 try {
     if (!h) return GR4PM_ERR_INVALID;
-    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
-    h->carried = 0;
-    return GR4PM_OK;
+    return h->tail.reset(h->stream);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_channelizer_output_items(const gr4pm_channelizer* h, size_t n_in, size_t* n_frames)
 try {
     if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    *n_frames = (h->carried + n_in) / h->M;
+    *n_frames = h->tail.frames(n_in);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH

@@ -18,13 +18,14 @@
 //   within 64 KiB: L > Lc runs the t loop over re-staged chunks, still ascending in t, so chunking changes no bit.  Each channel's T items leave as one contiguous run, lanes on consecutive items.
 //   One form serves every size: a tile shrinks to T >= 3 frames at D = 1024, which wastes lanes but not correctness.
 // Every result is a function of (channel, frame, stream) only: it does not depend on how the stream is cut into calls.
-// k_ddc_history: the last L - 1 samples plus the incomplete frame move to the handle's other history buffer.
+// The stream's tail -- the last L - 1 samples plus the incomplete frame -- is stream_tail.hpp's: its kernel moves it to
+// the handle's other history buffer.
 // Integer input (gr4pm_ddc_process_iq): both kernels are templated on the input format and convert where a sample
 // enters them with iq_format.hpp's unpack_item(), the very expression gr4pm_iq_unpack evaluates; the stage and the
 // history stay complex64, so the result is that of process() on the unpacked samples bit for bit.
-#include "iq_format.hpp"
 #include "freq_xlate.hpp"
 #include "kaiser_design.hpp"
+#include "stream_tail.hpp"
 
 #include <cmath>
 
@@ -57,15 +58,6 @@ struct DdcArgs {
     float scale;          // of an integer format's unpack
 };
 
-template <int F>
-__device__ __forceinline__ float2 vsample(const DdcArgs& a, size_t v)
-{
-    if constexpr (F == iq::kC64)
-        return v < a.H ? a.hist[v] : static_cast<const float2*>(a.in)[v - a.H];
-    else
-        return v < a.H ? a.hist[v] : iq::unpack_item<F>(iq::load_item<F>(a.in, v - a.H), a.scale);
-}
-
 // NC: channels of this workgroup's group; F: the input's format (iq::kC64: complex64)
 template <int NC, int F>
 __device__ __forceinline__ void ddc_tile(const DdcArgs& a, float2* s)
@@ -90,7 +82,7 @@ __device__ __forceinline__ void ddc_tile(const DdcArgs& a, float2* s)
             const unsigned col = D == 1 ? j : __umulhi(j, a.rcpD);
             const unsigned row = j - col * D;
             const size_t v = vb + j;
-            s[row * RS + col] = v < a.total ? vsample<F>(a, v) : float2{0.0f, 0.0f};
+            s[row * RS + col] = v < a.total ? iq::vsample<F>(a.hist, a.H, a.in, a.scale, v) : float2{0.0f, 0.0f};
         }
         __syncthreads();
         if (tid < T) {
@@ -144,29 +136,6 @@ __global__ __launch_bounds__(kNt) void k_ddc(DdcArgs a)
     }
 }
 
-// the stream's last H_new samples (of hist[0 .. H) followed by in[0 .. n_in)) into the other history buffer
-template <int F>
-__global__ __launch_bounds__(256) void k_ddc_history(const float2* hist, size_t H, const void* in, size_t n_in, float scale,
-                                                     float2* hist_new, size_t H_new)
-{
-    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= H_new) return;
-    const size_t v = H + n_in - H_new + i;
-    if constexpr (F == iq::kC64)
-        hist_new[i] = v < H ? hist[v] : static_cast<const float2*>(in)[v - H];
-    else
-        hist_new[i] = v < H ? hist[v] : iq::unpack_item<F>(iq::load_item<F>(in, v - H), scale);
-}
-
-template <int F>
-void launch(dim3 grid, size_t smem, hipStream_t s, const DdcArgs& a, size_t n_in, float2* hist_new, size_t H_new)
-{
-    if (a.n_frames) hipLaunchKernelGGL(k_ddc<F>, grid, dim3(kNt), smem, s, a);
-    if (H_new)
-        hipLaunchKernelGGL(k_ddc_history<F>, dim3(static_cast<unsigned>((H_new + 255) / 256)), dim3(256), 0, s, a.hist, a.H, a.in,
-                           n_in, a.scale, hist_new, H_new);
-}
-
 gr4pm_status design_taps(size_t D, size_t P, double passband, double stopband, std::vector<double>& h)
 {
     using gr4pm::set_error;
@@ -178,7 +147,7 @@ gr4pm_status design_taps(size_t D, size_t P, double passband, double stopband, s
         set_error("ddc: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", P, D, kMaxL);
         return GR4PM_ERR_INVALID;
     }
-    if (!(passband >= 0.0) || !(passband < stopband) || !(passband + stopband <= static_cast<double>(D))) {
+    if (!gr4pm::band_edges_valid(passband, stopband, D, true)) {
         set_error("ddc: need 0 <= passband < stopband (units of the output rate) and a cutoff of at most fs / 2");
         return GR4PM_ERR_INVALID;
     }
@@ -193,12 +162,11 @@ struct gr4pm_ddc {
     unsigned T = 0, Lc = 0, RS = 0, rcpD = 0;
     size_t smem = 0;
     uint64_t start_index = 0;
-    uint64_t pos = 0;   // absolute index of the first sample that is not yet part of a produced frame
-    size_t carried = 0; // samples of the incomplete frame, < D
-    int cur = 0;        // which history buffer holds the stream's tail
+    uint64_t pos = 0;       // absolute index of the first sample that is not yet part of a produced frame
+    gr4pm::StreamTail tail; // L - 1 samples of history, then the incomplete frame
     hipStream_t stream = nullptr;
     std::vector<uint32_t> words;
-    gr4pm::DevBuf<float2> d_g, d_hist[2];
+    gr4pm::DevBuf<float2> d_g;
     gr4pm::DevBuf<uint32_t> d_w;
 };
 
@@ -220,7 +188,8 @@ static gr4pm_status process_any(gr4pm_ddc* h, const void* in, int format, float 
         return GR4PM_ERR_INVALID;
     }
     const size_t D = h->D, L = h->L;
-    const size_t F = (h->carried + n_in) / D;
+    const StreamTail::Plan t = h->tail.plan(n_in);
+    const size_t F = t.n_frames;
     if (F > out_cap_frames) {
         set_error("ddc: %zu frames, room for %zu", F, out_cap_frames);
         return GR4PM_ERR_OVERFLOW;
@@ -229,17 +198,14 @@ static gr4pm_status process_any(gr4pm_ddc* h, const void* in, int format, float 
         set_error("ddc: no output array, or a row stride of %zu items for %zu frames", out_stride, F);
         return GR4PM_ERR_INVALID;
     }
-    const size_t H = (L - 1) + h->carried;
-    const size_t carried_new = (h->carried + n_in) % D;
-    const size_t H_new = (L - 1) + carried_new;
     DdcArgs a;
-    a.hist = h->d_hist[h->cur].p;
+    a.hist = t.hist;
     a.in = in;
     a.out = reinterpret_cast<float2*>(out);
     a.g = h->d_g.p;
     a.w = h->d_w.p;
-    a.H = H;
-    a.total = H + n_in;
+    a.H = t.H;
+    a.total = t.H + n_in;
     a.out_stride = out_stride;
     a.n_frames = F;
     a.pos = h->pos;
@@ -252,18 +218,13 @@ static gr4pm_status process_any(gr4pm_ddc* h, const void* in, int format, float 
     a.rcpD = h->rcpD;
     a.scale = scale;
     const dim3 grid(static_cast<unsigned>((F + h->T - 1) / h->T), static_cast<unsigned>((h->K + kGroup - 1) / kGroup));
-    float2* hist_new = h->d_hist[1 - h->cur].p;
-    if (format == GR4PM_IQ_SC16)
-        launch<GR4PM_IQ_SC16>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
-    else if (format == GR4PM_IQ_SC8)
-        launch<GR4PM_IQ_SC8>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
-    else if (format == GR4PM_IQ_CU8)
-        launch<GR4PM_IQ_CU8>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
-    else
-        launch<iq::kC64>(grid, h->smem, h->stream, a, n_in, hist_new, H_new);
+    iq::with_format(format, [&](auto f) {
+        constexpr int Fm = decltype(f)::value;
+        if (F) hipLaunchKernelGGL(k_ddc<Fm>, grid, dim3(kNt), h->smem, h->stream, a);
+        h->tail.launch_history<Fm>(t, in, 0, n_in, scale, h->stream);
+    });
     GR4PM_HIP_TRY(hipGetLastError());
-    if (H_new) h->cur = 1 - h->cur;
-    h->carried = carried_new;
+    h->tail.commit(t);
     h->pos += static_cast<uint64_t>(F) * D;
     *n_frames = F;
     return GR4PM_OK;
@@ -276,7 +237,7 @@ try {
     if (!out) return GR4PM_ERR_INVALID;
     std::vector<double> h;
     GR4PM_TRY(design_taps(decimation, taps_per_phase, passband, stopband, h));
-    for (size_t t = 0; t < h.size(); ++t) out[t] = static_cast<float>(h[t]);
+    round_taps(h, out);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -286,48 +247,26 @@ try {
     if (!p || !out) return GR4PM_ERR_INVALID;
     *out = nullptr;
     const size_t K = p->n_channels, D = p->decimation;
-    if (K < 1 || K > kMaxK) {
-        set_error("ddc: the number of channels must be in [1, %zu], not %zu", kMaxK, K);
-        return GR4PM_ERR_INVALID;
-    }
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("ddc", p->frequencies, K, kMaxK, words));
     if (D < 1 || D > kMaxD) {
         set_error("ddc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
         return GR4PM_ERR_INVALID;
     }
-    if (!p->frequencies) {
-        set_error("ddc: no frequencies");
-        return GR4PM_ERR_INVALID;
-    }
-    for (size_t k = 0; k < K; ++k)
-        if (!std::isfinite(p->frequencies[k])) {
-            set_error("ddc: frequencies[%zu] is not finite", k);
-            return GR4PM_ERR_INVALID;
-        }
     if (p->max_frames == 0 || p->max_frames > (size_t(1) << 31)) {
         set_error("ddc: max_frames must be in [1, 2^31]");
         return GR4PM_ERR_INVALID;
     }
-    std::vector<float> taps;
-    if (p->taps) {
-        if (p->n_taps < 1 || p->n_taps > kMaxL) {
-            set_error("ddc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
-            return GR4PM_ERR_INVALID;
-        }
-        taps.assign(p->taps, p->taps + p->n_taps);
-    } else {
-        std::vector<double> hd;
-        GR4PM_TRY(design_taps(D, 12, 0.25, 0.75, hd));
-        taps.resize(hd.size());
-        for (size_t t = 0; t < hd.size(); ++t) taps[t] = static_cast<float>(hd[t]);
+    if (p->taps && (p->n_taps < 1 || p->n_taps > kMaxL)) {
+        set_error("ddc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
+        return GR4PM_ERR_INVALID;
     }
+    std::vector<float> taps;
+    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) { return design_taps(D, 12, 0.25, 0.75, hd); }, taps));
     const size_t L = taps.size();
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_ddc;
+    std::unique_ptr<gr4pm_ddc> h(new (std::nothrow) gr4pm_ddc);
     if (!h) return GR4PM_ERR_NOMEM;
-    auto bail = [&](gr4pm_status st) {
-        delete h;
-        return st;
-    };
     h->K = K;
     h->D = D;
     h->L = L;
@@ -348,43 +287,29 @@ try {
     h->T = static_cast<unsigned>(T);
     h->Lc = static_cast<unsigned>((extra + 1) * D < L ? (extra + 1) * D : L);
     h->RS = static_cast<unsigned>((T + extra) | 1);
-    h->rcpD = D >= 2 ? static_cast<unsigned>(((uint64_t(1) << 32) + D - 1) / D) : 0u;
+    h->rcpD = reciprocal_word(D);
     h->smem = static_cast<size_t>(h->RS) * D * sizeof(float2);
 
-    h->words.resize(K);
+    h->words = std::move(words);
     std::vector<float2> g(K * L);
     for (size_t k = 0; k < K; ++k) {
-        const uint32_t w = h->words[k] = frequency_word(p->frequencies[k]);
+        const uint32_t w = h->words[k];
         // a group's taps interleaved by channel: tap t of all its channels side by side
         const size_t k0 = k / kGroup * kGroup, nc = K - k0 < static_cast<size_t>(kGroup) ? K - k0 : static_cast<size_t>(kGroup);
         for (size_t t = 0; t < L; ++t) {
             g[k0 * L + t * nc + (k - k0)] = rotated_tap(static_cast<double>(taps[t]), w * static_cast<uint32_t>(t));
         }
     }
-    gr4pm_status st;
-    if ((st = h->d_g.alloc(K * L)) != GR4PM_OK || (st = h->d_w.alloc(K)) != GR4PM_OK ||
-        (st = h->d_hist[0].alloc(L - 1 + D)) != GR4PM_OK || (st = h->d_hist[1].alloc(L - 1 + D)) != GR4PM_OK)
-        return bail(st);
-    if ((st = h->d_g.upload(g.data(), g.size(), h->stream)) != GR4PM_OK ||
-        (st = h->d_w.upload(h->words.data(), K, h->stream)) != GR4PM_OK ||
-        (st = h->d_hist[0].zero(h->stream)) != GR4PM_OK || (st = h->d_hist[1].zero(h->stream)) != GR4PM_OK)
-        return bail(st);
-    if (h->smem > 48 * 1024) { // beyond the default dynamic-LDS window
-        const void* fns[] = {reinterpret_cast<const void*>(&k_ddc<iq::kC64>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC16>),
-                             reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC8>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_CU8>)};
-        for (const void* fn : fns)
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    static_cast<int>(kStageItems * sizeof(float2))) != hipSuccess) {
-                set_error("ddc: hipFuncSetAttribute(%zu bytes of LDS) failed", kStageItems * sizeof(float2));
-                return bail(GR4PM_ERR_HIP);
-            }
-    }
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
-        set_error("ddc: hipStreamSynchronize failed at create");
-        return bail(GR4PM_ERR_HIP);
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_g.alloc(K * L));
+    GR4PM_TRY(h->d_w.alloc(K));
+    GR4PM_TRY(h->tail.alloc(L - 1, D, 1, h->stream));
+    GR4PM_TRY(h->d_g.upload(g.data(), g.size(), h->stream));
+    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
+    if (h->smem > 48 * 1024)
+        GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_ddc<iq::kC64>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC16>),
+                                     reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_SC8>), reinterpret_cast<const void*>(&k_ddc<GR4PM_IQ_CU8>)},
+                                    kStageItems * sizeof(float2), "ddc"));
+    return finish_create(h, out, "ddc");
 }
 GR4PM_ABI_CATCH
 
@@ -399,8 +324,7 @@ GR4PM_ABI_CATCH_VOID
 gr4pm_status gr4pm_ddc_reset(gr4pm_ddc* h)
 try {
     if (!h) return GR4PM_ERR_INVALID;
-    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
-    h->carried = 0;
+    GR4PM_TRY(h->tail.reset(h->stream));
     h->pos = h->start_index;
     return GR4PM_OK;
 }
@@ -409,7 +333,7 @@ GR4PM_ABI_CATCH
 gr4pm_status gr4pm_ddc_output_items(const gr4pm_ddc* h, size_t n_in, size_t* n_frames)
 try {
     if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    *n_frames = (h->carried + n_in) / h->D;
+    *n_frames = h->tail.frames(n_in);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH

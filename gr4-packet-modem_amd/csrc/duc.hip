@@ -25,10 +25,11 @@
 //   accumulating lanes (consecutive frames of one phase) and the storing lanes (consecutive samples, so consecutive
 //   phases) both hit distinct banks, and the tile leaves as 16-byte stores contiguous across the workgroup.
 // A result is a function of (absolute output index, the rows' streams) only: not of call or tile sizes.
-// k_duc_history: the last P - 1 items of every row move to the handle's other history buffer.
-#include "common.hpp"
+// The rows' tails -- the last P - 1 items of each -- are stream_tail.hpp's: its kernel moves them to the handle's other
+// history buffer.
 #include "freq_xlate.hpp"
 #include "kaiser_design.hpp"
+#include "stream_tail.hpp"
 
 #include <cmath>
 
@@ -165,17 +166,6 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
     }
 }
 
-// the last P - 1 items of every row (of hist[k][0 .. P - 1) followed by in[k][0 .. n_in)) into the other history buffer
-__global__ __launch_bounds__(256) void k_duc_history(const float2* hist, const float2* in, size_t in_stride, size_t n_in,
-                                                     float2* hist_new, size_t H, size_t K)
-{
-    const size_t idx = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (idx >= K * H) return;
-    const size_t k = idx / H, i = idx - k * H;
-    const size_t v = n_in + i; // of the row's virtual stream, whose last H items these are
-    hist_new[idx] = v < H ? hist[k * H + v] : in[k * in_stride + (v - H)];
-}
-
 template <int R>
 void launch_r(dim3 grid, size_t smem, hipStream_t s, const DucArgs& a, const float2* g)
 {
@@ -193,7 +183,7 @@ gr4pm_status design_taps(size_t I, size_t P, double passband, double stopband, s
         set_error("duc: %zu taps per phase at an interpolation of %zu: the prototype has 1 .. %zu taps", P, I, kMaxL);
         return GR4PM_ERR_INVALID;
     }
-    if (!(passband >= 0.0) || !(passband < stopband) || !(passband + stopband <= static_cast<double>(I))) {
+    if (!gr4pm::band_edges_valid(passband, stopband, I, true)) {
         set_error("duc: need 0 <= passband < stopband (units of the input rate) and a cutoff of at most fs / 2");
         return GR4PM_ERR_INVALID;
     }
@@ -208,11 +198,11 @@ struct gr4pm_duc {
     unsigned R = 0, IP = 0, T = 0, TS = 0, WF = 0, G = 0, Pc = 0, ZS = 0, rcpI = 0;
     size_t smem = 0;
     uint64_t start_index = 0;
-    uint64_t pos = 0; // absolute index of the next output sample
-    int cur = 0;      // which history buffer holds the rows' tails
+    uint64_t pos = 0;       // absolute index of the next output sample
+    gr4pm::StreamTail tail; // P - 1 items of every row, frames of one item: nothing is ever carried
     hipStream_t stream = nullptr;
     std::vector<uint32_t> words;
-    gr4pm::DevBuf<float2> d_g, d_hist[2];
+    gr4pm::DevBuf<float2> d_g;
     gr4pm::DevBuf<uint32_t> d_w;
 };
 
@@ -225,7 +215,7 @@ try {
     if (!out) return GR4PM_ERR_INVALID;
     std::vector<double> h;
     GR4PM_TRY(design_taps(interpolation, taps_per_phase, passband, stopband, h));
-    for (size_t t = 0; t < h.size(); ++t) out[t] = static_cast<float>(h[t]);
+    round_taps(h, out);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -235,53 +225,31 @@ try {
     if (!p || !out) return GR4PM_ERR_INVALID;
     *out = nullptr;
     const size_t K = p->n_channels, I = p->interpolation;
-    if (K < 1 || K > kMaxK) {
-        set_error("duc: the number of channels must be in [1, %zu], not %zu", kMaxK, K);
-        return GR4PM_ERR_INVALID;
-    }
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("duc", p->frequencies, K, kMaxK, words));
     if (I < 1 || I > kMaxI) {
         set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
         return GR4PM_ERR_INVALID;
     }
-    if (!p->frequencies) {
-        set_error("duc: no frequencies");
-        return GR4PM_ERR_INVALID;
-    }
-    for (size_t k = 0; k < K; ++k) {
-        if (!std::isfinite(p->frequencies[k])) {
-            set_error("duc: frequencies[%zu] is not finite", k);
-            return GR4PM_ERR_INVALID;
-        }
-        if (p->gains && !std::isfinite(p->gains[k])) {
+    for (size_t k = 0; p->gains && k < K; ++k)
+        if (!std::isfinite(p->gains[k])) {
             set_error("duc: gains[%zu] is not finite", k);
             return GR4PM_ERR_INVALID;
         }
-    }
     if (p->max_items == 0 || p->max_items > (size_t(1) << 31)) {
         set_error("duc: max_items must be in [1, 2^31]");
         return GR4PM_ERR_INVALID;
     }
-    std::vector<float> taps;
-    if (p->taps) {
-        if (p->n_taps < 1 || p->n_taps > kMaxL) {
-            set_error("duc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
-            return GR4PM_ERR_INVALID;
-        }
-        taps.assign(p->taps, p->taps + p->n_taps);
-    } else {
-        std::vector<double> hd;
-        GR4PM_TRY(design_taps(I, 12, 0.25, 0.75, hd));
-        taps.resize(hd.size());
-        for (size_t t = 0; t < hd.size(); ++t) taps[t] = static_cast<float>(hd[t]);
+    if (p->taps && (p->n_taps < 1 || p->n_taps > kMaxL)) {
+        set_error("duc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
+        return GR4PM_ERR_INVALID;
     }
+    std::vector<float> taps;
+    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) { return design_taps(I, 12, 0.25, 0.75, hd); }, taps));
     const size_t L = taps.size(), P = (L + I - 1) / I;
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_duc;
+    std::unique_ptr<gr4pm_duc> h(new (std::nothrow) gr4pm_duc);
     if (!h) return GR4PM_ERR_NOMEM;
-    auto bail = [&](gr4pm_status st) {
-        delete h;
-        return st;
-    };
     h->K = K;
     h->I = I;
     h->L = L;
@@ -310,31 +278,23 @@ try {
     h->G = static_cast<unsigned>(G);
     h->Pc = static_cast<unsigned>(Pc);
     h->ZS = static_cast<unsigned>(T + Pc - 1);
-    h->rcpI = I >= 2 ? static_cast<unsigned>(((uint64_t(1) << 32) + I - 1) / I) : 0u;
+    h->rcpI = reciprocal_word(I);
     h->smem = (IP * h->TS + G * h->ZS) * sizeof(float2); // at most 29 KiB + 16 KiB
 
-    h->words.resize(K);
+    h->words = std::move(words);
     std::vector<float2> g(K * P * IP, float2{0.0f, 0.0f});
     for (size_t k = 0; k < K; ++k) {
-        const uint32_t w = h->words[k] = frequency_word(p->frequencies[k]);
+        const uint32_t w = h->words[k];
         const double a = p->gains ? p->gains[k] : 1.0;
         for (size_t t = 0; t < L; ++t)
             g[(k * P + t / I) * IP + t % I] = rotated_tap(a * static_cast<double>(taps[t]), w * static_cast<uint32_t>(t));
     }
-    gr4pm_status st;
-    if ((st = h->d_g.alloc(g.size())) != GR4PM_OK || (st = h->d_w.alloc(K)) != GR4PM_OK ||
-        (st = h->d_hist[0].alloc(K * (P - 1))) != GR4PM_OK || (st = h->d_hist[1].alloc(K * (P - 1))) != GR4PM_OK)
-        return bail(st);
-    if ((st = h->d_g.upload(g.data(), g.size(), h->stream)) != GR4PM_OK ||
-        (st = h->d_w.upload(h->words.data(), K, h->stream)) != GR4PM_OK ||
-        (st = h->d_hist[0].zero(h->stream)) != GR4PM_OK || (st = h->d_hist[1].zero(h->stream)) != GR4PM_OK)
-        return bail(st);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { // the uploads read host vectors that end with this call
-        set_error("duc: hipStreamSynchronize failed at create");
-        return bail(GR4PM_ERR_HIP);
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_g.alloc(g.size()));
+    GR4PM_TRY(h->d_w.alloc(K));
+    GR4PM_TRY(h->tail.alloc(P - 1, 1, K, h->stream));
+    GR4PM_TRY(h->d_g.upload(g.data(), g.size(), h->stream));
+    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
+    return finish_create(h, out, "duc");
 }
 GR4PM_ABI_CATCH
 
@@ -349,7 +309,7 @@ GR4PM_ABI_CATCH_VOID
 gr4pm_status gr4pm_duc_reset(gr4pm_duc* h)
 try {
     if (!h) return GR4PM_ERR_INVALID;
-    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
+    GR4PM_TRY(h->tail.reset(h->stream));
     h->pos = h->start_index;
     return GR4PM_OK;
 }
@@ -381,7 +341,7 @@ try {
         return GR4PM_ERR_OVERFLOW;
     }
     if (n_in == 0) return GR4PM_OK;
-    const size_t N = n_in * h->I, H = h->P - 1;
+    const size_t N = n_in * h->I;
     if (N > out_cap) {
         set_error("duc: %zu samples, room for %zu", N, out_cap);
         return GR4PM_ERR_OVERFLOW;
@@ -390,8 +350,9 @@ try {
         set_error("duc: no input or output array, or a row stride of %zu items for %zu items", in_stride, n_in);
         return GR4PM_ERR_INVALID;
     }
+    const StreamTail::Plan t = h->tail.plan(n_in);
     DucArgs a;
-    a.hist = h->d_hist[h->cur].p;
+    a.hist = t.hist;
     a.in = reinterpret_cast<const float2*>(in);
     a.out = reinterpret_cast<float2*>(out);
     a.w = h->d_w.p;
@@ -419,11 +380,9 @@ try {
     case 4: launch_r<4>(grid, h->smem, h->stream, a, h->d_g.p); break;
     default: launch_r<8>(grid, h->smem, h->stream, a, h->d_g.p); break;
     }
-    if (H)
-        hipLaunchKernelGGL(k_duc_history, dim3(static_cast<unsigned>((h->K * H + 255) / 256)), dim3(256), 0, h->stream, a.hist,
-                           a.in, in_stride, n_in, h->d_hist[1 - h->cur].p, H, h->K);
+    h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
     GR4PM_HIP_TRY(hipGetLastError());
-    if (H) h->cur = 1 - h->cur;
+    h->tail.commit(t);
     h->pos += N;
     *n_out = N;
     return GR4PM_OK;

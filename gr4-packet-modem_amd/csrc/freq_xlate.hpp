@@ -1,7 +1,8 @@
-// freq_xlate.hpp -- what the Ddc (ddc.hip) and the Duc (duc.hip) share: the frequency word, the rotated-tap table's
-// entries and the complex multiply-accumulate of their definitions (include/gr4pm_hip.h).
+// freq_xlate.hpp -- what the Ddc (ddc.hip) and the Duc (duc.hip) share: the frequency word and create()'s checks of
+// the frequencies, the rotated-tap table's entries and the complex multiply-accumulate of their definitions
+// (include/gr4pm_hip.h).
 #pragma once
-#include <hip/hip_runtime.h>
+#include "common.hpp"
 
 #include <cmath>
 #include <cstdint>
@@ -23,6 +24,31 @@ inline uint32_t frequency_word(double f)
     const double m = std::fmod(f, 1.0);
     return static_cast<uint32_t>(static_cast<uint64_t>(std::llrint(m * 4294967296.0)));
 }
+
+// a create()'s frequencies: 1 .. max_K of them, all finite, as words
+inline gr4pm_status frequency_words(const char* name, const double* f, size_t K, size_t max_K, std::vector<uint32_t>& words)
+{
+    if (K < 1 || K > max_K) {
+        set_error("%s: the number of channels must be in [1, %zu], not %zu", name, max_K, K);
+        return GR4PM_ERR_INVALID;
+    }
+    if (!f) {
+        set_error("%s: no frequencies", name);
+        return GR4PM_ERR_INVALID;
+    }
+    words.resize(K);
+    for (size_t k = 0; k < K; ++k) {
+        if (!std::isfinite(f[k])) {
+            set_error("%s: frequencies[%zu] is not finite", name, k);
+            return GR4PM_ERR_INVALID;
+        }
+        words[k] = frequency_word(f[k]);
+    }
+    return GR4PM_OK;
+}
+
+// ceil(2^32 / n) for n >= 2: j div n = umulhi(j, reciprocal_word(n)) for j < 2^13
+inline unsigned reciprocal_word(size_t n) { return n >= 2 ? static_cast<unsigned>(((uint64_t(1) << 32) + n - 1) / n) : 0u; }
 
 // w / 2^32 folded to [-0.5, 0.5)
 inline double folded_frequency(uint32_t w)

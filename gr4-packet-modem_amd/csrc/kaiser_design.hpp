@@ -7,6 +7,15 @@
 
 namespace gr4pm {
 
+// the band edges a design takes for a decimation by D: 0 <= passband < stopband and the cutoff, midway between them,
+// below fs / 2, or at most fs / 2 where `cutoff_at_nyquist` (the Ddc and the Duc; the Channelizer does not allow it).
+// A NaN fails.
+inline bool band_edges_valid(double passband, double stopband, size_t D, bool cutoff_at_nyquist)
+{
+    const double sum = passband + stopband, d = static_cast<double>(D);
+    return passband >= 0.0 && passband < stopband && (cutoff_at_nyquist ? sum <= d : sum < d);
+}
+
 // Kaiser-windowed sinc of L taps in double for a decimation by D: band edges in units of the output rate fs / D, the
 // cutoff midway between them, the window's beta from the attenuation that Kaiser's length rule gives for L taps over
 // the transition width; DC gain 1, or `gain` (an interpolator's D), applied in double to the unit-gain taps.  The caller

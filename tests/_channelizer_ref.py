@@ -6,6 +6,8 @@ analysis64() computes exactly these lines; analysis64_polyphase() is the form th
 forward M-point DFT per frame) and is pinned to the former by tests/test_channelizer_ref.py."""
 import numpy as np
 
+import _ddc_ref
+
 EPS32 = 2.0 ** -24
 
 
@@ -40,14 +42,7 @@ def analysis64_polyphase(x, h, M):
 
 def kaiser_taps64(M, P=12, passband=0.25, stopband=0.75):
     """the design gr4pm_channelizer_taps states, in numpy, in double (not rounded to float)"""
-    L = P * M
-    dw = 2.0 * np.pi * (stopband - passband) / M
-    A = 2.285 * dw * (L - 1) + 7.95
-    beta = 0.1102 * (A - 8.7) if A > 50 else (0.5842 * (A - 21.0) ** 0.4 + 0.07886 * (A - 21.0) if A >= 21 else 0.0)
-    fc = 0.5 * (passband + stopband) / M
-    t = np.arange(L) - 0.5 * (L - 1)
-    h = 2.0 * fc * np.sinc(2.0 * fc * t) * np.kaiser(L, beta)
-    return h / np.sum(h)
+    return _ddc_ref.kaiser_taps64(M, P * M, passband, stopband)
 
 
 def response_db(h, M, oversample=64):

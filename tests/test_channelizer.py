@@ -14,6 +14,7 @@ import pytest
 
 import _channelizer_ref as cref
 import test_syncword_float64 as t64
+from _frontend import bits, dev, exact_iq_forms, host, load_package, received_packets, short_calls_of_mixed_formats
 
 pytestmark = pytest.mark.gpu
 
@@ -23,25 +24,7 @@ FAST = [(16, 12), (64, 12), (256, 8), (256, 12)]
 
 @pytest.fixture(scope="module")
 def pkg():
-    torch = pytest.importorskip("torch")
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
+    return load_package()
 
 
 def random_taps(M, P, seed=0):
@@ -122,6 +105,21 @@ def test_one_call_equals_any_chain_of_calls(pkg, M, P):
             cuts.append(pos)
     assert len(cuts) > 30
     assert np.array_equal(bits(run(pkg, x, M, P, h, cuts)), bits(one))
+
+
+def test_short_calls_of_mixed_formats_equal_one_call(pkg):
+    """the history kernel's hard case: calls of 1, 2, 7, 3, 64, 1, ... samples against a tail of 16 to 23, so that most
+    of a new tail comes from the old one and the boundary between the old tail and the call's input falls inside it,
+    the calls by turns complex64, sc16, sc8 and cu8 forms that unpack exactly to the stream: bit for bit what one
+    complex64 call on a fresh handle gives"""
+    M, P = 8, 3
+    x, forms = exact_iq_forms(624, 32)
+    h = random_taps(M, P, 7)
+    one = run(pkg, x, M, P, h)
+    got = short_calls_of_mixed_formats(pkg, pkg.Channelizer(M, taps=h), x, forms)
+    assert one.shape == got.shape == (M, x.size // M)
+    assert np.array_equal(bits(got), bits(one))
+    assert np.all(np.max(np.abs(one), axis=1) > 0)
 
 
 @pytest.mark.timeout(300)
@@ -206,15 +204,6 @@ def test_fast_and_generic_forms_agree_bit_for_bit(pkg, monkeypatch, M, P):
     monkeypatch.setenv("GR4PM_CHANNELIZER", "neither")
     with pytest.raises(pkg.Gr4pmError, match="GR4PM_CHANNELIZER"):
         pkg.Channelizer(M, taps=h)
-
-
-def received_packets(r):
-    data, lens = r["packets"].cpu().numpy(), r["packet_lengths"]
-    got, pos = [], 0
-    for n in lens[lens > 0]:
-        got.append(data[pos:pos + int(n)].tobytes())
-        pos += int(n)
-    return got
 
 
 @pytest.mark.timeout(600)

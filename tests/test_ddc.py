@@ -16,13 +16,12 @@ import pytest
 
 import _ddc_ref as dref
 import test_syncword_float64 as t64
+from _frontend import (FREQ_POOL, bits, dev, exact_iq_forms, host, load_package, random_taps, received_packets,
+                       short_calls_of_mixed_formats)
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(5, 60, 3), (4, 48, 1), (64, 768, 8), (1, 1, 1), (20, 161, 16), (3, 96, 2), (1000, 2000, 2), (16, 8192, 9)]
-# 0, exactly 0.5, a negative one, a word with only low bits set; a shape with K channels takes K from its own offset on
-FREQ_POOL = [0.0, 0.5, -0.3137, 3.0 * 2.0 ** -32, 0.123456789, -0.05, 0.41, 1.0 / 3.0, -0.4999, 0.25, 0.02, -0.17,
-             0.3, -0.26, 0.07, 0.45]
 
 
 def freqs_of(D, L, K):
@@ -32,25 +31,7 @@ def freqs_of(D, L, K):
 
 @pytest.fixture(scope="module")
 def pkg():
-    torch = pytest.importorskip("torch")
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import __graft_entry__ as ge
-    return ge.load_package()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
+    return load_package()
 
 
 def default_taps(pkg, D, L):
@@ -58,12 +39,6 @@ def default_taps(pkg, D, L):
     if L % D == 0:
         return pkg.ddc_taps(D, L // D)
     return dref.kaiser_taps64(D, L).astype(np.float32)
-
-
-def random_taps(D, L, seed=0):
-    """a low-pass shape with random signs mixed in: every tap matters, none is tiny"""
-    rng = np.random.default_rng(seed)
-    return (dref.kaiser_taps64(D, L) * D + 0.05 * rng.standard_normal(L)).astype(np.float32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -245,6 +220,21 @@ def test_integer_ingest_is_bit_equal(pkg):
         assert np.max(np.abs(host(ya))) > 0
 
 
+def test_short_calls_of_mixed_formats_equal_one_call(pkg):
+    """the history kernel's hard case: calls of 1, 2, 7, 3, 64, 1, ... samples against a tail of 59 to 63, so that most
+    of a new tail comes from the old one and the boundary between the old tail and the call's input falls inside it,
+    the calls by turns complex64, sc16, sc8 and cu8 forms that unpack exactly to the stream: bit for bit what one
+    complex64 call on a fresh handle gives"""
+    D, L, K = 5, 60, 3
+    x, forms = exact_iq_forms(624, 31)
+    f, h = freqs_of(D, L, K), random_taps(D, L, 7)
+    one = run(pkg, x, D, f, h, start=99)
+    got = short_calls_of_mixed_formats(pkg, pkg.Ddc(f, D, taps=h, start_index=99), x, forms)
+    assert one.shape == got.shape == (K, x.size // D)
+    assert np.array_equal(bits(got), bits(one))
+    assert np.all(np.max(np.abs(one), axis=1) > 0)
+
+
 @pytest.mark.timeout(300)
 def test_stride_reset_two_handles(pkg):
     import torch
@@ -295,15 +285,6 @@ def test_stride_reset_two_handles(pkg):
     torch.cuda.synchronize()
     assert np.array_equal(bits(host(torch.cat(p1, dim=1))), bits(full))
     assert np.array_equal(bits(host(torch.cat(p2, dim=1))), bits(full2))
-
-
-def received_packets(r):
-    data, lens = r["packets"].cpu().numpy(), r["packet_lengths"]
-    got, pos = [], 0
-    for n in lens[lens > 0]:
-        got.append(data[pos:pos + int(n)].tobytes())
-        pos += int(n)
-    return got
 
 
 @pytest.mark.timeout(600)

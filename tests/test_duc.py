@@ -16,7 +16,7 @@ import pytest
 
 import _ddc_ref as dref
 import _duc_ref as uref
-from test_ddc import FREQ_POOL, bits, dev, host, random_taps, received_packets
+from _frontend import FREQ_POOL, bits, dev, host, load_package, random_taps, received_packets
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +37,7 @@ def gains_of(K):
 
 @pytest.fixture(scope="module")
 def pkg():
-    torch = pytest.importorskip("torch")
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import __graft_entry__ as ge
-    return ge.load_package()
+    return load_package()
 
 
 def default_taps(pkg, I, L):
