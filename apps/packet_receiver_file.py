@@ -2,7 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_receiver_file.cpp (apps/README.md:5-24):
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
-                            [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE --decimate D]
+                            [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE --decimate N[/M]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
 FileSource<c64> freads, file_source.hpp:32,53) at 4 samples/symbol, runs the whole receiver on
@@ -23,7 +23,9 @@ becomes complex64 on the device (gr4pm_iq_unpack, `--scale`: per component, defa
 `--tune F --decimate D`: the file is a wideband recording with the modem's carrier F cycles per file sample off centre
 and D times the modem's rate: it goes through a one-channel `Ddc` (gr4pm_ddc: mix by -F, low-pass, keep every D-th
 sample) in front of the receiver.  Combines with `--format` (the Ddc reads the integers itself).  The
-counts are then in samples at the receiver's rate.
+counts are then in samples at the receiver's rate.  `--decimate N/M` (N >= M, for instance 25/4 for a 25 Msps file of a
+1 Msym/s carrier): N / M file samples per receiver sample, the same Ddc resampling by M / N in the same pass (DESIGN
+section 18), so any symbol rate lands on the receiver's 4 samples per symbol.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -49,9 +51,22 @@ import __graft_entry__ as ge  # noqa: E402
 FILE_DTYPES = {"cf32": torch.complex64, "sc16": torch.int16, "sc8": torch.int8, "cu8": torch.uint8}
 
 
+def decimation(v):
+    """--decimate: `N` or `N/M`, file samples per receiver sample, as (N, M); an integer passes as (N, 1)"""
+    n, _, m = str(v).partition("/")
+    try:
+        n, m = int(n), int(m) if m else 1
+    except ValueError:
+        raise ValueError(f"--decimate: {v!r} is neither N nor N/M") from None
+    if m < 1 or (m > 1 and n < m):
+        raise ValueError(f"--decimate: {v!r}: need N >= M >= 1 (file samples per receiver sample)")
+    return n, m  # a plain integer goes to the Ddc as it is, which refuses what it cannot take
+
+
 def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
                  fmt="cf32", scale=None, tune=None, decimate=None):
-    """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures)"""
+    """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures).  decimate: an
+    integer, "N/M" or (N, M)"""
     pkg = pkg or ge.load_package()
     file_dtype = FILE_DTYPES[fmt]
     shape = (chunk_items,) if fmt == "cf32" else (chunk_items, 2)  # integer IQ: [items, (I, Q)]
@@ -66,7 +81,8 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
         rx.publish_symbol_pdus(f"tcp://*:{zmq_ports[0]}", f"tcp://*:{zmq_ports[1]}")
     ddc = None
     if tune is not None or decimate is not None:
-        ddc = pkg.Ddc([0.0 if tune is None else tune], 1 if decimate is None else decimate, max_frames=chunk_items)
+        dec, interp = (1, 1) if decimate is None else (decimate if isinstance(decimate, tuple) else decimation(decimate))
+        ddc = pkg.Ddc([0.0 if tune is None else tune], dec, interpolation=interp, max_frames=chunk_items)
     fft = 3072  # smallest batch the receiver takes in this mode (one header window + one FFT block)
     pinned = [torch.empty(shape, dtype=file_dtype).pin_memory() for _ in range(2)]
     staged = [torch.empty(shape, dtype=file_dtype, device=dev) for _ in range(2)]
@@ -151,7 +167,8 @@ def main():
     ap.add_argument("--format", choices=list(FILE_DTYPES), default="cf32", help="the file's items (default: complex64)")
     ap.add_argument("--scale", type=float, help="of an integer format's components (default: 2^-15 for sc16, else 2^-7)")
     ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Ddc in front)")
-    ap.add_argument("--decimate", type=int, metavar="D", help="file samples per receiver sample (a Ddc in front)")
+    ap.add_argument("--decimate", type=decimation, metavar="N[/M]",  # argparse reports a type's ValueError as a usage error
+                    help="file samples per receiver sample, an integer or a ratio such as 25/4 (a Ddc in front)")
     a = ap.parse_args()
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,

@@ -206,6 +206,10 @@ class DdcParams(C.Structure):
                 ("n_taps", C.c_size_t), ("max_frames", C.c_size_t), ("start_index", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class DdcRationalParams(C.Structure):
+    _fields_ = DdcParams._fields_ + [("interpolation", C.c_size_t)]
+
+
 class DucParams(C.Structure):
     _fields_ = [("n_channels", C.c_size_t), ("interpolation", C.c_size_t), ("frequencies", C.c_void_p), ("gains", C.c_void_p),
                 ("taps", C.c_void_p), ("n_taps", C.c_size_t), ("max_items", C.c_size_t), ("start_index", C.c_uint64),
@@ -279,6 +283,7 @@ EXPORTS = [
     "gr4pm_iq_unpack", "gr4pm_iq_pack",
     "gr4pm_ddc_taps", "gr4pm_ddc_create", "gr4pm_ddc_destroy", "gr4pm_ddc_reset", "gr4pm_ddc_output_items",
     "gr4pm_ddc_frequencies", "gr4pm_ddc_process", "gr4pm_ddc_process_iq",
+    "gr4pm_ddc_rational_taps", "gr4pm_ddc_create_rational",
     "gr4pm_duc_taps", "gr4pm_duc_create", "gr4pm_duc_destroy", "gr4pm_duc_reset", "gr4pm_duc_output_items",
     "gr4pm_duc_frequencies", "gr4pm_duc_process",
 ]
@@ -488,6 +493,8 @@ def lib():
     L.gr4pm_ddc_frequencies.argtypes = [vp, vp]
     L.gr4pm_ddc_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
     L.gr4pm_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
+    L.gr4pm_ddc_rational_taps.argtypes = [sz, sz, sz, C.c_double, C.c_double, vp]
+    L.gr4pm_ddc_create_rational.argtypes = [C.POINTER(DdcRationalParams), C.POINTER(vp)]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

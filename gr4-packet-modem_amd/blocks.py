@@ -9,6 +9,8 @@ numpy records (TAG_DTYPE) with explicit indices instead of the runtime's chunk-h
 The C++ gr::Block wrappers in host/ are the drop-in for the reference's flowgraphs; this
 module is what the parity tests and bench.py drive."""
 import ctypes as C
+import fractions
+import math
 import os
 
 import numpy as np
@@ -1906,6 +1908,20 @@ def ddc_taps(decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
     return _design_taps("gr4pm_ddc_taps", decimation, taps_per_phase, passband, stopband, "ddc_taps")
 
 
+def ddc_rational_taps(interpolation, decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
+    """gr4pm_ddc_rational_taps: the prototype low-pass of a Ddc that resamples by interpolation / decimation, at the
+    rate interpolation * fs: the Kaiser design of ddc_taps with taps_per_phase * decimation float32 taps and DC gain
+    `interpolation`, scaled in double before the one rounding to float32 (host only: works without a GPU).  passband /
+    stopband: the band edges in units of the output rate; a cutoff beyond half of the lower of the input and the output
+    rate (passband + stopband > min(1, decimation / interpolation)) is refused.  With interpolation = 1 the floats are
+    those of ddc_taps."""
+    n = int(decimation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_ddc_rational_taps(int(interpolation), int(decimation), int(taps_per_phase), float(passband),
+                                        float(stopband), _np_ptr(out)), "ddc_rational_taps")
+    return out[:n]
+
+
 class Ddc:
     """gr4pm_ddc: tunable down-converter.  One wideband complex64 stream at fs becomes len(frequencies) channels at
     fs / decimation: row k is the band centred on frequencies[k] (cycles per input sample, any real value, quantised to
@@ -1915,26 +1931,51 @@ class Ddc:
     taps_per_phase)).  start_index: the absolute index of the first sample (the phase of a channel follows from the
     absolute index in integer arithmetic, exactly, at any stream position).  process_bulk() takes any number of
     samples; the filter history and the samples of an incomplete frame stay on the device.  Frequencies are fixed: make
-    another Ddc to retune.  The handle works on the stream that is current when it is made."""
+    another Ddc to retune.  The handle works on the stream that is current when it is made.
 
-    def __init__(self, frequencies, decimation, taps=None, taps_per_phase=12, start_index=0, max_frames=1 << 22):
-        self.decimation = int(decimation)
+    interpolation = I > 1 (at most 64) resamples by I / decimation in the same pass (gr4pm_ddc_create_rational): the
+    output rate is fs I / decimation (.rate, a Fraction), N samples make floor(N I / decimation) items per row, and
+    the prototype (None: ddc_rational_taps(I, decimation, taps_per_phase)) runs at I fs.  Without taps the pair is
+    reduced to lowest terms (.interpolation and .decimation hold the reduced values); with taps a pair that is not in
+    lowest terms is refused, since the taps belong to one rate.  max_frames bounds the items of one call."""
+
+    def __init__(self, frequencies, decimation, interpolation=1, taps=None, taps_per_phase=12, start_index=0,
+                 max_frames=1 << 22):
+        self.decimation, self.interpolation = int(decimation), int(interpolation)
+        if self.interpolation > 1 and self.decimation >= 1:
+            g = math.gcd(self.interpolation, self.decimation)
+            if g > 1 and taps is not None:
+                raise Gr4pmError(f"Ddc: {self.interpolation} / {self.decimation} is not in lowest terms, and the taps "
+                                 f"belong to one rate: use {self.interpolation // g} / {self.decimation // g}")
+            if g > 1:
+                self.decimation, self.interpolation = self.decimation // g, self.interpolation // g
+        if self.interpolation == 1:
+            design = ddc_taps
+        else:
+            design = lambda d, per: ddc_rational_taps(self.interpolation, d, per)
         f, self.taps, self.start_index = _xlate_settings("Ddc", frequencies, self.decimation, taps, taps_per_phase,
-                                                         start_index, ddc_taps)
+                                                         start_index, design)
+        self.rate = fractions.Fraction(self.interpolation, self.decimation) if self.decimation > 0 else None
         self.n_channels = self.n_rows = int(f.size)
         self.max_frames = int(max_frames)
         stream = _stream_handle()
         self._stream = stream.value
-        p = _abi.DdcParams(self.n_channels, self.decimation, _np_ptr(f) if f.size else None, _np_ptr(self.taps),
-                           self.taps.size, self.max_frames, self.start_index, stream)
         self._h = C.c_void_p()
-        check(lib().gr4pm_ddc_create(C.byref(p), C.byref(self._h)), "Ddc")
+        if self.interpolation == 1:
+            p = _abi.DdcParams(self.n_channels, self.decimation, _np_ptr(f) if f.size else None, _np_ptr(self.taps),
+                               self.taps.size, self.max_frames, self.start_index, stream)
+            check(lib().gr4pm_ddc_create(C.byref(p), C.byref(self._h)), "Ddc")
+        else:
+            p = _abi.DdcRationalParams(self.n_channels, self.decimation, _np_ptr(f) if f.size else None,
+                                       _np_ptr(self.taps), self.taps.size, self.max_frames, self.start_index, stream,
+                                       self.interpolation)
+            check(lib().gr4pm_ddc_create_rational(C.byref(p), C.byref(self._h)), "Ddc")
         q = np.zeros(self.n_channels, dtype=np.float64)
         check(lib().gr4pm_ddc_frequencies(self._h, _np_ptr(q)), "Ddc.frequencies")
         self.frequencies = q
 
     def output_items(self, n_in):
-        """frames (items per row) the next process_bulk() of n_in samples produces"""
+        """items per row the next process_bulk() of n_in samples produces"""
         n = C.c_size_t(0)
         check(lib().gr4pm_ddc_output_items(self._h, int(n_in), C.byref(n)), "Ddc.output_items")
         return n.value

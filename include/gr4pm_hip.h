@@ -1074,6 +1074,58 @@ gr4pm_status gr4pm_ddc_process(gr4pm_ddc* h, const gr4pm_c64* in, size_t n_in, g
 gr4pm_status gr4pm_ddc_process_iq(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
                                   size_t out_stride, size_t out_cap_frames, size_t* n_frames);
 
+/* ------------------------------------------------------------------------------------
+ * Ddc, rational resampling by I / D (output rate fs I / D) in the same pass: a gr4pm_ddc handle made by
+ * gr4pm_ddc_create_rational.  I in [1, 64], D in [1, 1024], gcd(I, D) = 1 (a pair
+ * that is not in lowest terms is refused with GR4PM_ERR_INVALID, the message names the reduced pair).
+ * The real prototype h[0 .. L - 1], 1 <= L <= 8192, runs at the virtual rate I fs; L need not be a
+ * multiple of I: P = ceil(L / I) and h[t] = 0 for t >= L.  w_k, phi_k and x = 0 before the handle's
+ * first sample are the Ddc's above.  Output item n, counted from the handle's start:
+ *     m_n = n D + D - 1                  its index in the stream zero-stuffed by I
+ *     i_n = start_index + m_n div I      its input index
+ *     p_n = m_n mod I                    its polyphase branch
+ *     y_k[n] = sum_{s = 0}^{P - 1} h[p_n + s I] x[i_n - s] exp(-2 pi j phi_k(i_n - s) / 2^32)
+ * With I = 1 this is the Ddc item for item.  For a fixed branch p the items n, n + I, n + 2 I, ... have
+ * i stepping by exactly D: every branch is an integer-D Ddc with the taps h[p::I].  Evaluated as
+ *     g_k[p][s] = h[p + s I] exp(+2 pi j phi_k(s) / 2^32)   on the host in double, with the Ddc's quadrant
+ *                                                           reduction, each component rounded to float once
+ *     r_k[n] = exp(-2 pi j phi_k(i_n) / 2^32)               double sincospi of the exact argument, rounded
+ *     y_k[n] = r_k[n] sum_s g_k[p_n][s] x[i_n - s]
+ * with one accumulator per channel, s ascending over the taps of h[p_n::I], every complex
+ * multiply-accumulate the Ddc's four fmaf in its order and the product with r_k[n] the same four from
+ * zero.  A result is a function of (k, n, stream) only: not of the call cuts, the grid or the input's format.
+ * Stream contract: all input of a call is consumed; item n exists as soon as sample i_n has arrived, so
+ * after N samples in all floor(N I / D) items exist per row.  The handle keeps P - 1 samples of history
+ * on the device and never a partial frame; the position (the next item's input index and branch, and the
+ * samples taken) lives on the host in 64-bit integers and reaches the kernel by value; process() reads
+ * nothing back.  With I > D a call makes more items than it takes samples: max_frames bounds the
+ * output items of a call, n_in I <= max_frames D.
+ * gr4pm_ddc_process / _process_iq / _reset / _output_items / _frequencies / _destroy take such a handle
+ * with the contracts documented above; *n_frames is the item count of this section.  interpolation = 1
+ * makes the handle gr4pm_ddc_create makes, with its results bit for bit.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t decimation;          /* D: 1 .. 1024 */
+    const double* frequencies;  /* host: K frequencies in cycles per input sample, any finite value */
+    const float* taps;          /* host: n_taps prototype taps at the rate I fs, copied at create (NULL: the default
+                                   design, gr4pm_ddc_rational_taps(I, D, 12, 0.25, 0.75)) */
+    size_t n_taps;              /* L: 1 .. 8192 (ignored when taps is NULL) */
+    size_t max_frames;          /* output items per process() call: n_in I <= max_frames D; 1..2^31 */
+    uint64_t start_index;       /* absolute index of the first sample the handle sees */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+    size_t interpolation;       /* I: 1 .. 64, gcd(I, D) = 1 */
+} gr4pm_ddc_rational_params;
+/* The Kaiser design of gr4pm_ddc_taps with L = taps_per_phase * decimation taps at the virtual rate I fs
+ * (the span of gr4pm_ddc_taps in output items) and DC gain I (every polyphase branch has gain about 1),
+ * scaled in double before the one rounding to float (host only).  passband / stopband: the band edges in
+ * units of the output rate fs I / D; refused when the cutoff, midway between them, exceeds half of the
+ * lower of the input and the output rate: passband + stopband <= min(1, D / I).  With I = 1 the floats
+ * are those of gr4pm_ddc_taps.  out: taps_per_phase * decimation floats. */
+gr4pm_status gr4pm_ddc_rational_taps(size_t interpolation, size_t decimation, size_t taps_per_phase, double passband,
+                                     double stopband, float* out);
+gr4pm_status gr4pm_ddc_create_rational(const gr4pm_ddc_rational_params* params, gr4pm_ddc** out);
+
 /* ====================================================================================
  * Duc -- tunable up-converter, the mirror of the Ddc: K complex64 rows at fs / I become ONE wideband
  * stream at fs (the project's own block).  Any integer interpolation I in [1, 1024], K in [1, 64] rows
