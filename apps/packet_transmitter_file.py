@@ -2,7 +2,7 @@
 """MI355X counterpart of the reference's apps/packet_transmitter_pdu.cpp:
 
     packet_transmitter_file.py output_file (--in packets.bin | --random COUNT SIZE) [--stream-mode] [--gap N]
-                               [--format {cf32,sc16,sc8,cu8}] [--gain G] [--tune CYCLES_PER_SAMPLE --interpolate I]
+                               [--format {cf32,sc16,sc8,cu8}] [--gain G] [--tune CYCLES_PER_SAMPLE --interpolate N[/M]]
 
 makes the IQ of PacketTransmitterPdu (packet_transmitter_pdu.hpp:40-355) on the GPU (gr4pm_packet_transmitter) at
 4 samples/symbol and writes it to `output_file` as raw little-endian complex64 (what packet_receiver_file.py reads).
@@ -20,7 +20,10 @@ clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is pr
 `--tune F --interpolate I`: the file is a wideband stream at I times the modem's rate with the carrier F cycles per file
 sample off centre: a one-channel `Duc` (gr4pm_duc: interpolate by I, mix by +F) sits behind the
 transmitter, and packet_receiver_file.py --tune F --decimate I receives the file.  Combines with `--format`; the
-prototype's P - 1 items of tail are flushed, so the last burst's ramp-down is whole."""
+prototype's P - 1 items of tail are flushed, so the last burst's ramp-down is whole.  `--interpolate N/M` (N >= M, for
+instance 25/4 for a 25 Msps file of a 1 Msym/s carrier): N / M file samples per transmitter sample, the same Duc
+resampling by N / M in the same pass (DESIGN section 19), so a file can be written at any rate above the modem's;
+packet_receiver_file.py --tune F --decimate N/M receives it."""
 import argparse
 import os
 import sys
@@ -45,11 +48,23 @@ def read_packets(path):
     return packets
 
 
+def interpolation(v):
+    """--interpolate: `N` or `N/M`, file samples per transmitter sample, as (N, M); an integer passes as (N, 1)"""
+    n, _, m = str(v).partition("/")
+    try:
+        n, m = int(n), int(m) if m else 1
+    except ValueError:
+        raise ValueError(f"--interpolate: {v!r} is neither N nor N/M") from None
+    if m < 1 or (m > 1 and n < m):
+        raise ValueError(f"--interpolate: {v!r}: need N >= M >= 1 (file samples per transmitter sample)")
+    return n, m  # a plain integer goes to the Duc as it is, which refuses what it cannot take
+
+
 def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, fmt="cf32", gain=None, stats=None,
              tune=None, interpolate=None):
     """writes the IQ of `packets` to out_path; returns the number of samples written.  stats: an optional dict that
     receives "clipped", the number of components an integer format clipped.  tune / interpolate: a Duc behind the
-    transmitter"""
+    transmitter; interpolate: an integer, "N/M" or (N, M)"""
     pkg = pkg or ge.load_package()
     clipped = None if fmt == "cf32" else torch.zeros(1, dtype=torch.int64, device="cuda")
     empty = [k for k, p in enumerate(packets) if len(p) == 0]
@@ -60,7 +75,8 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
                                max_payload_bytes=batch_bytes)
     duc = None
     if tune is not None or interpolate is not None:
-        duc = pkg.Duc([0.0 if tune is None else tune], 1 if interpolate is None else interpolate)
+        up, down = (1, 1) if interpolate is None else (interpolate if isinstance(interpolate, tuple) else interpolation(interpolate))
+        duc = pkg.Duc([0.0 if tune is None else tune], up, decimation=down)
     written = 0
 
     def emit(f, x):
@@ -102,10 +118,16 @@ def main():
     ap.add_argument("--format", choices=["cf32", "sc16", "sc8", "cu8"], default="cf32", help="the file's items (default: complex64)")
     ap.add_argument("--gain", type=float, help="of an integer format's components (default: 2^15 for sc16, else 2^7)")
     ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Duc behind)")
-    ap.add_argument("--interpolate", type=int, metavar="I", help="file samples per transmitter sample (a Duc behind)")
+    ap.add_argument("--interpolate", metavar="N[/M]", help="file samples per transmitter sample, an integer or a ratio N/M "
+                    "such as 25/4 (a Duc behind)")
     a = ap.parse_args()
     if a.stream_mode and a.gap:
         ap.error("--gap is a burst mode option")
+    if a.interpolate is not None:
+        try:
+            a.interpolate = interpolation(a.interpolate)
+        except ValueError as e:
+            ap.error(str(e))
     if a.random:
         count, size = a.random
         if not 1 <= size <= 65535:

@@ -216,6 +216,10 @@ class DucParams(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class DucRationalParams(C.Structure):
+    _fields_ = DucParams._fields_ + [("decimation", C.c_size_t)]
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -286,6 +290,7 @@ EXPORTS = [
     "gr4pm_ddc_rational_taps", "gr4pm_ddc_create_rational",
     "gr4pm_duc_taps", "gr4pm_duc_create", "gr4pm_duc_destroy", "gr4pm_duc_reset", "gr4pm_duc_output_items",
     "gr4pm_duc_frequencies", "gr4pm_duc_process",
+    "gr4pm_duc_rational_taps", "gr4pm_duc_create_rational",
 ]
 
 _lib = None
@@ -503,6 +508,8 @@ def lib():
     L.gr4pm_duc_output_items.argtypes = [vp, sz, szp]
     L.gr4pm_duc_frequencies.argtypes = [vp, vp]
     L.gr4pm_duc_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
+    L.gr4pm_duc_rational_taps.argtypes = [sz, sz, sz, C.c_double, C.c_double, vp]
+    L.gr4pm_duc_create_rational.argtypes = [C.POINTER(DucRationalParams), C.POINTER(vp)]
     L.gr4pm_iq_unpack.argtypes = [vp, sz, C.c_int, C.c_float, sz, sz, vp, sz, vp]
     L.gr4pm_iq_pack.argtypes = [vp, sz, sz, sz, C.c_int, C.c_float, vp, sz, vp, vp]
     _lib = L

@@ -2013,6 +2013,20 @@ def duc_taps(interpolation, taps_per_phase=12, passband=0.25, stopband=0.75):
     return _design_taps("gr4pm_duc_taps", interpolation, taps_per_phase, passband, stopband, "duc_taps")
 
 
+def duc_rational_taps(interpolation, decimation, taps_per_phase=12, passband=0.25, stopband=0.75):
+    """gr4pm_duc_rational_taps: the prototype low-pass of a Duc that resamples by interpolation / decimation, at the
+    rate interpolation * the input rate: the Kaiser design of duc_taps with taps_per_phase * interpolation float32 taps
+    and DC gain `interpolation`, scaled in double before the one rounding to float32 (host only: works without a GPU).
+    passband / stopband: the band edges in units of the input rate; a cutoff beyond half of the lower of the input and
+    the output rate (passband + stopband > min(1, interpolation / decimation)) is refused.  With decimation = 1 the
+    floats are those of duc_taps."""
+    n = int(interpolation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_duc_rational_taps(int(interpolation), int(decimation), int(taps_per_phase), float(passband),
+                                        float(stopband), _np_ptr(out)), "duc_rational_taps")
+    return out[:n]
+
+
 class Duc:
     """gr4pm_duc: tunable up-converter, the mirror of Ddc.  len(frequencies) complex64 rows at fs / interpolation become
     one wideband stream at fs: row k is interpolated by any integer 1 .. 1024 through the prototype, scaled by gains[k]
@@ -2022,13 +2036,33 @@ class Duc:
     the first output sample (a row's phase follows from the absolute index in integer arithmetic, exactly, at any
     stream position), so Ddc(frequencies, interpolation, start_index=...) on the result returns the rows.
     process_bulk() takes any number of items per row; the filter history stays on the device.  Frequencies and gains
-    are fixed: make another Duc to retune.  The handle works on the stream that is current when it is made."""
+    are fixed: make another Duc to retune.  The handle works on the stream that is current when it is made.
 
-    def __init__(self, frequencies, interpolation, gains=None, taps=None, taps_per_phase=12, start_index=0,
+    decimation = D > 1 (at most 64) resamples by interpolation / D in the same pass (gr4pm_duc_create_rational): the
+    output rate is the rows' rate times interpolation / D (.rate, a Fraction), N items per row make ceil(N
+    interpolation / D) samples, and the prototype (None: duc_rational_taps(interpolation, D, taps_per_phase), which
+    exists for interpolation >= D only) runs at interpolation times the rows' rate.  Without taps the pair is reduced
+    to lowest terms (.interpolation and .decimation hold the reduced values); with taps a pair that is not in lowest
+    terms is refused, since the taps belong to one rate.  Ddc(frequencies, interpolation, interpolation=D,
+    start_index=...) on the result returns the rows."""
+
+    def __init__(self, frequencies, interpolation, decimation=1, gains=None, taps=None, taps_per_phase=12, start_index=0,
                  max_items=1 << 22):
-        self.interpolation = int(interpolation)
+        self.interpolation, self.decimation = int(interpolation), int(decimation)
+        if self.decimation > 1 and self.interpolation >= 1:
+            g = math.gcd(self.interpolation, self.decimation)
+            if g > 1 and taps is not None:
+                raise Gr4pmError(f"Duc: {self.interpolation} / {self.decimation} is not in lowest terms, and the taps "
+                                 f"belong to one rate: use {self.interpolation // g} / {self.decimation // g}")
+            if g > 1:
+                self.interpolation, self.decimation = self.interpolation // g, self.decimation // g
+        if self.decimation == 1:
+            design = duc_taps
+        else:
+            design = lambda i, per: duc_rational_taps(i, self.decimation, per)
         f, self.taps, self.start_index = _xlate_settings("Duc", frequencies, self.interpolation, taps, taps_per_phase,
-                                                         start_index, duc_taps)
+                                                         start_index, design)
+        self.rate = fractions.Fraction(self.interpolation, self.decimation) if self.decimation > 0 else None
         self.n_channels = int(f.size)
         a = None
         if gains is not None:
@@ -2039,17 +2073,25 @@ class Duc:
         self.max_items = int(max_items)
         stream = _stream_handle()
         self._stream = stream.value
-        p = _abi.DucParams(self.n_channels, self.interpolation, _np_ptr(f) if f.size else None,
-                           _np_ptr(a) if a is not None and a.size else None, _np_ptr(self.taps), self.taps.size,
-                           self.max_items, self.start_index, stream)
+        args = (self.n_channels, self.interpolation, _np_ptr(f) if f.size else None,
+                _np_ptr(a) if a is not None and a.size else None, _np_ptr(self.taps), self.taps.size, self.max_items,
+                self.start_index, stream)
         self._h = C.c_void_p()
-        check(lib().gr4pm_duc_create(C.byref(p), C.byref(self._h)), "Duc")
+        if self.decimation == 1:
+            p = _abi.DucParams(*args)
+            check(lib().gr4pm_duc_create(C.byref(p), C.byref(self._h)), "Duc")
+        else:
+            p = _abi.DucRationalParams(*args, self.decimation)
+            check(lib().gr4pm_duc_create_rational(C.byref(p), C.byref(self._h)), "Duc")
         q = np.zeros(self.n_channels, dtype=np.float64)
         check(lib().gr4pm_duc_frequencies(self._h, _np_ptr(q)), "Duc.frequencies")
         self.frequencies = q
 
     def output_items(self, n_in):
-        """samples the next process_bulk() of n_in items per row produces: n_in * interpolation"""
+        """samples the next process_bulk() of n_in items per row produces.  With decimation = 1 that is n_in *
+        interpolation; a handle that resamples by interpolation / decimation makes ceil(N interpolation / decimation)
+        samples from N items in all, so the count of one call depends on where the handle stands in its stream: ask
+        before each call (the state is unchanged by asking)"""
         n = C.c_size_t(0)
         check(lib().gr4pm_duc_output_items(self._h, int(n_in), C.byref(n)), "Duc.output_items")
         return n.value
@@ -2060,8 +2102,9 @@ class Duc:
 
     def process_bulk(self, v, out=None):
         """v: a CUDA complex64 tensor [n_channels, n] with contiguous rows and any row stride (a window of a wider
-        tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[n * interpolation]; out: an optional
-        contiguous CUDA complex64 tensor of at least that many samples to write into."""
+        tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[output_items(n)] (n * interpolation
+        samples with decimation = 1); out: an optional contiguous CUDA complex64 tensor of at least that many samples to
+        write into."""
         torch = _torch()
         if isinstance(v, torch.Tensor) and self.n_channels == 1 and (v.dim() == 1 or (v.dim() == 2 and v.shape[0] == 1)):
             v = _dev_c64(v.reshape(-1) if v.dim() == 2 else v, "v")  # one row: its stride means nothing

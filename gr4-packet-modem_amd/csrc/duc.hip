@@ -27,7 +27,27 @@
 // A result is a function of (absolute output index, the rows' streams) only: not of call or tile sizes.
 // The rows' tails -- the last P - 1 items of each -- are stream_tail.hpp's: its kernel moves them to the handle's other
 // history buffer.
+//
+// Rational resampling by I / D (gr4pm_duc_create_rational): output sample j of the handle has the
+// upsampled index u = j D, the newest item m = u div I and the polyphase branch r = u mod I.  j and m - p are no longer
+// an integer apart, so there is no rotator per input item: filter first, then mix.
+//     g_k[t] = fl(a_k h[t])                               (host: the product in double, rounded to float once; real)
+//     b_k[j] = sum_{p : p I + r < L} g_k[p I + r] v_k[m - p]   (from zero, p ascending, two fmaf per step)
+//     q_k(i) = A_k[i div B] (x) T_k[i mod B],  B = 2^10, i the ABSOLUTE output index:  A from double sincospi of the exact
+//              phase of the aligned block's first sample (device, once per channel and block, rounded to float),
+//              T_k[0 .. B) a host table of freq_xlate.hpp's phasors, the product four fmaf from zero
+//     x[i] = sum_k q_k(i) b_k[j]                          (one accumulator from zero, k ascending, cmac)
+// k_duc_rational: a workgroup owns I T consecutive samples: since gcd(I, D) = 1 exactly T of every branch.  The about
+//   T D + P items per row the tile spans go to LDS once, in ddc.hip's layout (item n at row n mod D, column n div D, odd
+//   row length), so that lanes D items apart read consecutive items of a row.  A wave takes 64 samples of one branch at
+//   a time: sample q + I l of the tile for lane l, where q < I names the branch ((b0 + q D) mod I); the branch's taps are
+//   wave-uniform, a table [k][branch][p] read through the constant address space (scalar loads).  Channels run in groups
+//   that fit the stage, one after the other; the accumulators rest in an LDS tile [q][l] with an odd row stride between
+//   groups, and the same tile transposes the stride-I results so that the block leaves as 16-byte stores.
+// A sample is a function of (absolute output index, the rows' streams) only.  The position is
+// hostlogic/duc_position.hpp's: 64-bit integers on the host, by value to the kernel.
 #include "freq_xlate.hpp"
+#include "hostlogic/duc_position.hpp"
 #include "kaiser_design.hpp"
 #include "stream_tail.hpp"
 
@@ -172,6 +192,167 @@ void launch_r(dim3 grid, size_t smem, hipStream_t s, const DucArgs& a, const flo
     hipLaunchKernelGGL(k_duc<R>, grid, dim3(kNt), smem, s, a, g);
 }
 
+constexpr size_t kMaxD = 64;
+constexpr unsigned kRotBlock = 1024;       // B: the rotator's aligned block of absolute output indices
+constexpr unsigned kRotSpan = 3;           // aligned blocks that a tile of at most 2048 samples touches
+constexpr size_t kLdsItems = 6144;         // complex64 items of LDS a rational tile aims at: 48 KiB ...
+constexpr size_t kLdsItemsMost = 10240;    // ... and what it may take where one sample per branch needs more: 80 KiB
+
+struct RducArgs {
+    const float2* hist;  // [K][P - 1]: the items in front of in[k][0]
+    const float2* in;    // row k at in + k in_stride
+    float2* out;
+    const uint32_t* w;   // [K] frequency words
+    size_t in_stride;
+    size_t total;        // P - 1 + n_in: items of a row's virtual stream hist ++ in
+    size_t n_out;
+    uint64_t u0;         // the call's first sample: its upsampled index, counted from that of in[k][0]
+    uint32_t pos;        // absolute index of the call's first sample: the low 32 bits are all the phase needs
+    unsigned K, I, D, L, P;
+    unsigned T, TS;      // samples per branch of a tile; items of a tile row (odd)
+    unsigned chunks;     // ceil(T / 64): a wave takes 64 samples of a branch at a time
+    unsigned S, RS;      // items of a row that a tile spans; items of a stage row (odd)
+    unsigned G;          // channels of a group
+    unsigned rcpI, rcpD; // ceil(2^32 / n) for n >= 2: j div n = umulhi(j, rcp) for j < 2^22
+};
+
+typedef const float __attribute__((address_space(4))) * ConstTaps;
+
+// taps: [K][I][P] real taps g_k[p I + r] at [k][r][p], zero where p I + r >= L.  rot: [K][kRotBlock] phasors T_k.
+// Both are written at create only and are parameters of their own.
+__global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* __restrict__ taps, const float2* __restrict__ rot)
+{
+    extern __shared__ float2 s_rduc[];
+    const unsigned tid = threadIdx.x, lane = tid & 63;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned I = a.I, D = a.D, L = a.L, P = a.P, T = a.T, TS = a.TS, RS = a.RS;
+    const unsigned IT = I * T, row_items = D * RS;
+    float2* tile = s_rduc;                     // [I][TS]
+    float2* blk = s_rduc + I * TS;             // [G][kRotSpan]: A_k of the aligned blocks the tile touches
+    float2* stage = blk + a.G * kRotSpan;      // [G][D][RS]
+    const size_t n0 = static_cast<size_t>(blockIdx.x) * IT; // the tile's first sample
+    const unsigned n = static_cast<unsigned>(a.n_out - n0 < IT ? a.n_out - n0 : IT);
+    const uint64_t u0 = a.u0 + static_cast<uint64_t>(n0) * D;
+    const uint64_t c0 = u0 / I;                              // its newest item, counted from in[k][0] ...
+    const unsigned b0 = static_cast<unsigned>(u0 - c0 * I); // ... and its branch
+    const uint32_t i0 = a.pos + static_cast<uint32_t>(n0);
+    const unsigned o0 = i0 & (kRotBlock - 1);
+    const unsigned n_blk = (o0 + n - 1) / kRotBlock + 1;     // at most kRotSpan: I T <= 2048
+    const unsigned n_units = I * a.chunks;
+    auto div_I = [&](unsigned j) { return I == 1 ? j : __umulhi(j, a.rcpI); };
+    auto div_D = [&](unsigned j) { return D == 1 ? j : __umulhi(j, a.rcpD); };
+
+    bool first = true;
+    for (unsigned k0 = 0; k0 < a.K; k0 += a.G) {
+        const unsigned gc = a.K - k0 < a.G ? a.K - k0 : a.G;
+        if (!first) __syncthreads(); // the previous group's stage has been read
+        // stage item s of a row: item c0 + s of its virtual stream, that is item c0 - (P - 1) + s of this call; the
+        // tile's last sample takes its tap 0 from item (b0 + (I T - 1) D) div I + P - 1 < S
+        for (unsigned kk = 0; kk < gc; ++kk) {
+            const float2* hist = a.hist + static_cast<size_t>(k0 + kk) * (P - 1);
+            const float2* in = a.in + static_cast<size_t>(k0 + kk) * a.in_stride;
+            float2* sk = stage + kk * row_items;
+            for (unsigned s = tid; s < a.S; s += kNt) {
+                const unsigned col = div_D(s), row = s - col * D;
+                const size_t v = static_cast<size_t>(c0) + s;
+                float2 x = {0.0f, 0.0f};
+                if (v < a.total) x = v < P - 1 ? hist[v] : in[v - (P - 1)];
+                sk[row * RS + col] = x;
+            }
+        }
+        if (tid < gc * n_blk) {
+            const unsigned kk = tid / n_blk, bb = tid - kk * n_blk;
+            const uint32_t phi = a.w[k0 + kk] * (i0 - o0 + bb * kRotBlock);
+            double sn, cs;
+            sincospi(static_cast<double>(phi) * (1.0 / 2147483648.0), &sn, &cs); // the argument is exact
+            blk[kk * kRotSpan + bb] = float2{static_cast<float>(cs), static_cast<float>(sn)};
+        }
+        __syncthreads();
+        for (unsigned u = wave; u < n_units; u += kNt / 64) {
+            // 64 samples of the branch named q: sample q + I l of the tile for l = 64 chunk + lane
+            const unsigned chunk = div_I(u), q = u - chunk * I;
+            const unsigned ub = b0 + q * D;
+            const unsigned e = div_I(ub), r = ub - e * I;   // the first one's newest item, counted from c0; the branch
+            const unsigned n_taps = r < L ? div_I(L - r + I - 1) : 0; // taps of h[r::I]
+            const unsigned l = chunk * 64 + lane, t = q + I * l;
+            if (l < T && t < n) {
+                float2 acc = first ? float2{0.0f, 0.0f} : tile[q * TS + l];
+                const unsigned ti = o0 + t;
+                for (unsigned kk = 0; kk < gc; ++kk) {
+                    const ConstTaps g = (ConstTaps)(taps + (static_cast<size_t>(k0 + kk) * I + r) * P);
+                    const float2* sk = stage + kk * row_items;
+                    float2 b = {0.0f, 0.0f};
+                    // tap p takes stage item e + P - 1 - p + l D: row (e + P - 1 - p) mod D, lanes on consecutive columns
+                    unsigned col = div_D(e + P - 1), row = (e + P - 1) - col * D, left = n_taps, p = 0;
+                    while (left) {
+                        const unsigned run = row + 1 < left ? row + 1 : left;
+                        const float2* sp = sk + row * RS + col + l;
+#pragma unroll 4
+                        for (unsigned i = 0; i < run; ++i, sp -= RS, ++p) {
+                            const float2 x = *sp;
+                            const float gp = g[p];
+                            b.x = fmaf(gp, x.x, b.x);
+                            b.y = fmaf(gp, x.y, b.y);
+                        }
+                        left -= run;
+                        --col;
+                        row = D - 1;
+                    }
+                    float2 qk = {0.0f, 0.0f};
+                    cmac(qk, blk[kk * kRotSpan + ti / kRotBlock], rot[static_cast<size_t>(k0 + kk) * kRotBlock + (ti & (kRotBlock - 1))]);
+                    cmac(acc, qk, b);
+                }
+                tile[q * TS + l] = acc;
+            }
+        }
+        first = false;
+    }
+    __syncthreads();
+
+    // sample t of the tile is at tile[t mod I][t div I]; one sample alone where out + n0 is only 8-byte aligned
+    float2* __restrict__ out = a.out + n0;
+    auto sample = [&](unsigned t) {
+        const unsigned l = div_I(t);
+        return tile[(t - l * I) * TS + l];
+    };
+    const unsigned head = static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) >> 3) & 1u;
+    if (tid == 0 && head && n) out[0] = sample(0);
+    for (unsigned t = head + 2 * tid; t < n; t += 2 * kNt) {
+        if (t + 1 < n) {
+            const float2 lo = sample(t), hi = sample(t + 1);
+            *reinterpret_cast<float4*>(out + t) = float4{lo.x, lo.y, hi.x, hi.y};
+        } else {
+            out[t] = sample(t);
+        }
+    }
+}
+
+gr4pm_status design_rational_taps(size_t I, size_t D, size_t P, double passband, double stopband, std::vector<double>& h)
+{
+    using gr4pm::set_error;
+    if (I < 1 || I > kMaxI) {
+        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
+        return GR4PM_ERR_INVALID;
+    }
+    if (D < 1 || D > kMaxD) {
+        set_error("duc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
+        return GR4PM_ERR_INVALID;
+    }
+    if (P < 1 || P * I > kMaxL) {
+        set_error("duc: %zu taps per phase at an interpolation of %zu: the prototype has 1 .. %zu taps", P, I, kMaxL);
+        return GR4PM_ERR_INVALID;
+    }
+    // the cutoff, (passband + stopband) / 2 of the input rate, within half of the input rate and half of the output rate
+    const double most = I < D ? static_cast<double>(I) / static_cast<double>(D) : 1.0;
+    if (!(passband >= 0.0 && passband < stopband && passband + stopband <= most)) {
+        set_error("duc: need 0 <= passband < stopband (units of the input rate, the output's is %zu / %zu of it) and a cutoff "
+                  "of at most half of the lower of the input and the output rate: passband + stopband <= %g", I, D, most);
+        return GR4PM_ERR_INVALID;
+    }
+    gr4pm::kaiser_lowpass(P * I, I, passband, stopband, h, static_cast<double>(I));
+    return GR4PM_OK;
+}
+
 gr4pm_status design_taps(size_t I, size_t P, double passband, double stopband, std::vector<double>& h)
 {
     using gr4pm::set_error;
@@ -204,9 +385,69 @@ struct gr4pm_duc {
     std::vector<uint32_t> words;
     gr4pm::DevBuf<float2> d_g;
     gr4pm::DevBuf<uint32_t> d_w;
+    // a rational handle (D > 1; the tail still keeps P - 1 items of every row)
+    size_t D = 1;
+    unsigned chunks = 0, S = 0, RS = 0, rcpD = 0;
+    gr4pm::hostlogic::DucPosition at; // items taken, the next sample's newest item and branch
+    gr4pm::DevBuf<float> d_taps;      // [K][I][P]
+    gr4pm::DevBuf<float2> d_rot;      // [K][kRotBlock]
 };
 
 using namespace gr4pm;
+
+static gr4pm_status process_rational(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
+                                     size_t out_cap, size_t* n_out)
+{
+    if (n_in > h->max_items) {
+        set_error("duc: %zu items per row, the handle was made for %zu", n_in, h->max_items);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (n_in == 0) return GR4PM_OK;
+    const uint64_t F = h->at.samples(n_in);
+    const uint64_t tile = static_cast<uint64_t>(h->I) * h->T, blocks = (F + tile - 1) / tile;
+    if (F > out_cap || blocks > 0x7FFFFFFFu) {
+        set_error("duc: %llu samples, room for %zu", static_cast<unsigned long long>(F), out_cap);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (!in || (F && !out) || (h->K > 1 && in_stride < n_in)) {
+        set_error("duc: no input or output array, or a row stride of %zu items for %zu items", in_stride, n_in);
+        return GR4PM_ERR_INVALID;
+    }
+    const StreamTail::Plan t = h->tail.plan(n_in);
+    RducArgs a;
+    a.hist = t.hist;
+    a.in = reinterpret_cast<const float2*>(in);
+    a.out = reinterpret_cast<float2*>(out);
+    a.w = h->d_w.p;
+    a.in_stride = in_stride;
+    a.total = t.H + n_in;
+    a.n_out = static_cast<size_t>(F);
+    a.u0 = h->at.first();
+    a.pos = static_cast<uint32_t>(h->pos);
+    a.K = static_cast<unsigned>(h->K);
+    a.I = static_cast<unsigned>(h->I);
+    a.D = static_cast<unsigned>(h->D);
+    a.L = static_cast<unsigned>(h->L);
+    a.P = static_cast<unsigned>(h->P);
+    a.T = h->T;
+    a.TS = h->TS;
+    a.chunks = h->chunks;
+    a.S = h->S;
+    a.RS = h->RS;
+    a.G = h->G;
+    a.rcpI = h->rcpI;
+    a.rcpD = h->rcpD;
+    if (F)
+        hipLaunchKernelGGL(k_duc_rational, dim3(static_cast<unsigned>(blocks)), dim3(kNt), h->smem, h->stream, a, h->d_taps.p,
+                           h->d_rot.p);
+    h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
+    GR4PM_HIP_TRY(hipGetLastError());
+    h->tail.commit(t);
+    h->at.advance(n_in, F);
+    h->pos += F;
+    *n_out = static_cast<size_t>(F);
+    return GR4PM_OK;
+}
 
 extern "C" {
 
@@ -298,6 +539,129 @@ try {
 }
 GR4PM_ABI_CATCH
 
+gr4pm_status gr4pm_duc_rational_taps(size_t interpolation, size_t decimation, size_t taps_per_phase, double passband,
+                                     double stopband, float* out)
+try {
+    if (!out) return GR4PM_ERR_INVALID;
+    std::vector<double> h;
+    GR4PM_TRY(design_rational_taps(interpolation, decimation, taps_per_phase, passband, stopband, h));
+    round_taps(h, out);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_duc_create_rational(const gr4pm_duc_rational_params* p, gr4pm_duc** out)
+try {
+    if (!p || !out) return GR4PM_ERR_INVALID;
+    *out = nullptr;
+    const size_t K = p->n_channels, I = p->interpolation, D = p->decimation;
+    if (D < 1 || D > kMaxD) {
+        set_error("duc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
+        return GR4PM_ERR_INVALID;
+    }
+    if (D == 1) { // the integer Duc, with its own kernel
+        const gr4pm_duc_params q = {K, I, p->frequencies, p->gains, p->taps, p->n_taps, p->max_items, p->start_index, p->stream};
+        return gr4pm_duc_create(&q, out);
+    }
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("duc", p->frequencies, K, kMaxK, words));
+    if (I < 1 || I > kMaxI) {
+        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
+        return GR4PM_ERR_INVALID;
+    }
+    size_t gcd = I;
+    for (size_t b = D % I; b;) {
+        const size_t r = gcd % b;
+        gcd = b, b = r;
+    }
+    if (gcd != 1) {
+        set_error("duc: the ratio %zu / %zu is not in lowest terms: use %zu / %zu", I, D, I / gcd, D / gcd);
+        return GR4PM_ERR_INVALID;
+    }
+    for (size_t k = 0; p->gains && k < K; ++k)
+        if (!std::isfinite(p->gains[k])) {
+            set_error("duc: gains[%zu] is not finite", k);
+            return GR4PM_ERR_INVALID;
+        }
+    if (p->max_items == 0 || p->max_items > (size_t(1) << 31)) {
+        set_error("duc: max_items must be in [1, 2^31]");
+        return GR4PM_ERR_INVALID;
+    }
+    if (p->taps && (p->n_taps < 1 || p->n_taps > kMaxL)) {
+        set_error("duc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
+        return GR4PM_ERR_INVALID;
+    }
+    std::vector<float> taps;
+    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) { return design_rational_taps(I, D, 12, 0.25, 0.75, hd); },
+                             taps));
+    const size_t L = taps.size(), P = (L + I - 1) / I;
+    GR4PM_TRY(require_device());
+    std::unique_ptr<gr4pm_duc> h(new (std::nothrow) gr4pm_duc);
+    if (!h) return GR4PM_ERR_NOMEM;
+    h->K = K;
+    h->I = I;
+    h->D = D;
+    h->L = L;
+    h->P = P;
+    h->max_items = p->max_items;
+    h->start_index = h->pos = p->start_index;
+    h->stream = static_cast<hipStream_t>(p->stream);
+    h->at.I = I;
+    h->at.D = D;
+    // the tile: T samples per branch, about kTileItems in all and whole waves of a branch where that gives 64 or more;
+    // the stage: D rows of an odd number of items for the ((I T - 1) D + I - 1) div I + P items that I T consecutive
+    // samples reach.  The largest T whose tile and one channel's stage fit kLdsItems, or T = 1 in kLdsItemsMost; then as
+    // many channels to a group as fit.  The taps are never chunked.
+    size_t T = kTileItems / I;
+    T = T >= 64 ? (T > static_cast<size_t>(kNt) ? static_cast<size_t>(kNt) : T / 64 * 64) : (T < 1 ? 1 : T);
+    size_t S = 0, RS = 0, budget = kLdsItems;
+    for (;;) {
+        S = ((I * T - 1) * D + I - 1) / I + P;
+        RS = ((S + D - 1) / D) | 1;
+        if (I * (T | 1) + kRotSpan + D * RS <= budget) break;
+        if (T == 1) {
+            if (budget == kLdsItemsMost) {
+                set_error("duc: no tile of %zu / %zu with %zu taps fits the stage", I, D, L);
+                return GR4PM_ERR_INVALID;
+            }
+            budget = kLdsItemsMost;
+        } else {
+            T -= T > 64 ? 64 : 1;
+        }
+    }
+    size_t G = (budget - I * (T | 1)) / (D * RS + kRotSpan);
+    if (G > K) G = K;
+    h->T = static_cast<unsigned>(T);
+    h->TS = static_cast<unsigned>(T | 1);
+    h->chunks = static_cast<unsigned>((T + 63) / 64);
+    h->S = static_cast<unsigned>(S);
+    h->RS = static_cast<unsigned>(RS);
+    h->G = static_cast<unsigned>(G);
+    h->rcpI = reciprocal_word(I);
+    h->rcpD = reciprocal_word(D);
+    h->smem = (I * h->TS + G * (D * RS + kRotSpan)) * sizeof(float2);
+
+    h->words = std::move(words);
+    std::vector<float> g(K * I * P, 0.0f);
+    std::vector<float2> rot(K * kRotBlock);
+    for (size_t k = 0; k < K; ++k) {
+        const double a = p->gains ? p->gains[k] : 1.0;
+        for (size_t t = 0; t < L; ++t) g[(k * I + t % I) * P + t / I] = static_cast<float>(a * static_cast<double>(taps[t]));
+        for (size_t t = 0; t < kRotBlock; ++t) rot[k * kRotBlock + t] = rotated_tap(1.0, h->words[k] * static_cast<uint32_t>(t));
+    }
+    GR4PM_TRY(h->d_taps.alloc(g.size()));
+    GR4PM_TRY(h->d_rot.alloc(rot.size()));
+    GR4PM_TRY(h->d_w.alloc(K));
+    GR4PM_TRY(h->tail.alloc(P - 1, 1, K, h->stream));
+    GR4PM_TRY(h->d_taps.upload(g.data(), g.size(), h->stream));
+    GR4PM_TRY(h->d_rot.upload(rot.data(), rot.size(), h->stream));
+    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
+    if (h->smem > 48 * 1024)
+        GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_duc_rational)}, kLdsItemsMost * sizeof(float2), "duc"));
+    return finish_create(h, out, "duc");
+}
+GR4PM_ABI_CATCH
+
 void gr4pm_duc_destroy(gr4pm_duc* h)
 try {
     if (!h) return;
@@ -311,6 +675,7 @@ try {
     if (!h) return GR4PM_ERR_INVALID;
     GR4PM_TRY(h->tail.reset(h->stream));
     h->pos = h->start_index;
+    h->at.reset();
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -318,7 +683,7 @@ GR4PM_ABI_CATCH
 gr4pm_status gr4pm_duc_output_items(const gr4pm_duc* h, size_t n_in, size_t* n_out)
 try {
     if (!h || !n_out) return GR4PM_ERR_INVALID;
-    *n_out = n_in * h->I;
+    *n_out = h->D > 1 ? static_cast<size_t>(h->at.samples(n_in)) : n_in * h->I;
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -336,6 +701,7 @@ gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stri
 try {
     if (!h || !n_out) return GR4PM_ERR_INVALID;
     *n_out = 0;
+    if (h->D > 1) return process_rational(h, in, in_stride, n_in, out, out_cap, n_out);
     if (n_in > h->max_items) {
         set_error("duc: %zu items per row, the handle was made for %zu", n_in, h->max_items);
         return GR4PM_ERR_OVERFLOW;

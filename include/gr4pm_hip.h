@@ -1185,6 +1185,69 @@ gr4pm_status gr4pm_duc_frequencies(const gr4pm_duc* h, double* out);
 gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
                                size_t out_cap, size_t* n_out);
 
+/* ------------------------------------------------------------------------------------
+ * Duc, rational resampling by I / D (output rate fs_in I / D) in the same pass: a gr4pm_duc handle made by
+ * gr4pm_duc_create_rational, the mirror of gr4pm_ddc_create_rational.  I in
+ * [1, 1024], D in [1, 64], gcd(I, D) = 1 (a pair that is not in lowest terms is refused with
+ * GR4PM_ERR_INVALID, the message names the reduced pair).  The real prototype h[0 .. L - 1], 1 <= L <= 8192,
+ * runs at the virtual rate I fs_in; P = ceil(L / I) and h[t] = 0 for t >= L.  w_k, phi_k, the gains a_k and
+ * v_k[m] = 0 before the handle's first item are the Duc's above.  Output sample j, counted from the
+ * handle's start:
+ *     i   = start_index + j      its absolute index (uint64)
+ *     u_j = j D                  its index in the rows zero-stuffed by I
+ *     m_j = u_j div I            its newest item
+ *     r_j = u_j mod I            its polyphase branch
+ *     x[i] = sum_k a_k exp(+2 pi j phi_k(i) / 2^32) sum_{p : p I + r_j < L} h[p I + r_j] v_k[m_j - p]
+ * (zero-stuff every row by I, filter with h at the rate I fs_in, keep every D-th, mix, sum).  With D = 1
+ * this is the Duc sample for sample.  j and m_j - p are not an integer apart, so there is no rotator per
+ * input item: filter first, then mix.  Evaluated as
+ *     g_k[t] = fl(a_k h[t])                                   the product in double, rounded to float once
+ *     b_k[j] = sum_{p : p I + r_j < L} g_k[p I + r_j] v_k[m_j - p]
+ *                                                             from zero, p ascending, per step
+ *                                                             re = fmaf(g, vr, re); im = fmaf(g, vi, im)
+ *     q_k(i) = A_k[i div B] (x) T_k[i mod B],  B = 1024       A_k[n]: double sincospi of phi_k(n B) / 2^31 (exact
+ *                                                             argument) on the device, rounded to float;
+ *                                                             T_k[t] = exp(+2 pi j phi_k(t) / 2^32) made at create
+ *                                                             on the host in double with the Ddc's quadrant
+ *                                                             reduction, rounded to float; (x): the four fmaf of
+ *                                                             the Ddc's multiply-accumulate from zero, A first
+ *     x[i] = sum_k q_k(i) b_k[j]                              one accumulator from zero, k ascending, the same
+ *                                                             four fmaf with q_k first
+ * The rotator is aligned to the ABSOLUTE index, so a sample is a function of (absolute output index, the
+ * rows' streams) only: not of the call cuts or the grid.
+ * Stream contract: all input of a call is consumed; sample j exists once item m_j has arrived, so after N
+ * items per row in all ceil(N I / D) samples exist, and a call writes the difference of that count across
+ * the call: none is possible when I < D, several per item when I > D.  The handle keeps P - 1 items of
+ * every row on the device; the position (items taken, the next sample's m and r) lives on the host in
+ * 64-bit integers, advanced by (r + F D) divmod I after a call of F samples, and reaches the kernel by
+ * value; process() reads nothing back.  max_items bounds n_in; out_cap must hold the call's samples.
+ * gr4pm_duc_process / _reset / _output_items / _frequencies / _destroy take such a handle with the
+ * contracts documented above; *n_out and output_items are the sample count of this section, which
+ * depends on the handle's position.  decimation = 1 makes the handle gr4pm_duc_create makes, with its
+ * results bit for bit.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t interpolation;       /* I: 1 .. 1024 */
+    const double* frequencies;  /* host: K frequencies in cycles per output sample, any finite value */
+    const double* gains;        /* host: K finite real gains a_k (NULL: all 1) */
+    const float* taps;          /* host: n_taps prototype taps at the rate I fs_in, copied at create (NULL: the default
+                                   design, gr4pm_duc_rational_taps(I, D, 12, 0.25, 0.75), which exists for I >= D) */
+    size_t n_taps;              /* L: 1 .. 8192 (ignored when taps is NULL) */
+    size_t max_items;           /* per process() call: n_in <= max_items; 1..2^31 */
+    uint64_t start_index;       /* absolute index of the first output sample */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+    size_t decimation;          /* D: 1 .. 64, gcd(I, D) = 1 */
+} gr4pm_duc_rational_params;
+/* The Kaiser design of gr4pm_duc_taps with L = taps_per_phase * interpolation taps and DC gain I, scaled
+ * in double before the one rounding to float (host only).  passband / stopband: the band edges in units
+ * of the input rate; refused when the cutoff, midway between them, exceeds half of the lower of the input
+ * and the output rate: passband + stopband <= min(1, I / D).  With D = 1 the floats are those of
+ * gr4pm_duc_taps.  out: taps_per_phase * interpolation floats. */
+gr4pm_status gr4pm_duc_rational_taps(size_t interpolation, size_t decimation, size_t taps_per_phase, double passband,
+                                     double stopband, float* out);
+gr4pm_status gr4pm_duc_create_rational(const gr4pm_duc_rational_params* params, gr4pm_duc** out);
+
 /* ====================================================================================
  * Integer IQ formats (the project's own block: the reference moves complex64 only).  An item is one
  * complex sample, I then Q, little-endian integers.

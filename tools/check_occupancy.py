@@ -118,6 +118,9 @@ BUDGETS = [
     (r"k_ddc_rationalILi", dict(vgpr=72, scratch=0)),
     # the up-converter: eight phase accumulators per lane, taps in SGPRs, eight waves per SIMD
     (r"k_ducILi", dict(vgpr=64, scratch=0)),
+    # its rational form: one real-tap accumulator per lane, the branch's taps in SGPRs, eight waves per SIMD (DESIGN
+    # section 19)
+    (r"k_duc_rational", dict(vgpr=64, scratch=0)),
 ]
 
 
