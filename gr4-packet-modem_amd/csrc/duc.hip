@@ -26,7 +26,8 @@
 //   phases) both hit distinct banks, and the tile leaves as 16-byte stores contiguous across the workgroup.
 // A result is a function of (absolute output index, the rows' streams) only: not of call or tile sizes.
 // The rows' tails -- the last P - 1 items of each -- are stream_tail.hpp's: its kernel moves them to the handle's other
-// history buffer.
+// history buffer.  The tile's sizes are hostlogic/xlate_geometry.hpp's duc_geometry(): the handle keeps them in a
+// prefilled DucArgs, and a call writes only what changes from call to call.
 //
 // Rational resampling by I / D (gr4pm_duc_create_rational): output sample j of the handle has the
 // upsampled index u = j D, the newest item m = u div I and the polyphase branch r = u mod I.  j and m - p are no longer
@@ -44,10 +45,11 @@
 //   wave-uniform, a table [k][branch][p] read through the constant address space (scalar loads).  Channels run in groups
 //   that fit the stage, one after the other; the accumulators rest in an LDS tile [q][l] with an odd row stride between
 //   groups, and the same tile transposes the stride-I results so that the block leaves as 16-byte stores.
-// A sample is a function of (absolute output index, the rows' streams) only.  The position is
-// hostlogic/duc_position.hpp's: 64-bit integers on the host, by value to the kernel.
+// A sample is a function of (absolute output index, the rows' streams) only.  The tile is rduc_geometry()'s, the
+// position hostlogic/resample_position.hpp's with lead = 0: 64-bit integers on the host, by value to the kernel.
+// Both creates are one create(): gr4pm_duc_create's is the ratio I / 1.
 #include "freq_xlate.hpp"
-#include "hostlogic/duc_position.hpp"
+#include "hostlogic/resample_position.hpp"
 #include "kaiser_design.hpp"
 #include "stream_tail.hpp"
 
@@ -55,12 +57,11 @@
 
 namespace {
 
+using namespace gr4pm::hostlogic;
 using gr4pm::cmac;
+using gr4pm::ConstTaps;
 
-constexpr int kNt = 256;             // threads of a workgroup, and the most frames of a tile
-constexpr size_t kTileItems = 2048;  // output samples of a tile, about
-constexpr size_t kStageItems = 2048; // complex64 items of the stage: 16 KiB
-constexpr size_t kMaxK = 64, kMaxI = 1024, kMaxL = 8192;
+constexpr size_t kMaxK = 64, kMaxI = 1024, kMaxD = 64, kMaxL = 8192;
 
 struct DucArgs {
     const float2* hist;  // [K][P - 1]: the items in front of in[k][0]
@@ -70,13 +71,7 @@ struct DucArgs {
     size_t in_stride, n_in, n_out;
     uint32_t pos;        // absolute index of this call's first output sample: the low 32 bits are all the phase needs
     unsigned K, I, L, P;
-    unsigned IP;         // phases of the table and rows of the tile: I rounded up to a multiple of R
-    unsigned T, TS;      // frames of a tile; items of a tile row (odd)
-    unsigned WF;         // waves that share the tile's frames: 1, 2 or 4
-    unsigned G;          // channels of a group
-    unsigned Pc;         // taps per phase of a chunk (P unless G == 1)
-    unsigned ZS;         // items of a stage row: T + Pc - 1
-    unsigned rcpI;       // ceil(2^32 / I) for I >= 2: j div I = umulhi(j, rcpI) for j < 2^13
+    DucTile tile;
     unsigned vec;        // out is 16-byte aligned: the tile leaves two samples per store
 };
 
@@ -90,19 +85,19 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
 {
     extern __shared__ float2 s_duc[];
     const unsigned tid = threadIdx.x;
-    const unsigned I = a.I, L = a.L, P = a.P, IP = a.IP, T = a.T, TS = a.TS, ZS = a.ZS;
+    const unsigned I = a.I, L = a.L, P = a.P, IP = a.tile.IP, T = a.tile.T, TS = a.tile.TS, ZS = a.tile.ZS;
     float2* tile = s_duc;             // [IP][TS]
     float2* stage = s_duc + IP * TS;  // [G][ZS]
     const size_t m0 = static_cast<size_t>(blockIdx.x) * T;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned mi = (wave % a.WF) * 64 + (tid & 63); // this lane's frame of the tile
-    const unsigned rb0 = wave / a.WF, rb_step = 4 / a.WF, n_rb = IP / R;
+    const unsigned mi = (wave % a.tile.WF) * 64 + (tid & 63); // this lane's frame of the tile
+    const unsigned rb0 = wave / a.tile.WF, rb_step = 4 / a.tile.WF, n_rb = IP / R;
 
     bool first = true;
-    for (unsigned k0 = 0; k0 < a.K; k0 += a.G) {
-        const unsigned gc = a.K - k0 < a.G ? a.K - k0 : a.G;
-        for (unsigned p0 = 0; p0 < P; p0 += a.Pc) {
-            const unsigned pc = P - p0 < a.Pc ? P - p0 : a.Pc;
+    for (unsigned k0 = 0; k0 < a.K; k0 += a.tile.G) {
+        const unsigned gc = a.K - k0 < a.tile.G ? a.K - k0 : a.tile.G;
+        for (unsigned p0 = 0; p0 < P; p0 += a.tile.Pc) {
+            const unsigned pc = P - p0 < a.tile.Pc ? P - p0 : a.tile.Pc;
             const unsigned S = T + pc - 1;
             // stage item s of a row: frame fb + s of this call (negative: the handle's history); frame m0 + n takes
             // tap phase p from item n + (p0 + pc - 1 - p)
@@ -118,11 +113,8 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
                         v = a.hist[static_cast<size_t>(k) * (P - 1) + static_cast<size_t>(fr + (P - 1))];
                     else if (static_cast<size_t>(fr) < a.n_in)
                         v = a.in[static_cast<size_t>(k) * a.in_stride + static_cast<size_t>(fr)];
-                    const uint32_t phi = wk * (a.pos + static_cast<uint32_t>(fr) * I);
-                    double sn, cs;
-                    sincospi(static_cast<double>(phi) * (1.0 / 2147483648.0), &sn, &cs); // the argument is exact
                     float2 z = {0.0f, 0.0f};
-                    cmac(z, float2{static_cast<float>(cs), static_cast<float>(sn)}, v);
+                    cmac(z, gr4pm::mixer<1>(wk, a.pos + static_cast<uint32_t>(fr) * I), v);
                     stage[kk * ZS + s] = z;
                 }
             }
@@ -169,34 +161,15 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
     const unsigned n = static_cast<unsigned>(a.n_out - j0 < static_cast<size_t>(T) * I ? a.n_out - j0 : static_cast<size_t>(T) * I);
     float2* __restrict__ out = a.out + j0;
     auto sample = [&](unsigned j) {
-        const unsigned m = I == 1 ? j : __umulhi(j, a.rcpI);
+        const unsigned m = I == 1 ? j : __umulhi(j, a.tile.rcpI);
         return tile[(j - m * I) * TS + m];
     };
     if (a.vec) { // j0 is even (T I is), so out + j0 keeps the alignment of out
-        for (unsigned j = 2 * tid; j < n; j += 2 * kNt) {
-            if (j + 1 < n) {
-                const float2 lo = sample(j), hi = sample(j + 1);
-                *reinterpret_cast<float4*>(out + j) = float4{lo.x, lo.y, hi.x, hi.y};
-            } else {
-                out[j] = sample(j);
-            }
-        }
+        gr4pm::store_tile(out, n, 0, sample);
     } else {
         for (unsigned j = tid; j < n; j += kNt) out[j] = sample(j);
     }
 }
-
-template <int R>
-void launch_r(dim3 grid, size_t smem, hipStream_t s, const DucArgs& a, const float2* g)
-{
-    hipLaunchKernelGGL(k_duc<R>, grid, dim3(kNt), smem, s, a, g);
-}
-
-constexpr size_t kMaxD = 64;
-constexpr unsigned kRotBlock = 1024;       // B: the rotator's aligned block of absolute output indices
-constexpr unsigned kRotSpan = 3;           // aligned blocks that a tile of at most 2048 samples touches
-constexpr size_t kLdsItems = 6144;         // complex64 items of LDS a rational tile aims at: 48 KiB ...
-constexpr size_t kLdsItemsMost = 10240;    // ... and what it may take where one sample per branch needs more: 80 KiB
 
 struct RducArgs {
     const float2* hist;  // [K][P - 1]: the items in front of in[k][0]
@@ -209,14 +182,8 @@ struct RducArgs {
     uint64_t u0;         // the call's first sample: its upsampled index, counted from that of in[k][0]
     uint32_t pos;        // absolute index of the call's first sample: the low 32 bits are all the phase needs
     unsigned K, I, D, L, P;
-    unsigned T, TS;      // samples per branch of a tile; items of a tile row (odd)
-    unsigned chunks;     // ceil(T / 64): a wave takes 64 samples of a branch at a time
-    unsigned S, RS;      // items of a row that a tile spans; items of a stage row (odd)
-    unsigned G;          // channels of a group
-    unsigned rcpI, rcpD; // ceil(2^32 / n) for n >= 2: j div n = umulhi(j, rcp) for j < 2^22
+    RducTile tile;
 };
-
-typedef const float __attribute__((address_space(4))) * ConstTaps;
 
 // taps: [K][I][P] real taps g_k[p I + r] at [k][r][p], zero where p I + r >= L.  rot: [K][kRotBlock] phasors T_k.
 // Both are written at create only and are parameters of their own.
@@ -225,11 +192,11 @@ __global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* _
     extern __shared__ float2 s_rduc[];
     const unsigned tid = threadIdx.x, lane = tid & 63;
     const unsigned wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned I = a.I, D = a.D, L = a.L, P = a.P, T = a.T, TS = a.TS, RS = a.RS;
+    const unsigned I = a.I, D = a.D, L = a.L, P = a.P, T = a.tile.T, TS = a.tile.TS, RS = a.tile.RS;
     const unsigned IT = I * T, row_items = D * RS;
     float2* tile = s_rduc;                     // [I][TS]
     float2* blk = s_rduc + I * TS;             // [G][kRotSpan]: A_k of the aligned blocks the tile touches
-    float2* stage = blk + a.G * kRotSpan;      // [G][D][RS]
+    float2* stage = blk + a.tile.G * kRotSpan; // [G][D][RS]
     const size_t n0 = static_cast<size_t>(blockIdx.x) * IT; // the tile's first sample
     const unsigned n = static_cast<unsigned>(a.n_out - n0 < IT ? a.n_out - n0 : IT);
     const uint64_t u0 = a.u0 + static_cast<uint64_t>(n0) * D;
@@ -238,34 +205,24 @@ __global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* _
     const uint32_t i0 = a.pos + static_cast<uint32_t>(n0);
     const unsigned o0 = i0 & (kRotBlock - 1);
     const unsigned n_blk = (o0 + n - 1) / kRotBlock + 1;     // at most kRotSpan: I T <= 2048
-    const unsigned n_units = I * a.chunks;
-    auto div_I = [&](unsigned j) { return I == 1 ? j : __umulhi(j, a.rcpI); };
-    auto div_D = [&](unsigned j) { return D == 1 ? j : __umulhi(j, a.rcpD); };
+    const unsigned n_units = I * a.tile.chunks;
+    auto div_I = [&](unsigned j) { return I == 1 ? j : __umulhi(j, a.tile.rcpI); };
+    auto div_D = [&](unsigned j) { return D == 1 ? j : __umulhi(j, a.tile.rcpD); };
 
     bool first = true;
-    for (unsigned k0 = 0; k0 < a.K; k0 += a.G) {
-        const unsigned gc = a.K - k0 < a.G ? a.K - k0 : a.G;
+    for (unsigned k0 = 0; k0 < a.K; k0 += a.tile.G) {
+        const unsigned gc = a.K - k0 < a.tile.G ? a.K - k0 : a.tile.G;
         if (!first) __syncthreads(); // the previous group's stage has been read
         // stage item s of a row: item c0 + s of its virtual stream, that is item c0 - (P - 1) + s of this call; the
         // tile's last sample takes its tap 0 from item (b0 + (I T - 1) D) div I + P - 1 < S
         for (unsigned kk = 0; kk < gc; ++kk) {
             const float2* hist = a.hist + static_cast<size_t>(k0 + kk) * (P - 1);
             const float2* in = a.in + static_cast<size_t>(k0 + kk) * a.in_stride;
-            float2* sk = stage + kk * row_items;
-            for (unsigned s = tid; s < a.S; s += kNt) {
-                const unsigned col = div_D(s), row = s - col * D;
-                const size_t v = static_cast<size_t>(c0) + s;
-                float2 x = {0.0f, 0.0f};
-                if (v < a.total) x = v < P - 1 ? hist[v] : in[v - (P - 1)];
-                sk[row * RS + col] = x;
-            }
+            gr4pm::stage_by_phase(stage + kk * row_items, a.tile.S, D, a.tile.rcpD, RS, static_cast<size_t>(c0), a.total, hist, P - 1, in);
         }
         if (tid < gc * n_blk) {
             const unsigned kk = tid / n_blk, bb = tid - kk * n_blk;
-            const uint32_t phi = a.w[k0 + kk] * (i0 - o0 + bb * kRotBlock);
-            double sn, cs;
-            sincospi(static_cast<double>(phi) * (1.0 / 2147483648.0), &sn, &cs); // the argument is exact
-            blk[kk * kRotSpan + bb] = float2{static_cast<float>(cs), static_cast<float>(sn)};
+            blk[kk * kRotSpan + bb] = gr4pm::mixer<1>(a.w[k0 + kk], i0 - o0 + bb * kRotBlock);
         }
         __syncthreads();
         for (unsigned u = wave; u < n_units; u += kNt / 64) {
@@ -311,42 +268,22 @@ __global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* _
 
     // sample t of the tile is at tile[t mod I][t div I]; one sample alone where out + n0 is only 8-byte aligned
     float2* __restrict__ out = a.out + n0;
-    auto sample = [&](unsigned t) {
+    gr4pm::store_tile(out, n, static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) >> 3) & 1u, [&](unsigned t) {
         const unsigned l = div_I(t);
         return tile[(t - l * I) * TS + l];
-    };
-    const unsigned head = static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) >> 3) & 1u;
-    if (tid == 0 && head && n) out[0] = sample(0);
-    for (unsigned t = head + 2 * tid; t < n; t += 2 * kNt) {
-        if (t + 1 < n) {
-            const float2 lo = sample(t), hi = sample(t + 1);
-            *reinterpret_cast<float4*>(out + t) = float4{lo.x, lo.y, hi.x, hi.y};
-        } else {
-            out[t] = sample(t);
-        }
-    }
+    });
 }
 
+// the two designs share their sizes' checks only; their band edges differ: the integer Duc admits passband + stopband
+// <= I of the input rate (band_edges_valid: a cutoff within fs / 2), the rational one at most min(1, I / D)
 gr4pm_status design_rational_taps(size_t I, size_t D, size_t P, double passband, double stopband, std::vector<double>& h)
 {
-    using gr4pm::set_error;
-    if (I < 1 || I > kMaxI) {
-        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
-        return GR4PM_ERR_INVALID;
-    }
-    if (D < 1 || D > kMaxD) {
-        set_error("duc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
-        return GR4PM_ERR_INVALID;
-    }
-    if (P < 1 || P * I > kMaxL) {
-        set_error("duc: %zu taps per phase at an interpolation of %zu: the prototype has 1 .. %zu taps", P, I, kMaxL);
-        return GR4PM_ERR_INVALID;
-    }
+    GR4PM_TRY(gr4pm::design_sizes("duc", I, kMaxI, D, kMaxD, P, I, "an interpolation", kMaxL));
     // the cutoff, (passband + stopband) / 2 of the input rate, within half of the input rate and half of the output rate
     const double most = I < D ? static_cast<double>(I) / static_cast<double>(D) : 1.0;
     if (!(passband >= 0.0 && passband < stopband && passband + stopband <= most)) {
-        set_error("duc: need 0 <= passband < stopband (units of the input rate, the output's is %zu / %zu of it) and a cutoff "
-                  "of at most half of the lower of the input and the output rate: passband + stopband <= %g", I, D, most);
+        gr4pm::set_error("duc: need 0 <= passband < stopband (units of the input rate, the output's is %zu / %zu of it) and a cutoff "
+                         "of at most half of the lower of the input and the output rate: passband + stopband <= %g", I, D, most);
         return GR4PM_ERR_INVALID;
     }
     gr4pm::kaiser_lowpass(P * I, I, passband, stopband, h, static_cast<double>(I));
@@ -355,17 +292,9 @@ gr4pm_status design_rational_taps(size_t I, size_t D, size_t P, double passband,
 
 gr4pm_status design_taps(size_t I, size_t P, double passband, double stopband, std::vector<double>& h)
 {
-    using gr4pm::set_error;
-    if (I < 1 || I > kMaxI) {
-        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
-        return GR4PM_ERR_INVALID;
-    }
-    if (P < 1 || P * I > kMaxL) {
-        set_error("duc: %zu taps per phase at an interpolation of %zu: the prototype has 1 .. %zu taps", P, I, kMaxL);
-        return GR4PM_ERR_INVALID;
-    }
+    GR4PM_TRY(gr4pm::design_sizes("duc", I, kMaxI, 1, kMaxD, P, I, "an interpolation", kMaxL));
     if (!gr4pm::band_edges_valid(passband, stopband, I, true)) {
-        set_error("duc: need 0 <= passband < stopband (units of the input rate) and a cutoff of at most fs / 2");
+        gr4pm::set_error("duc: need 0 <= passband < stopband (units of the input rate) and a cutoff of at most fs / 2");
         return GR4PM_ERR_INVALID;
     }
     gr4pm::kaiser_lowpass(P * I, I, passband, stopband, h, static_cast<double>(I));
@@ -375,78 +304,103 @@ gr4pm_status design_taps(size_t I, size_t P, double passband, double stopband, s
 } // namespace
 
 struct gr4pm_duc {
-    size_t K = 0, I = 0, L = 0, P = 0, max_items = 0;
-    unsigned R = 0, IP = 0, T = 0, TS = 0, WF = 0, G = 0, Pc = 0, ZS = 0, rcpI = 0;
-    size_t smem = 0;
+    size_t K = 0, I = 0, D = 1, max_items = 0;
     uint64_t start_index = 0;
     uint64_t pos = 0;       // absolute index of the next output sample
     gr4pm::StreamTail tail; // P - 1 items of every row, frames of one item: nothing is ever carried
     hipStream_t stream = nullptr;
     std::vector<uint32_t> words;
-    gr4pm::DevBuf<float2> d_g;
     gr4pm::DevBuf<uint32_t> d_w;
-    // a rational handle (D > 1; the tail still keeps P - 1 items of every row)
-    size_t D = 1;
-    unsigned chunks = 0, S = 0, RS = 0, rcpD = 0;
-    gr4pm::hostlogic::DucPosition at; // items taken, the next sample's newest item and branch
-    gr4pm::DevBuf<float> d_taps;      // [K][I][P]
-    gr4pm::DevBuf<float2> d_rot;      // [K][kRotBlock]
+    // what does not change from call to call, in the struct the handle's kernel takes
+    DucArgs args = {};   // D = 1
+    RducArgs rargs = {}; // D > 1
+    unsigned smem = 0, R = 0;         // of a launch
+    gr4pm::DevBuf<float2> d_g;        // D = 1: the rotated taps [K][P][IP]
+    gr4pm::hostlogic::ResamplePosition at; // D > 1: items taken, the next sample's newest item and branch
+    gr4pm::DevBuf<float> d_taps;      // D > 1: [K][I][P]
+    gr4pm::DevBuf<float2> d_rot;      // D > 1: [K][kRotBlock]
 };
 
 using namespace gr4pm;
 
-static gr4pm_status process_rational(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
-                                     size_t out_cap, size_t* n_out)
+template <int R>
+static void launch_r(dim3 grid, size_t smem, hipStream_t s, const DucArgs& a, const float2* g)
 {
-    if (n_in > h->max_items) {
-        set_error("duc: %zu items per row, the handle was made for %zu", n_in, h->max_items);
-        return GR4PM_ERR_OVERFLOW;
+    hipLaunchKernelGGL(k_duc<R>, grid, dim3(kNt), smem, s, a, g);
+}
+
+// both creates: gr4pm_duc_create's handle is the ratio I / 1
+static gr4pm_status create(const gr4pm_duc_rational_params* p, gr4pm_duc** out)
+{
+    const size_t K = p->n_channels, I = p->interpolation, D = p->decimation;
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("duc", p->frequencies, K, kMaxK, words));
+    GR4PM_TRY(resample_ratio("duc", I, kMaxI, D, kMaxD));
+    GR4PM_TRY(finite_gains("duc", p->gains, K));
+    GR4PM_TRY(per_call_cap("duc", "max_items", p->max_items));
+    GR4PM_TRY(prototype_length("duc", p->taps, p->n_taps, kMaxL));
+    std::vector<float> taps;
+    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) {
+        return D > 1 ? design_rational_taps(I, D, 12, 0.25, 0.75, hd) : design_taps(I, 12, 0.25, 0.75, hd);
+    }, taps));
+    const size_t L = taps.size(), P = (L + I - 1) / I;
+    GR4PM_TRY(require_device());
+    std::unique_ptr<gr4pm_duc> h(new (std::nothrow) gr4pm_duc);
+    if (!h) return GR4PM_ERR_NOMEM;
+    h->K = K;
+    h->I = I;
+    h->D = D;
+    h->max_items = p->max_items;
+    h->start_index = h->pos = p->start_index;
+    h->stream = static_cast<hipStream_t>(p->stream);
+    h->words = std::move(words);
+    GR4PM_TRY(h->d_w.alloc(K));
+    const unsigned Ku = static_cast<unsigned>(K), Iu = static_cast<unsigned>(I), Lu = static_cast<unsigned>(L),
+                   Pu = static_cast<unsigned>(P);
+    if (D > 1) {
+        RducArgs& a = h->rargs;
+        a.w = h->d_w.p;
+        a.K = Ku, a.I = Iu, a.D = static_cast<unsigned>(D), a.L = Lu, a.P = Pu;
+        RducGeometry geo;
+        if (!rduc_geometry(I, D, L, K, geo)) {
+            set_error("duc: no tile of %zu / %zu with %zu taps fits the stage", I, D, L);
+            return GR4PM_ERR_INVALID;
+        }
+        a.tile = geo.tile, h->smem = geo.smem;
+        h->at.I = I, h->at.D = D;
+        std::vector<float> g(K * I * P, 0.0f);
+        std::vector<float2> rot(K * kRotBlock);
+        for (size_t k = 0; k < K; ++k) {
+            const double gain = p->gains ? p->gains[k] : 1.0;
+            for (size_t t = 0; t < L; ++t) g[(k * I + t % I) * P + t / I] = static_cast<float>(gain * static_cast<double>(taps[t]));
+            for (size_t t = 0; t < kRotBlock; ++t) rot[k * kRotBlock + t] = rotated_tap(1.0, h->words[k] * static_cast<uint32_t>(t));
+        }
+        GR4PM_TRY(h->d_taps.alloc(g.size()));
+        GR4PM_TRY(h->d_rot.alloc(rot.size()));
+        GR4PM_TRY(h->d_taps.upload(g.data(), g.size(), h->stream));
+        GR4PM_TRY(h->d_rot.upload(rot.data(), rot.size(), h->stream));
+        if (h->smem > 48 * 1024)
+            GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_duc_rational)}, kRducLdsItemsMost * sizeof(float2), "duc"));
+    } else {
+        DucArgs& a = h->args;
+        a.w = h->d_w.p;
+        a.K = Ku, a.I = Iu, a.L = Lu, a.P = Pu;
+        const DucGeometry geo = duc_geometry(I, L, K);
+        a.tile = geo.tile, h->smem = geo.smem, h->R = geo.R;
+        const size_t IP = geo.tile.IP;
+        std::vector<float2> g(K * P * IP, float2{0.0f, 0.0f});
+        for (size_t k = 0; k < K; ++k) {
+            const uint32_t w = h->words[k];
+            const double gain = p->gains ? p->gains[k] : 1.0;
+            for (size_t t = 0; t < L; ++t)
+                g[(k * P + t / I) * IP + t % I] = rotated_tap(gain * static_cast<double>(taps[t]), w * static_cast<uint32_t>(t));
+        }
+        GR4PM_TRY(h->d_g.alloc(g.size()));
+        GR4PM_TRY(h->d_g.upload(g.data(), g.size(), h->stream));
     }
-    if (n_in == 0) return GR4PM_OK;
-    const uint64_t F = h->at.samples(n_in);
-    const uint64_t tile = static_cast<uint64_t>(h->I) * h->T, blocks = (F + tile - 1) / tile;
-    if (F > out_cap || blocks > 0x7FFFFFFFu) {
-        set_error("duc: %llu samples, room for %zu", static_cast<unsigned long long>(F), out_cap);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (!in || (F && !out) || (h->K > 1 && in_stride < n_in)) {
-        set_error("duc: no input or output array, or a row stride of %zu items for %zu items", in_stride, n_in);
-        return GR4PM_ERR_INVALID;
-    }
-    const StreamTail::Plan t = h->tail.plan(n_in);
-    RducArgs a;
-    a.hist = t.hist;
-    a.in = reinterpret_cast<const float2*>(in);
-    a.out = reinterpret_cast<float2*>(out);
-    a.w = h->d_w.p;
-    a.in_stride = in_stride;
-    a.total = t.H + n_in;
-    a.n_out = static_cast<size_t>(F);
-    a.u0 = h->at.first();
-    a.pos = static_cast<uint32_t>(h->pos);
-    a.K = static_cast<unsigned>(h->K);
-    a.I = static_cast<unsigned>(h->I);
-    a.D = static_cast<unsigned>(h->D);
-    a.L = static_cast<unsigned>(h->L);
-    a.P = static_cast<unsigned>(h->P);
-    a.T = h->T;
-    a.TS = h->TS;
-    a.chunks = h->chunks;
-    a.S = h->S;
-    a.RS = h->RS;
-    a.G = h->G;
-    a.rcpI = h->rcpI;
-    a.rcpD = h->rcpD;
-    if (F)
-        hipLaunchKernelGGL(k_duc_rational, dim3(static_cast<unsigned>(blocks)), dim3(kNt), h->smem, h->stream, a, h->d_taps.p,
-                           h->d_rot.p);
-    h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
-    GR4PM_HIP_TRY(hipGetLastError());
-    h->tail.commit(t);
-    h->at.advance(n_in, F);
-    h->pos += F;
-    *n_out = static_cast<size_t>(F);
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
+    GR4PM_TRY(h->tail.alloc(P - 1, 1, K, h->stream));
+    return finish_create(h, out, "duc");
 }
 
 extern "C" {
@@ -465,77 +419,9 @@ gr4pm_status gr4pm_duc_create(const gr4pm_duc_params* p, gr4pm_duc** out)
 try {
     if (!p || !out) return GR4PM_ERR_INVALID;
     *out = nullptr;
-    const size_t K = p->n_channels, I = p->interpolation;
-    std::vector<uint32_t> words;
-    GR4PM_TRY(frequency_words("duc", p->frequencies, K, kMaxK, words));
-    if (I < 1 || I > kMaxI) {
-        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
-        return GR4PM_ERR_INVALID;
-    }
-    for (size_t k = 0; p->gains && k < K; ++k)
-        if (!std::isfinite(p->gains[k])) {
-            set_error("duc: gains[%zu] is not finite", k);
-            return GR4PM_ERR_INVALID;
-        }
-    if (p->max_items == 0 || p->max_items > (size_t(1) << 31)) {
-        set_error("duc: max_items must be in [1, 2^31]");
-        return GR4PM_ERR_INVALID;
-    }
-    if (p->taps && (p->n_taps < 1 || p->n_taps > kMaxL)) {
-        set_error("duc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
-        return GR4PM_ERR_INVALID;
-    }
-    std::vector<float> taps;
-    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) { return design_taps(I, 12, 0.25, 0.75, hd); }, taps));
-    const size_t L = taps.size(), P = (L + I - 1) / I;
-    GR4PM_TRY(require_device());
-    std::unique_ptr<gr4pm_duc> h(new (std::nothrow) gr4pm_duc);
-    if (!h) return GR4PM_ERR_NOMEM;
-    h->K = K;
-    h->I = I;
-    h->L = L;
-    h->P = P;
-    h->max_items = p->max_items;
-    h->start_index = h->pos = p->start_index;
-    h->stream = static_cast<hipStream_t>(p->stream);
-    // the tile: R phases per lane, T frames (even unless I = 1, so that T I is even) of about kTileItems samples in all;
-    // the stage: whole channels while T + P - 1 items of each fit, else one channel and chunks of the p loop
-    const size_t R = I >= 8 ? 8 : I >= 4 ? 4 : I >= 2 ? 2 : 1;
-    const size_t IP = (I + R - 1) / R * R;
-    size_t T = kTileItems / I & ~size_t(1);
-    T = T > static_cast<size_t>(kNt) ? static_cast<size_t>(kNt) : T < 2 ? 2 : T;
-    size_t G = 1, Pc = P;
-    if (T + P - 1 <= kStageItems) {
-        G = kStageItems / (T + P - 1);
-        if (G > K) G = K;
-    } else {
-        Pc = kStageItems - T + 1;
-    }
-    h->R = static_cast<unsigned>(R);
-    h->IP = static_cast<unsigned>(IP);
-    h->T = static_cast<unsigned>(T);
-    h->TS = static_cast<unsigned>(T | 1);
-    h->WF = T <= 64 ? 1u : T <= 128 ? 2u : 4u;
-    h->G = static_cast<unsigned>(G);
-    h->Pc = static_cast<unsigned>(Pc);
-    h->ZS = static_cast<unsigned>(T + Pc - 1);
-    h->rcpI = reciprocal_word(I);
-    h->smem = (IP * h->TS + G * h->ZS) * sizeof(float2); // at most 29 KiB + 16 KiB
-
-    h->words = std::move(words);
-    std::vector<float2> g(K * P * IP, float2{0.0f, 0.0f});
-    for (size_t k = 0; k < K; ++k) {
-        const uint32_t w = h->words[k];
-        const double a = p->gains ? p->gains[k] : 1.0;
-        for (size_t t = 0; t < L; ++t)
-            g[(k * P + t / I) * IP + t % I] = rotated_tap(a * static_cast<double>(taps[t]), w * static_cast<uint32_t>(t));
-    }
-    GR4PM_TRY(h->d_g.alloc(g.size()));
-    GR4PM_TRY(h->d_w.alloc(K));
-    GR4PM_TRY(h->tail.alloc(P - 1, 1, K, h->stream));
-    GR4PM_TRY(h->d_g.upload(g.data(), g.size(), h->stream));
-    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
-    return finish_create(h, out, "duc");
+    const gr4pm_duc_rational_params q = {p->n_channels, p->interpolation, p->frequencies, p->gains, p->taps, p->n_taps,
+                                         p->max_items, p->start_index, p->stream, 1};
+    return create(&q, out);
 }
 GR4PM_ABI_CATCH
 
@@ -554,111 +440,7 @@ gr4pm_status gr4pm_duc_create_rational(const gr4pm_duc_rational_params* p, gr4pm
 try {
     if (!p || !out) return GR4PM_ERR_INVALID;
     *out = nullptr;
-    const size_t K = p->n_channels, I = p->interpolation, D = p->decimation;
-    if (D < 1 || D > kMaxD) {
-        set_error("duc: the decimation must be in [1, %zu], not %zu", kMaxD, D);
-        return GR4PM_ERR_INVALID;
-    }
-    if (D == 1) { // the integer Duc, with its own kernel
-        const gr4pm_duc_params q = {K, I, p->frequencies, p->gains, p->taps, p->n_taps, p->max_items, p->start_index, p->stream};
-        return gr4pm_duc_create(&q, out);
-    }
-    std::vector<uint32_t> words;
-    GR4PM_TRY(frequency_words("duc", p->frequencies, K, kMaxK, words));
-    if (I < 1 || I > kMaxI) {
-        set_error("duc: the interpolation must be in [1, %zu], not %zu", kMaxI, I);
-        return GR4PM_ERR_INVALID;
-    }
-    size_t gcd = I;
-    for (size_t b = D % I; b;) {
-        const size_t r = gcd % b;
-        gcd = b, b = r;
-    }
-    if (gcd != 1) {
-        set_error("duc: the ratio %zu / %zu is not in lowest terms: use %zu / %zu", I, D, I / gcd, D / gcd);
-        return GR4PM_ERR_INVALID;
-    }
-    for (size_t k = 0; p->gains && k < K; ++k)
-        if (!std::isfinite(p->gains[k])) {
-            set_error("duc: gains[%zu] is not finite", k);
-            return GR4PM_ERR_INVALID;
-        }
-    if (p->max_items == 0 || p->max_items > (size_t(1) << 31)) {
-        set_error("duc: max_items must be in [1, 2^31]");
-        return GR4PM_ERR_INVALID;
-    }
-    if (p->taps && (p->n_taps < 1 || p->n_taps > kMaxL)) {
-        set_error("duc: the prototype has 1 .. %zu taps, not %zu", kMaxL, p->n_taps);
-        return GR4PM_ERR_INVALID;
-    }
-    std::vector<float> taps;
-    GR4PM_TRY(taps_or_design(p->taps, p->n_taps, [&](std::vector<double>& hd) { return design_rational_taps(I, D, 12, 0.25, 0.75, hd); },
-                             taps));
-    const size_t L = taps.size(), P = (L + I - 1) / I;
-    GR4PM_TRY(require_device());
-    std::unique_ptr<gr4pm_duc> h(new (std::nothrow) gr4pm_duc);
-    if (!h) return GR4PM_ERR_NOMEM;
-    h->K = K;
-    h->I = I;
-    h->D = D;
-    h->L = L;
-    h->P = P;
-    h->max_items = p->max_items;
-    h->start_index = h->pos = p->start_index;
-    h->stream = static_cast<hipStream_t>(p->stream);
-    h->at.I = I;
-    h->at.D = D;
-    // the tile: T samples per branch, about kTileItems in all and whole waves of a branch where that gives 64 or more;
-    // the stage: D rows of an odd number of items for the ((I T - 1) D + I - 1) div I + P items that I T consecutive
-    // samples reach.  The largest T whose tile and one channel's stage fit kLdsItems, or T = 1 in kLdsItemsMost; then as
-    // many channels to a group as fit.  The taps are never chunked.
-    size_t T = kTileItems / I;
-    T = T >= 64 ? (T > static_cast<size_t>(kNt) ? static_cast<size_t>(kNt) : T / 64 * 64) : (T < 1 ? 1 : T);
-    size_t S = 0, RS = 0, budget = kLdsItems;
-    for (;;) {
-        S = ((I * T - 1) * D + I - 1) / I + P;
-        RS = ((S + D - 1) / D) | 1;
-        if (I * (T | 1) + kRotSpan + D * RS <= budget) break;
-        if (T == 1) {
-            if (budget == kLdsItemsMost) {
-                set_error("duc: no tile of %zu / %zu with %zu taps fits the stage", I, D, L);
-                return GR4PM_ERR_INVALID;
-            }
-            budget = kLdsItemsMost;
-        } else {
-            T -= T > 64 ? 64 : 1;
-        }
-    }
-    size_t G = (budget - I * (T | 1)) / (D * RS + kRotSpan);
-    if (G > K) G = K;
-    h->T = static_cast<unsigned>(T);
-    h->TS = static_cast<unsigned>(T | 1);
-    h->chunks = static_cast<unsigned>((T + 63) / 64);
-    h->S = static_cast<unsigned>(S);
-    h->RS = static_cast<unsigned>(RS);
-    h->G = static_cast<unsigned>(G);
-    h->rcpI = reciprocal_word(I);
-    h->rcpD = reciprocal_word(D);
-    h->smem = (I * h->TS + G * (D * RS + kRotSpan)) * sizeof(float2);
-
-    h->words = std::move(words);
-    std::vector<float> g(K * I * P, 0.0f);
-    std::vector<float2> rot(K * kRotBlock);
-    for (size_t k = 0; k < K; ++k) {
-        const double a = p->gains ? p->gains[k] : 1.0;
-        for (size_t t = 0; t < L; ++t) g[(k * I + t % I) * P + t / I] = static_cast<float>(a * static_cast<double>(taps[t]));
-        for (size_t t = 0; t < kRotBlock; ++t) rot[k * kRotBlock + t] = rotated_tap(1.0, h->words[k] * static_cast<uint32_t>(t));
-    }
-    GR4PM_TRY(h->d_taps.alloc(g.size()));
-    GR4PM_TRY(h->d_rot.alloc(rot.size()));
-    GR4PM_TRY(h->d_w.alloc(K));
-    GR4PM_TRY(h->tail.alloc(P - 1, 1, K, h->stream));
-    GR4PM_TRY(h->d_taps.upload(g.data(), g.size(), h->stream));
-    GR4PM_TRY(h->d_rot.upload(rot.data(), rot.size(), h->stream));
-    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
-    if (h->smem > 48 * 1024)
-        GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_duc_rational)}, kLdsItemsMost * sizeof(float2), "duc"));
-    return finish_create(h, out, "duc");
+    return create(p, out);
 }
 GR4PM_ABI_CATCH
 
@@ -701,56 +483,57 @@ gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stri
 try {
     if (!h || !n_out) return GR4PM_ERR_INVALID;
     *n_out = 0;
-    if (h->D > 1) return process_rational(h, in, in_stride, n_in, out, out_cap, n_out);
     if (n_in > h->max_items) {
         set_error("duc: %zu items per row, the handle was made for %zu", n_in, h->max_items);
         return GR4PM_ERR_OVERFLOW;
     }
     if (n_in == 0) return GR4PM_OK;
-    const size_t N = n_in * h->I;
-    if (N > out_cap) {
-        set_error("duc: %zu samples, room for %zu", N, out_cap);
+    const bool rational = h->D > 1;
+    const uint64_t F = rational ? h->at.samples(n_in) : static_cast<uint64_t>(n_in) * h->I;
+    const uint64_t tile = static_cast<uint64_t>(h->I) * (rational ? h->rargs.tile.T : h->args.tile.T), blocks = (F + tile - 1) / tile;
+    if (F > out_cap || blocks > 0x7FFFFFFFu) {
+        set_error("duc: %llu samples, room for %zu", static_cast<unsigned long long>(F), out_cap);
         return GR4PM_ERR_OVERFLOW;
     }
-    if (!in || !out || (h->K > 1 && in_stride < n_in)) {
+    if (!in || (F && !out) || (h->K > 1 && in_stride < n_in)) {
         set_error("duc: no input or output array, or a row stride of %zu items for %zu items", in_stride, n_in);
         return GR4PM_ERR_INVALID;
     }
     const StreamTail::Plan t = h->tail.plan(n_in);
-    DucArgs a;
-    a.hist = t.hist;
-    a.in = reinterpret_cast<const float2*>(in);
-    a.out = reinterpret_cast<float2*>(out);
-    a.w = h->d_w.p;
-    a.in_stride = in_stride;
-    a.n_in = n_in;
-    a.n_out = N;
-    a.pos = static_cast<uint32_t>(h->pos);
-    a.K = static_cast<unsigned>(h->K);
-    a.I = static_cast<unsigned>(h->I);
-    a.L = static_cast<unsigned>(h->L);
-    a.P = static_cast<unsigned>(h->P);
-    a.IP = h->IP;
-    a.T = h->T;
-    a.TS = h->TS;
-    a.WF = h->WF;
-    a.G = h->G;
-    a.Pc = h->Pc;
-    a.ZS = h->ZS;
-    a.rcpI = h->rcpI;
-    a.vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
-    const dim3 grid(static_cast<unsigned>((n_in + h->T - 1) / h->T));
-    switch (h->R) {
-    case 1: launch_r<1>(grid, h->smem, h->stream, a, h->d_g.p); break;
-    case 2: launch_r<2>(grid, h->smem, h->stream, a, h->d_g.p); break;
-    case 4: launch_r<4>(grid, h->smem, h->stream, a, h->d_g.p); break;
-    default: launch_r<8>(grid, h->smem, h->stream, a, h->d_g.p); break;
+    // the per-call fields of either argument struct
+    auto fill = [&](auto& a) {
+        a.hist = t.hist;
+        a.in = reinterpret_cast<const float2*>(in);
+        a.out = reinterpret_cast<float2*>(out);
+        a.in_stride = in_stride;
+        a.n_out = static_cast<size_t>(F);
+        a.pos = static_cast<uint32_t>(h->pos);
+    };
+    const dim3 grid(static_cast<unsigned>(blocks));
+    if (rational) {
+        RducArgs a = h->rargs;
+        fill(a);
+        a.total = t.H + n_in;
+        a.u0 = h->at.first();
+        if (F) hipLaunchKernelGGL(k_duc_rational, grid, dim3(kNt), h->smem, h->stream, a, h->d_taps.p, h->d_rot.p);
+    } else {
+        DucArgs a = h->args;
+        fill(a);
+        a.n_in = n_in;
+        a.vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
+        switch (h->R) {
+        case 1: launch_r<1>(grid, h->smem, h->stream, a, h->d_g.p); break;
+        case 2: launch_r<2>(grid, h->smem, h->stream, a, h->d_g.p); break;
+        case 4: launch_r<4>(grid, h->smem, h->stream, a, h->d_g.p); break;
+        default: launch_r<8>(grid, h->smem, h->stream, a, h->d_g.p); break;
+        }
     }
     h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
     GR4PM_HIP_TRY(hipGetLastError());
     h->tail.commit(t);
-    h->pos += N;
-    *n_out = N;
+    if (rational) h->at.advance(n_in, F);
+    h->pos += F;
+    *n_out = static_cast<size_t>(F);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH

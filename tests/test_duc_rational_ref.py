@@ -2,7 +2,7 @@
 (zero-stuff, filter, keep every D-th, mix, sum), the form the kernel implements and plain zero-stuff / np.convolve /
 [::D], large start indices against a direct evaluation with Python integers, D = 1 against the integer Duc's
 reference, the sample count under random call cuts, the float64 loopback through the rational Ddc's reference, the
-host-only tap design, and the HIP-free position arithmetic (csrc/hostlogic/duc_position.hpp) as a stand-alone program
+host-only tap design, and the HIP-free position arithmetic (csrc/hostlogic/resample_position.hpp) as a stand-alone program
 under UndefinedBehaviorSanitizer and AddressSanitizer against Python integers."""
 import math
 import os
@@ -196,39 +196,55 @@ def test_tap_design():
 
 
 def test_position_header_under_sanitizers(tmp_path):
-    """csrc/hostlogic/duc_position.hpp, the arithmetic gr4pm_duc_process runs on the host, as a stand-alone program
-    built with -fsanitize=undefined,address: the samples of every call, first() and the state behind it against Python
-    integers, for random (I, D) and call lengths, from positions near 2^63 and across the wrap of the 64-bit counters"""
+    """csrc/hostlogic/resample_position.hpp, the arithmetic gr4pm_duc_process and gr4pm_ddc_process run on the host, as
+    a stand-alone program built with -fsanitize=undefined,address: the outputs of every call, first() and the state
+    behind it against Python integers, for random (I, D) and call lengths, from positions near 2^63 and across the wrap
+    of the 64-bit counters.  Every case runs as a Duc's (lead = 0: N items have made ceil(N I / D) samples) and, with the
+    pair swapped so that I <= 64 and D <= 1024, as a Ddc's (lead = D - 1: floor(N I / D) items, and the calls of any cut
+    of N samples sum to _ddc_rational_ref.item_count)"""
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "needs a host C++ compiler"
-    exe = str(tmp_path / "duc_position_check.bin")
+    exe = str(tmp_path / "resample_position_check.bin")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-fsanitize=undefined,address",
                     "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "gr4-packet-modem_amd", "csrc"), "-o", exe,
-                    os.path.join(ROOT, "tests", "hostlogic", "duc_position_check.cpp")], check=True, capture_output=True, text=True)
+                    os.path.join(ROOT, "tests", "hostlogic", "resample_position_check.cpp")], check=True, capture_output=True, text=True)
     rng = np.random.default_rng(19)
     M = 1 << 64
-    lines, want = [], []
+    lines, want, cuts = [], [], []  # cuts: (first line of `want`, calls, I, D, N before, N after) of every Ddc case
     pairs = [(25, 4), (3, 2), (12, 5), (1, 7), (5, 3), (1000, 63), (63, 64), (1023, 64), (2, 3), (1024, 63), (1, 64)]
     while len(pairs) < 60:
         i, d = int(rng.integers(1, 1025)), int(rng.integers(2, 65))
         if math.gcd(i, d) == 1:
             pairs.append((i, d))
     bases = [0, 1, (1 << 31) + 5, (1 << 63) - 1000, (1 << 63) + 3, M - 50, (M - 3 * 1024) // 1024]
-    for c, (I, D) in enumerate(pairs):
-        N = bases[c % len(bases)] + int(rng.integers(0, 100))  # items taken so far: a Python integer, never reduced
-        J = -(-N * I // D)                                     # samples made so far
-        lens = [0, 1, 1, 0, 1, D, I] + [int(t) for t in rng.integers(0, 4 * D + 3, 30)] + [1 << 31, int(rng.integers(1, 1 << 31))]
-        m, r = divmod(J * D, I)
-        lines.append(" ".join(str(t) for t in [I, D, N % M, m % M, r, len(lens)] + lens))
+
+    def case(I, D, lead, N, lens):
+        made = lambda n: max(0, -(-(n * I - lead) // D))  # outputs whose newest item (lead + j D) div I is below n
+        J = made(N)
+        m, r = divmod(lead + J * D, I)
+        lines.append(" ".join(str(t) for t in [I, D, lead, N % M, m % M, r, len(lens)] + lens))
         for n in lens:
-            first = J * D - N * I
+            first = lead + J * D - N * I
             assert 0 <= first < I + D
             N += n
-            Jn = -(-N * I // D)
-            m, r = divmod(Jn * D, I)
+            Jn = made(N)
+            m, r = divmod(lead + Jn * D, I)
             want.append(f"{Jn - J} {first} {N % M} {m % M} {r}")
             J = Jn
-        want.append("reset 0 0 0")
+        want.append(f"reset 0 {lead // I} {lead % I}")
+        return N
+
+    for c, (I, D) in enumerate(pairs):
+        N = bases[c % len(bases)] + int(rng.integers(0, 100))  # items taken so far: a Python integer, never reduced
+        lens = [0, 1, 1, 0, 1, D, I] + [int(t) for t in rng.integers(0, 4 * D + 3, 30)] + [1 << 31, int(rng.integers(1, 1 << 31))]
+        case(I, D, 0, N, lens)
+    assert all(w == "reset 0 0 0" for w in want if w.startswith("reset"))
+    for c, (D, I) in enumerate(pairs):  # the same pairs, bases and kinds of cut as a Ddc's: I <= 64, D <= 1024
+        assert I <= 64 and D <= 1024
+        for N in (bases[c % len(bases)] + int(rng.integers(0, 100)), 0):
+            lens = [0, 1, 1, 0, 1, D, I] + [int(t) for t in rng.integers(0, 4 * D + 3, 30)] + [1 << 31, int(rng.integers(1, 1 << 31))]
+            at = len(want)
+            cuts.append((at, len(lens), I, D, N, case(I, D, D - 1, N, lens)))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
     run = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env, timeout=120)
     assert run.returncode == 0, (run.stdout + run.stderr)[-4000:]
@@ -237,3 +253,7 @@ def test_position_header_under_sanitizers(tmp_path):
     assert len(got) == len(want)
     bad = [(g, w) for g, w in zip(got, want) if g != w]
     assert not bad, bad[:5]
+    for at, calls, I, D, N0, N1 in cuts:  # what the program printed, summed over the cut
+        total = sum(int(g.split()[0]) for g in got[at:at + calls])
+        assert total == dref_r.item_count(N1, I, D) - dref_r.item_count(N0, I, D)
+        assert N0 or total == N1 * I // D

@@ -61,7 +61,8 @@ def rational_legs(pkg, torch, args, x, n):
         Ki, Di, Li = (SHAPES[name][k] for k in "KDL")
         items = n * I // D
         d = pkg.Ddc(FREQS[:K], D, interpolation=I, taps=pkg.ddc_rational_taps(I, D, L // D), max_frames=items + I)
-        out = torch.empty((K, items), dtype=torch.complex64, device="cuda")
+        # the calls continue one stream: a call makes floor or ceil of n I / D items, by the handle's position
+        out = torch.empty((K, items + 1), dtype=torch.complex64, device="cuda")
         ms = median_ms(lambda: d.process_bulk(x, out=out), args.iters, torch)
         del d, out
         di = pkg.Ddc(FREQS[:Ki], Di, taps_per_phase=Li // Di, max_frames=n // Di)
