@@ -23,5 +23,12 @@ struct CopySpan {
     unsigned long long src, dst, len;
 };
 
+// a complex item as the kernels see it (stream_blocks.hip's `cf` is this type): the planners' tables hold it and the
+// kernels read those tables as they are
+struct cf {
+    float x, y;
+};
+static_assert(sizeof(cf) == 8, "two floats");
+
 } // namespace hostlogic
 } // namespace gr4pm

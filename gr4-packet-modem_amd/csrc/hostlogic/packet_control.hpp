@@ -2,7 +2,9 @@
 // (payload_metadata_insert.hpp:77-307), SyncwordRemove (syncword_remove.hpp:39-105) and HeaderPayloadSplit
 // (header_payload_split.hpp:38-135).  Each is a state machine over tags plus a copy of item spans; the replay of one
 // call -- chunk by chunk, chunks cut at the tags exactly as the runtime presents them -- yields the span table the
-// gather kernels work from and the output tags.
+// gather kernels work from and the output tags.  Beside them the two symbol-rate blocks that touch the items between
+// them: SyncwordWipeoff (syncword_wipeoff.hpp:53-82, the spans of a syncword inside a call) and ConstellationLLRDecoder
+// (constellation_llr_decoder.hpp:84-130, runs of one constellation and the re-indexed tags).
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -208,6 +210,110 @@ inline void sr_replay(SrState& h, size_t n, const gr4pm_packet_tag* tags_in, siz
         t = t1;
         pos = end;
     }
+}
+
+// SyncwordWipeoff (syncword_wipeoff.hpp:66-82): copy, then x[pos] *= syncword[pos] on spans
+struct WipeSpan {
+    unsigned long long start; // first item of the span inside this call
+    unsigned first;           // first syncword position
+    unsigned len;
+};
+static_assert(sizeof(WipeSpan) == 16, "the kernel's record");
+struct WipeState {
+    size_t syncword_size = 0;
+    bool in_syncword = false; // syncword_wipeoff.hpp:27-28
+    size_t position = 0;
+};
+// replay of syncword_wipeoff.hpp:53-75 over the tag list of one call: the spans of the syncword inside it
+// (base: offset of the channel's item 0 in the buffer the kernel indexes)
+inline void wipe_replay(WipeState& h, size_t n, const gr4pm_tag* tags, size_t n_tags, size_t base, std::vector<WipeSpan>& spans)
+{
+    size_t pos = 0, t = 0;
+    const size_t L = h.syncword_size;
+    while (pos < n) {
+        while (t < n_tags && tags[t].index < pos) ++t;
+        const bool has_tag = t < n_tags && tags[t].index == pos && (tags[t].flags & GR4PM_TAG_SYNCWORD);
+        if (!h.in_syncword && has_tag) {
+            h.in_syncword = true;
+            h.position = 0;
+        }
+        size_t end = n;
+        for (size_t u = t; u < n_tags; ++u)
+            if (tags[u].index > pos) {
+                end = std::min<size_t>(end, tags[u].index);
+                break;
+            }
+        if (h.in_syncword) {
+            const size_t m = std::min(end - pos, L - h.position);
+            spans.push_back({ base + pos, static_cast<unsigned>(h.position), static_cast<unsigned>(m) });
+            h.position += m;
+            if (h.position == L) h.in_syncword = false;
+        }
+        pos = end;
+        if (t < n_tags && tags[t].index < pos) ++t;
+    }
+}
+
+// LLR mapping of one run of symbols with one constellation: BPSK scale * re, QPSK
+// (scale * re, scale * im) = a scaled copy of the interleaved floats
+struct LlrRun {
+    unsigned long long in0, out0, n_out;
+    int qpsk;
+    int pad;
+};
+static_assert(sizeof(LlrRun) == 32, "the kernel's record");
+struct LlrState {
+    int constellation = 2; // 1 BPSK, 2 QPSK
+};
+// the host half of ConstellationLLRDecoder::processBulk over one call (constellation_llr_decoder.hpp:84-130): runs of
+// symbols with one constellation, the tags re-indexed to LLR positions (:93-99); the block's constellation follows the tags
+inline gr4pm_status llr_runs(LlrState& h, size_t n, size_t out_cap, const gr4pm_packet_tag* tags_in, size_t n_tags_in,
+                             gr4pm_packet_tag* tags_out, size_t tags_cap, size_t* n_tags_out, size_t* produced,
+                             std::vector<LlrRun>& runs)
+{
+    size_t pos = 0, opos = 0, n_pub = 0;
+    bool tag_overflow = false;
+    auto close_run = [&](size_t end) {
+        if (end <= pos) return;
+        LlrRun r{};
+        r.in0 = pos;
+        r.out0 = opos;
+        r.qpsk = h.constellation == 2;
+        r.n_out = (end - pos) * (r.qpsk ? 2 : 1);
+        runs.push_back(r);
+        opos += r.n_out;
+        pos = end;
+    };
+    for (size_t t = 0; t < n_tags_in; ++t) {
+        if (tags_in[t].index >= n) break;
+        close_run(static_cast<size_t>(tags_in[t].index));
+        if (tags_in[t].constellation >= 0) {
+            if (tags_in[t].constellation != 1 && tags_in[t].constellation != 2) {
+                set_error("constellation %d not supported", tags_in[t].constellation);
+                return GR4PM_ERR_INVALID;
+            }
+            h.constellation = tags_in[t].constellation;
+        }
+        if (tags_out && n_pub < tags_cap) { // :93-99
+            tags_out[n_pub] = tags_in[t];
+            tags_out[n_pub].index = opos;
+        } else {
+            tag_overflow = true;
+        }
+        ++n_pub;
+    }
+    close_run(n);
+    if (opos > out_cap) {
+        set_error("out_cap %zu < %zu LLRs", out_cap, opos);
+        return GR4PM_INSUFFICIENT_OUTPUT_ITEMS;
+    }
+    *produced = opos;
+    if (n_tags_out) *n_tags_out = n_pub;
+    if (tag_overflow) {
+        set_error("tags_cap too small");
+        return GR4PM_ERR_OVERFLOW;
+    }
+    return GR4PM_OK;
 }
 
 struct HpsState {

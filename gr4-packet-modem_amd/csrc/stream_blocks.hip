@@ -11,7 +11,9 @@
 // Pattern shared by all blocks: tags are sparse, so the tag-driven control flow of the
 // reference (which is per-chunk C++ on the CPU) is replayed on the host over the TAG LIST
 // only -- never over samples -- and turned into a small table of segments/runs; the kernels
-// then process every sample / symbol of the call in parallel from that table.  Recurrences
+// then process every sample / symbol of the call in parallel from that table.  That replay is
+// HIP-free code under hostlogic/ (built and checked on the CPU by tests/hostlogic/): this file
+// keeps the device side -- buffers, uploads, streams and events, kernel choice, launches.  Recurrences
 // whose float rounding makes them order dependent (rotator phasor, Costas PLL, resampler
 // phase accumulator) run serially per independent segment (one lane each).
 #include <algorithm>
@@ -22,9 +24,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "hostlogic/costas_plan.hpp"
+#include "hostlogic/packet_control.hpp"
+#include "hostlogic/rotator_plan.hpp"
 #include "hostlogic/sdf_gate.hpp"
 #include "hostlogic/symbol_filter_replay.hpp"
-#include "hostlogic/packet_control.hpp"
 
 namespace gr4pm {
 // GR4PM_TIMING_SKIP=name[,name]: timing experiments only -- the named kernels are not launched (their outputs are
@@ -51,9 +55,7 @@ static inline bool timing_skip(const char* name)
 #endif
 namespace {
 
-struct cf {
-    float x, y;
-};
+using hostlogic::cf; // hostlogic/base.hpp: the tables the host planners fill hold it
 __host__ __device__ __forceinline__ cf cmul(cf a, cf b)
 {
     return { a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x };
@@ -85,16 +87,8 @@ struct RotState {
     unsigned counter;
     unsigned pad;
 };
-struct RotSeg {
-    unsigned long long start; // offset inside the channel row
-    unsigned long long len;
-    unsigned channel;
-    unsigned ck0;  // first checkpoint slot of this segment
-    int mode;      // 0 continue from state[channel]; 1 set_freq: (exp0, incr)
-    int last;      // writes state[channel] back
-    cf exp0, incr;
-};
-constexpr unsigned kRotChunk = 8; // samples per checkpoint
+using hostlogic::RotSeg; // the segment table and who makes it: hostlogic/rotator_plan.hpp
+using hostlogic::kRotChunk;
 
 // one step of the phasor recurrence (rotator.hpp:58-63): e *= inc; renormalise when the
 // incremented counter is a multiple of 512
@@ -438,15 +432,7 @@ __device__ __forceinline__ void rot8_pk(cf (&x)[kRotChunk], cf e, cf inc)
 struct CostasState {
     float phase, freq;
 };
-struct CostasSeg {
-    unsigned long long start;
-    unsigned len;
-    unsigned channel;
-    int mode; // 0 continue, 1 set_phase(phase0)
-    int last;
-    float phase0;
-    float pad;
-};
+using hostlogic::CostasSeg; // hostlogic/costas_plan.hpp
 
 // cos/sin of the loop phase, BIT-EXACT with glibc's cosf / sinf / sincosf (what the reference's
 // std::cos(float) / std::sin(float) call, costas_loop.hpp:113-115).  glibc >= 2.28 evaluates them in
@@ -665,25 +651,9 @@ __global__ __attribute__((amdgpu_num_vgpr(16))) void k_costas_cap(const CostasSe
     }
 }
 
-// Tag-driven settings (gr4pm_costas_loop_process_packets): a chain is the run of items between
-// two set_phase events; it consists of pieces with their own constellation and loop
-// coefficients (syncword: PILOT, header and payload: QPSK with different bandwidths); phase
-// and frequency flow from piece to piece.  One lane per chain.
-struct CostasPiece {
-    unsigned long long start; // first item of the piece in the loop's OUTPUT (= its input stream's index)
-    long long in_off;         // its input items are in[start + in_off ...]: 0, or the gather of the block in front folded in
-    unsigned len;
-    int constellation;
-    float k1, k2;
-    unsigned pad;
-};
-struct CostasChain {
-    unsigned piece0, n_pieces;
-    int mode; // 0 continue from the carried state, 1 set_phase(phase0)
-    int last;
-    float phase0;
-    unsigned pad;
-};
+// Tag-driven settings (gr4pm_costas_loop_process_packets): one lane per chain of pieces (hostlogic/costas_plan.hpp)
+using hostlogic::CostasChain;
+using hostlogic::CostasPiece;
 template <int KV>
 __device__ __forceinline__ void costas_chains_body(const CostasChain* __restrict__ chains, unsigned n_chains,
                                                    const CostasPiece* __restrict__ pieces,
@@ -739,11 +709,7 @@ __global__ __attribute__((amdgpu_num_vgpr(16))) void k_costas_chains_cap(const C
 // =====================================================================================
 // SyncwordWipeoff (syncword_wipeoff.hpp:66-82): copy, then x[pos] *= syncword[pos] on spans
 // =====================================================================================
-struct WipeSpan {
-    unsigned long long start; // first item of the span inside this call
-    unsigned first;           // first syncword position
-    unsigned len;
-};
+using hostlogic::WipeSpan; // hostlogic/packet_control.hpp
 __global__ void k_wipe(const WipeSpan* __restrict__ spans, const float* __restrict__ syncword,
                        const cf* in, cf* out) // may be the same buffer
 {
@@ -1863,10 +1829,8 @@ unsigned grid_for(size_t n, unsigned block, unsigned cap = 65535u * 16u)
 using namespace gr4pm;
 
 // ------------------------------------------------------------------------ Rotator / CFC
-struct gr4pm_rotator {
-    int mode;
+struct gr4pm_rotator : gr4pm::hostlogic::RotHostState { // mode, delay, n_channels and what the tags carry: hostlogic/rotator_plan.hpp
     float phase_incr;
-    size_t delay, n_channels;
     hipStream_t stream;
     // [kStates][n_channels], st_cur selects the row a call reads; it writes the next one (round 6: a ring instead of two
     // halves -- the chain kernels of several plans are in flight at once, see PlanSync)
@@ -1920,18 +1884,6 @@ struct gr4pm_rotator {
     DevBuf<unsigned long long> mc_tab;
     DevBuf<SymWg> mc_wg;
     std::vector<unsigned long long> mc_host;
-    std::vector<float> next_freq;     // per channel, coarse_frequency_correction.hpp:44
-    std::vector<long> next_freq_delay; // :45
-    // Per channel: the carried phasor is a fixed point of the recurrence -- exp = (1, -+0) with incr = (1, -+0): every
-    // product e * incr gives e again and the renormalisation divides by hypot(1, 0) = 1.  That is the state of a
-    // CoarseFrequencyCorrection from start() to its first syncword_freq tag (set_freq(0) on the first item,
-    // coarse_frequency_correction.hpp:44-45,84-86), after every tag whose frequency is exactly 0, and of a Rotator with
-    // phase_incr 0: the stream the reference publishes its receiver benchmark on (zeros: no tag, ever) and every
-    // stream until its first detection.  Such a segment needs no serial chain: its checkpoints are the constant
-    // (k_rot_const_fill, parallel), the consumers multiply by it as before -- the same bits (x * (1, -0) is not a
-    // copy: it turns -0 into +0 in places, as the reference's multiplication does).
-    std::vector<uint8_t> fixed;
-    std::vector<cf> fixed_exp, fixed_incr;
 };
 
 // the handle's own streams idle (the chains of ring plans run there)
@@ -1960,12 +1912,7 @@ static gr4pm_status rotator_reset_impl(gr4pm_rotator* h)
                                  h->stream));
     GR4PM_HIP_TRY(hipStreamSynchronize(h->stream));
     h->st_cur = 0;
-    h->next_freq.assign(h->n_channels, 0.0f);
-    h->next_freq_delay.assign(h->n_channels, 0); // :45 -> set_freq(0) on the first item
-    // (a Rotator whose increment is (1, +-0) never leaves exp = (1, +0); a CFC starts with set_freq(0) on item 0)
-    h->fixed.assign(h->n_channels, h->mode == 0 && st[0].incr.x == 1.0f && st[0].incr.y == 0.0f ? 1 : 0);
-    h->fixed_exp.assign(h->n_channels, st[0].exp);
-    h->fixed_incr.assign(h->n_channels, st[0].incr);
+    hostlogic::rot_reset(*h, st[0].exp, st[0].incr);
     return GR4PM_OK;
 }
 
@@ -2023,126 +1970,28 @@ GR4PM_ABI_CATCH
 
 } // extern "C"
 
-// host replay of the tag-driven control flow + the serial phasor checkpoints; leaves the segment
+// host replay of the tag-driven control flow (hostlogic::rot_plan) + the serial phasor checkpoints; leaves the segment
 // table, checkpoints, increments and counters of this call on the device (h->plans[h->plan_cur])
 // ring: the plan goes to the next set of the ring (callers that keep several plans alive:
 // gr4pm_cfc_symbol_filter_plan*); otherwise the current set is reused.  When the ring is used for
 // the first time every set gets the capacity of the first plan, so that no later call of a
 // steady stream has to allocate.
-static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_tag* tags, const uint32_t* tag_channel,
-                                      size_t n_tags, std::vector<RotSeg>& segs, bool ring);
-// The host half of the carried state (pending frequency, fixed-point flags) is advanced while the segments are formed,
-// before the allocations, uploads and launches that can still fail: a call that fails leaves it as it found it, in step
-// with the device's RotState (st_cur flips only on success).
+// The host half of the carried state (pending frequency, fixed-point flags) comes back in rp.carried; the handle takes it
+// over, with plan_cur and st_cur, where this function returns GR4PM_OK -- behind the allocations, uploads and launches
+// that can still fail: a call that fails leaves all three as it found them, in step with the device's RotState.
 static gr4pm_status rotator_plan(gr4pm_rotator* h, size_t n, const gr4pm_tag* tags, const uint32_t* tag_channel,
-                                 size_t n_tags, std::vector<RotSeg>& segs, bool ring = false)
+                                 size_t n_tags, hostlogic::RotPlan& rp, bool ring = false)
 {
-    static thread_local std::vector<float> nf;
-    static thread_local std::vector<long> nd;
-    static thread_local std::vector<uint8_t> fx;
-    static thread_local std::vector<cf> fe, fi;
-    nf = h->next_freq, nd = h->next_freq_delay, fx = h->fixed, fe = h->fixed_exp, fi = h->fixed_incr;
-    const int plan_was = h->plan_cur;
-    gr4pm_status st;
-    try {
-        st = rotator_plan_impl(h, n, tags, tag_channel, n_tags, segs, ring);
-    } catch (...) {
-        h->next_freq.swap(nf), h->next_freq_delay.swap(nd), h->fixed.swap(fx), h->fixed_exp.swap(fe), h->fixed_incr.swap(fi);
-        h->plan_cur = plan_was;
-        throw;
-    }
-    if (st != GR4PM_OK) {
-        h->next_freq.swap(nf), h->next_freq_delay.swap(nd), h->fixed.swap(fx), h->fixed_exp.swap(fe), h->fixed_incr.swap(fi);
-        h->plan_cur = plan_was;
-    }
-    return st;
-}
-static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_tag* tags, const uint32_t* tag_channel,
-                                      size_t n_tags, std::vector<RotSeg>& segs, bool ring)
-{
-    unsigned ck = 0;
-    size_t n_const = 0;
-    for (size_t c = 0; c < h->n_channels; ++c) {
-        // set_freq events (item, freq) of this channel: coarse_frequency_correction.hpp:76-96
-        struct Ev {
-            size_t at;
-            float freq;
-        };
-        std::vector<Ev> evs;
-        bool pending = false;
-        size_t pending_at = 0;
-        float pending_freq = 0.0f;
-        if (h->mode == 1) {
-            if (h->next_freq_delay[c] >= 0) {
-                pending = true;
-                pending_at = static_cast<size_t>(h->next_freq_delay[c]);
-                pending_freq = h->next_freq[c];
-            }
-            for (size_t t = 0; t < n_tags; ++t) {
-                const size_t tc = tag_channel ? tag_channel[t] : 0;
-                if (tc != c || !(tags[t].flags & GR4PM_TAG_SYNCWORD) || tags[t].index >= n) continue;
-                const size_t i = static_cast<size_t>(tags[t].index);
-                // a countdown that has not reached zero when the next tag arrives is
-                // overwritten (:79-80 runs before the item loop of that chunk)
-                if (pending && pending_at < i) evs.push_back({ pending_at, pending_freq });
-                pending = true;
-                pending_at = i + h->delay;
-                pending_freq = static_cast<float>(tags[t].freq); // :79 cast to float
-            }
-            if (pending && pending_at < n) {
-                evs.push_back({ pending_at, pending_freq });
-                pending = false;
-            }
-            h->next_freq[c] = pending_freq;
-            h->next_freq_delay[c] = pending ? static_cast<long>(pending_at - n) : -1;
-        }
-        // pieces of this channel: [0, first event) continues the carried phasor; every event
-        // starts a piece with a fresh phasor (set_freq resets _exp and _counter, :55-58)
-        size_t pos = 0;
-        static const bool no_fixed = getenv("GR4PM_ROT_NO_FIXED_POINT") != nullptr; // A/B: every segment as a chain
-        auto push = [&](size_t start, size_t end, int mode, float freq) {
-            if (end <= start) return;
-            RotSeg g{};
-            g.start = start;
-            g.len = end - start;
-            g.channel = static_cast<unsigned>(c);
-            ck = (ck + 1u) & ~1u; // an even slot: 16-byte checkpoint stores without a test (k_rot_checkpoints_fresh)
-            g.ck0 = ck;
-            g.mode = mode;
-            g.last = 0;
-            if (mode == 1) { // set_freq(), :50-59 (float cos/sin of the host libm)
-                const float d = static_cast<float>(h->delay);
-                g.exp0 = { std::cos(freq * d), -std::sin(freq * d) };
-                g.incr = { std::cos(freq), -std::sin(freq) };
-                // exp0 = (1, -+0), incr = (1, -+0) (freq = +-0): e * incr == e for ever
-                h->fixed[c] = g.exp0.x == 1.0f && g.exp0.y == 0.0f && g.incr.x == 1.0f && g.incr.y == 0.0f;
-                h->fixed_exp[c] = g.exp0;
-                h->fixed_incr[c] = g.incr;
-            }
-            if (h->fixed[c] && !no_fixed) { // (mode 0: the carried phasor is the fixed point)
-                g.mode = 2;
-                g.exp0 = h->fixed_exp[c];
-                g.incr = h->fixed_incr[c];
-                n_const += 1;
-            }
-            ck += static_cast<unsigned>((g.len + kRotChunk - 1) / kRotChunk);
-            segs.push_back(g);
-        };
-        for (size_t k = 0; k < evs.size(); ++k) {
-            if (evs[k].at > pos) push(pos, evs[k].at, 0, 0.0f); // only possible for k == 0
-            const size_t end = k + 1 < evs.size() ? evs[k + 1].at : n;
-            push(evs[k].at, end, 1, evs[k].freq);
-            pos = end;
-        }
-        if (pos < n) push(pos, n, 0, 0.0f);
-        segs.back().last = 1; // the channel's final piece writes the carried state
-    }
+    static const bool no_fixed = getenv("GR4PM_ROT_NO_FIXED_POINT") != nullptr; // A/B: every segment as a chain
+    static const bool no_sort = gr4pm::experiment_env("GR4PM_ROT_NO_SORT", false) != nullptr;
+    hostlogic::rot_plan(*h, n, tags, tag_channel, n_tags, no_fixed, no_sort, rp);
+    const std::vector<RotSeg>& segs = rp.segs;
+    const unsigned ck = rp.ck_total;
+    const size_t n_const = rp.const_list.size();
     hipStream_t s = h->stream;
     const unsigned n_segs = static_cast<unsigned>(segs.size());
-    unsigned ck_total = 0;
-    for (const auto& g : segs) ck_total = std::max<unsigned>(ck_total, g.ck0 + static_cast<unsigned>((g.len + kRotChunk - 1) / kRotChunk));
+    const int plan = ring ? (h->plan_cur + 1) % GR4PM_CFC_PLANS : h->plan_cur;
     if (ring) {
-        h->plan_cur = (h->plan_cur + 1) % GR4PM_CFC_PLANS;
         if (!h->ring_sized) {
             h->ring_sized = true;
             for (auto& q : h->plans) {
@@ -2160,55 +2009,22 @@ static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_ta
             }
         }
     }
-    auto& pl = h->plans[h->plan_cur];
+    auto& pl = h->plans[plan];
     pl.n_segs = n_segs;
     pl.n_in = n;
-    pl.seg_first.assign(h->n_channels + 1, n_segs); // segments were generated channel by channel
-    for (unsigned i = n_segs; i-- > 0;) pl.seg_first[segs[i].channel] = i;
-    for (size_t c = h->n_channels; c-- > 0;) pl.seg_first[c] = std::min(pl.seg_first[c], pl.seg_first[c + 1]);
+    pl.seg_first = rp.seg_first;
     GR4PM_TRY(upload_vec(pl.segs, segs, s));
     if (pl.ck.n < ck) GR4PM_TRY(pl.ck.alloc(static_cast<size_t>(ck) * 2));
     if (pl.seg_incr.n < n_segs) {
         GR4PM_TRY(pl.seg_incr.alloc(n_segs * 2));
         GR4PM_TRY(pl.seg_counter0.alloc(n_segs * 2));
     }
-    // order[]: first the segments that depend on nothing before this call (a set_freq event starts them, or they are fixed
-    // points), then the ones that continue the carried phasor (mode 0: at most one per channel); each part by descending
-    // length, so that the long ones (a stream with missed detections) share waves
-    unsigned n_indep = 0, n_writer = 0;
-    bool dep_writes_state = false;
-    {
-        // ONE sort over 64-bit keys (part | longest first | position): this runs in the pipeline stage that makes the plans,
-        // 10 000 segments a batch -- two stable sorts with indirect comparisons were half a millisecond of that stage
-        static thread_local std::vector<unsigned> order;
-        static thread_local std::vector<unsigned long long> keys;
-        static const bool no_sort = gr4pm::experiment_env("GR4PM_ROT_NO_SORT", false) != nullptr;
-        auto part = [&](unsigned a) { return segs[a].mode == 0 ? 2u : segs[a].last ? 1u : 0u; }; // indep | writer | dep
-        keys.resize(n_segs);
-        for (unsigned i = 0; i < n_segs; ++i) {
-            const unsigned pt = part(i);
-            n_indep += pt == 0;
-            n_writer += pt == 1;
-            dep_writes_state |= pt == 2 && segs[i].last;
-            // (a segment is shorter than 2^36 items -- 2^33 checkpoint slots are 32-bit --, a call has fewer than 2^26 segments)
-            const unsigned long long by_len = no_sort ? 0ull : (~segs[i].len & ((1ull << 36) - 1));
-            keys[i] = (static_cast<unsigned long long>(pt) << 62) | (by_len << 26) | i;
-        }
-        std::sort(keys.begin(), keys.end());
-        order.resize(n_segs);
-        for (unsigned i = 0; i < n_segs; ++i) order[i] = static_cast<unsigned>(keys[i] & ((1u << 26) - 1));
-        GR4PM_TRY(upload_vec(pl.order, order, s));
-    }
-    if (n_const) {
-        static thread_local std::vector<unsigned> list;
-        list.clear();
-        for (unsigned i = 0; i < n_segs; ++i)
-            if (segs[i].mode == 2) list.push_back(i);
-        GR4PM_TRY(upload_vec(pl.const_list, list, s));
-    }
-    unsigned long long longest_const = 0;
-    for (unsigned i = 0; i < n_segs; ++i)
-        if (segs[i].mode == 2) longest_const = std::max(longest_const, segs[i].len);
+    // order[]: indep | writer | dep, each part by descending length (hostlogic::RotPlan)
+    const unsigned n_indep = rp.n_indep, n_writer = rp.n_writer;
+    const bool dep_writes_state = rp.dep_writes_state;
+    GR4PM_TRY(upload_vec(pl.order, rp.order, s));
+    if (n_const) GR4PM_TRY(upload_vec(pl.const_list, rp.const_list, s));
+    const unsigned long long longest_const = rp.longest_const;
     const RotState* st_in = h->state.p + static_cast<size_t>(h->st_cur) * h->n_channels;
     const int st_next = (h->st_cur + 1) % gr4pm_rotator::kStates;
     RotState* st_out = h->state.p + static_cast<size_t>(st_next) * h->n_channels;
@@ -2244,11 +2060,9 @@ static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_ta
     // (tests: GR4PM_TEST_ROT_DELAY_US holds every chain kernel of such a plan back by that long, so that a consumer that
     // does not wait for the plan's events reads checkpoints that are not there yet)
     const unsigned test_delay_us = h->test_delay_us;
-    unsigned long long longest_chain = 0;
-    for (unsigned i = 0; i < n_segs; ++i)
-        if (segs[i].mode != 2) longest_chain = std::max(longest_chain, segs[i].len);
+    const unsigned long long longest_chain = rp.longest_chain;
     const bool side_by_side = ring && (h->async_policy > 0 || (h->async_policy == 0 && longest_chain >= gr4pm_rotator::kAsyncMinItems));
-    auto& sy = h->sync[h->plan_cur];
+    auto& sy = h->sync[plan];
     if (side_by_side) {
         if (!h->async_ready) { // the handle's own streams (at the priority of the one it was given) and the plans' events
             int prio = 0;
@@ -2263,7 +2077,7 @@ static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_ta
             h->async_ready = true;
         }
         constexpr int K = gr4pm_rotator::kAux;
-        const int turn = h->plan_cur % K;
+        const int turn = plan % K;
         hipStream_t s_indep = h->aux[turn], s_writer = h->aux[K + turn], s_dep = h->aux[2 * K + turn];
         GR4PM_HIP_TRY(hipEventRecord(sy.up, s)); // tables of this plan on the device, and everything `s` carried before
         GR4PM_HIP_TRY(hipStreamWaitEvent(s_indep, sy.up, 0));
@@ -2287,7 +2101,7 @@ static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_ta
         GR4PM_HIP_TRY(hipEventRecord(sy.dep, s_dep));
         sy.async = true;
         sy.dep_writes_state = dep_writes_state;
-        h->last_async_plan = h->plan_cur;
+        h->last_async_plan = plan;
     } else {
         if (h->last_async_plan >= 0) { // (a plain call behind ring plans: their kernels wrote the state this one reads)
             GR4PM_HIP_TRY(hipStreamWaitEvent(s, h->sync[h->last_async_plan].writer, 0));
@@ -2299,6 +2113,8 @@ static gr4pm_status rotator_plan_impl(gr4pm_rotator* h, size_t n, const gr4pm_ta
         sy.async = false;
     }
     GR4PM_HIP_TRY(hipGetLastError());
+    std::swap(h->carried, rp.carried);
+    h->plan_cur = plan;
     h->st_cur = st_next;
     return GR4PM_OK;
 }
@@ -2315,8 +2131,9 @@ try {
         set_error("null sample pointer");
         return GR4PM_ERR_INVALID;
     }
-    std::vector<RotSeg> segs;
-    GR4PM_TRY(rotator_plan(h, n, tags, tag_channel, n_tags, segs));
+    static thread_local hostlogic::RotPlan rp; // (its vectors keep their capacity from call to call)
+    GR4PM_TRY(rotator_plan(h, n, tags, tag_channel, n_tags, rp));
+    const std::vector<RotSeg>& segs = rp.segs;
     hipStream_t s = h->stream;
     const unsigned n_segs = static_cast<unsigned>(segs.size());
     {
@@ -2341,19 +2158,9 @@ GR4PM_ABI_CATCH
 } // extern "C"
 
 // ------------------------------------------------------------------------ CostasLoop
-struct gr4pm_costas_loop {
-    double loop_bandwidth;
-    int constellation;
-    float k1, k2;
+struct gr4pm_costas_loop : gr4pm::hostlogic::CostasHostState { // the settings and their coefficients: hostlogic/costas_plan.hpp
     size_t n_channels;
     hipStream_t stream;
-    struct Memo {
-        bool valid = false;
-        double bw = 0.0;
-        int constellation = 0;
-        float k1 = 0.0f, k2 = 0.0f;
-    } memo[4];
-    unsigned memo_next = 0;
     DevBuf<CostasState> state; // [2][n_channels], st_cur selects the current half
     int st_cur = 0;
     int small_footprint = 0; // 0: k_costas<C, 8> (112 VGPRs, fastest alone), 1: k_costas<C, 2> (62), 2: k_costas_cap<C, 2> (32)
@@ -2361,32 +2168,7 @@ struct gr4pm_costas_loop {
     DevBuf<CostasChain> chains;
     DevBuf<CostasPiece> pieces;
 };
-
-static void costas_coeffs(gr4pm_costas_loop* h)
-{
-    // tag-driven settings alternate between a handful of (bandwidth, constellation) pairs, three
-    // times per packet: remember the last few results instead of redoing the cube roots
-    for (const auto& m : h->memo)
-        if (m.valid && m.bw == h->loop_bandwidth && m.constellation == h->constellation) {
-            h->k1 = m.k1;
-            h->k2 = m.k2;
-            return;
-        }
-    // settingsChanged(), costas_loop.hpp:62-87
-    double gain = 1.0;
-    if (h->constellation == 2) gain = 1.41421356237309504880;
-    const double bw = h->loop_bandwidth, bw2 = bw * bw, bw3 = bw2 * bw, bw4 = bw2 * bw2;
-    const double s = std::cbrt(36.0 * bw2 +
-                               std::sqrt(3.0) * std::sqrt(432.0 * bw4 + 848.0 * bw3 + 624.0 * bw2 +
-                                                          204.0 * bw + 25.0) +
-                               36.0 * bw + 9.0);
-    const double z = -(-12.0 * bw - 6.0) / (3.0 * std::cbrt(6.0) * (2.0 * bw + 1.0) * s) +
-                     (std::cbrt(2.0) * s) / (std::cbrt(9.0) * (2.0 * bw + 1.0)) - 1.0;
-    h->k1 = static_cast<float>((1.0 - z * z) / gain);
-    h->k2 = static_cast<float>(((1.0 - z) * (1.0 - z)) / gain);
-    auto& slot = h->memo[h->memo_next++ % 4];
-    slot = { true, h->loop_bandwidth, h->constellation, h->k1, h->k2 };
-}
+using hostlogic::costas_coeffs;
 
 extern "C" {
 
@@ -2402,7 +2184,7 @@ try {
     h->constellation = p->constellation;
     h->n_channels = p->n_channels;
     h->stream = static_cast<hipStream_t>(p->stream);
-    costas_coeffs(h);
+    costas_coeffs(*h);
     gr4pm_status s = h->state.alloc(static_cast<size_t>(gr4pm_rotator::kStates) * h->n_channels);
     if (s == GR4PM_OK) s = h->state.zero(h->stream);
     if (s == GR4PM_OK && hipStreamSynchronize(h->stream) != hipSuccess) s = GR4PM_ERR_HIP;
@@ -2444,7 +2226,7 @@ try {
     if (!h || constellation < 0 || constellation > 2) return GR4PM_ERR_INVALID;
     h->loop_bandwidth = loop_bandwidth;
     h->constellation = constellation;
-    costas_coeffs(h);
+    costas_coeffs(*h);
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -2456,52 +2238,11 @@ static gr4pm_status costas_process_impl(gr4pm_costas_loop* h, const gr4pm_c64* i
                                         gr4pm_c64* out, const gr4pm_tag* tags, const uint32_t* tag_channel,
                                         size_t n_tags)
 {
-    std::vector<CostasSeg> segs;
-    for (size_t c = 0; c < h->n_channels; ++c) {
-        const size_t n = n_of(c);
-        if (n == 0) { // a piece of length 0 that only hands the carried state on to the other slot
-            CostasSeg g{};
-            g.channel = static_cast<unsigned>(c);
-            g.last = 1;
-            segs.push_back(g);
-            continue;
-        }
-        size_t pos = 0;
-        int mode = 0;
-        float phase0 = 0.0f;
-        auto push = [&](size_t end) {
-            if (end <= pos) return;
-            CostasSeg g{};
-            g.start = pos;
-            g.len = static_cast<unsigned>(end - pos);
-            g.channel = static_cast<unsigned>(c);
-            g.mode = mode;
-            g.phase0 = phase0;
-            g.last = 0;
-            segs.push_back(g);
-            pos = end;
-        };
-        for (size_t t = 0; t < n_tags; ++t) {
-            const size_t tc = tag_channel ? tag_channel[t] : 0;
-            if (tc != c || !(tags[t].flags & GR4PM_TAG_SYNCWORD) || tags[t].index >= n) continue;
-            const size_t i = static_cast<size_t>(tags[t].index);
-            push(i);
-            if (i == pos) { // set_phase at the head of the chunk, costas_loop.hpp:101-106
-                mode = 1;
-                phase0 = tags[t].phase;
-            }
-        }
-        push(n);
-        if (!segs.empty() && segs.back().channel == c) segs.back().last = 1;
-    }
-    hipStream_t s = h->stream;
-    // A wave lives as long as its longest lane.  Segments are independent of one another (carried state travels through
-    // the ping-pong state array, not through their order), so the longest ones are put together: a stream with missed
-    // detections (segments that run through several packets: 64 channels of configs[2] hold ~80 of five packets'
-    // length among 9700) then keeps two waves alive for the long tail instead of eighty.
+    // one lane per segment, the longest ones together (hostlogic::costas_segments)
     static const bool costas_no_sort = gr4pm::experiment_env("GR4PM_COSTAS_NO_SORT", false) != nullptr;
-    if (!costas_no_sort)
-        std::stable_sort(segs.begin(), segs.end(), [](const CostasSeg& a, const CostasSeg& b) { return a.len > b.len; });
+    std::vector<CostasSeg> segs;
+    hostlogic::costas_segments(h->n_channels, n_of, tags, tag_channel, n_tags, costas_no_sort, segs);
+    hipStream_t s = h->stream;
     GR4PM_TRY(upload_vec(h->segs, segs, s));
     if (timing_skip("seg_stats")) { // GR4PM_TIMING_SKIP=seg_stats: what the serial kernel is given
         size_t longest = 0, total = 0;
@@ -2622,79 +2363,11 @@ gr4pm_status gr4pm::costas_loop_process_packets_from(gr4pm_costas_loop* h, const
         set_error("null sample pointer");
         return GR4PM_ERR_INVALID;
     }
+    // (the settings follow the tags inside: a refused call leaves those of the tags in front of the refusal applied)
     std::vector<CostasChain> chains;
     std::vector<CostasPiece> pieces;
-    CostasChain cur{};
-    cur.piece0 = 0;
-    cur.mode = 0;
-    size_t pos = 0;
-    size_t span_at = 0; // cursor into spans (pieces are closed in ascending order)
-    auto close_piece = [&](size_t end) {
-        while (pos < end) {
-            size_t stop = end;
-            long long in_off = 0;
-            if (spans) {
-                while (span_at < n_spans && spans[span_at].dst + spans[span_at].len <= pos) ++span_at;
-                if (span_at >= n_spans || spans[span_at].dst > pos) { // (a hole in the table: the caller's error)
-                    pos = end;
-                    span_at = n_spans + 1;
-                    return;
-                }
-                stop = std::min<size_t>(end, spans[span_at].dst + spans[span_at].len);
-                in_off = static_cast<long long>(spans[span_at].src) - static_cast<long long>(spans[span_at].dst);
-            }
-            while (pos < stop) { // (len is 32 bits wide)
-                const size_t m = std::min<size_t>(stop - pos, 1u << 30);
-                CostasPiece pc{};
-                pc.start = pos;
-                pc.in_off = in_off;
-                pc.len = static_cast<unsigned>(m);
-                pc.constellation = h->constellation;
-                pc.k1 = h->k1;
-                pc.k2 = h->k2;
-                pieces.push_back(pc);
-                pos += m;
-            }
-        }
-    };
-    auto close_chain = [&]() {
-        cur.n_pieces = static_cast<unsigned>(pieces.size()) - cur.piece0;
-        if (cur.n_pieces) chains.push_back(cur);
-        cur = CostasChain{};
-        cur.piece0 = static_cast<unsigned>(pieces.size());
-    };
-    for (size_t t = 0; t < n_tags; ++t) {
-        if (tags[t].index >= n) break;
-        close_piece(static_cast<size_t>(tags[t].index));
-        // keys naming settings are applied before the chunk, then settingsChanged(), :52-88
-        bool changed = false;
-        if (tags[t].constellation >= 0) {
-            if (tags[t].constellation > 2) {
-                set_error("constellation %d", tags[t].constellation);
-                return GR4PM_ERR_INVALID;
-            }
-            h->constellation = tags[t].constellation;
-            changed = true;
-        }
-        if (tags[t].loop_bandwidth >= 0.0) {
-            h->loop_bandwidth = tags[t].loop_bandwidth;
-            changed = true;
-        }
-        if (changed) costas_coeffs(h);
-        if (tags[t].kind == GR4PM_PKT_SYNCWORD && (tags[t].syncword.flags & GR4PM_TAG_SYNCWORD)) { // :101-106
-            close_chain();
-            cur.mode = 1;
-            cur.phase0 = tags[t].syncword.phase;
-        }
-    }
-    close_piece(n);
-    close_chain();
-    if (span_at > n_spans) {
-        set_error("process_packets: the span table does not cover the stream");
-        return GR4PM_ERR_INVALID;
-    }
+    GR4PM_TRY(hostlogic::costas_packet_chains(*h, spans, n_spans, n, tags, n_tags, chains, pieces));
     if (chains.empty()) return GR4PM_OK;
-    chains.back().last = 1;
     hipStream_t s = h->stream;
     GR4PM_TRY(upload_vec(h->chains, chains, s));
     GR4PM_TRY(upload_vec(h->pieces, pieces, s));
@@ -2718,14 +2391,13 @@ gr4pm_status gr4pm::costas_loop_process_packets_from(gr4pm_costas_loop* h, const
 }
 
 // ------------------------------------------------------------------------ SyncwordWipeoff
-struct gr4pm_syncword_wipeoff {
+struct gr4pm_syncword_wipeoff : gr4pm::hostlogic::WipeState { // the state machine: hostlogic/packet_control.hpp
     std::vector<float> syncword;
     hipStream_t stream;
     DevBuf<float> d_syncword;
     DevBuf<WipeSpan> spans;
-    bool in_syncword = false; // syncword_wipeoff.hpp:27-28
-    size_t position = 0;
 };
+using hostlogic::wipe_replay;
 
 extern "C" {
 
@@ -2738,6 +2410,7 @@ try {
     auto* h = new (std::nothrow) gr4pm_syncword_wipeoff;
     if (!h) return GR4PM_ERR_NOMEM;
     h->syncword.assign(p->syncword, p->syncword + p->n_syncword);
+    h->syncword_size = p->n_syncword;
     h->stream = static_cast<hipStream_t>(p->stream);
     gr4pm_status s = h->d_syncword.alloc(p->n_syncword);
     if (s == GR4PM_OK) s = h->d_syncword.upload(h->syncword.data(), h->syncword.size(), h->stream);
@@ -2767,37 +2440,6 @@ try {
 GR4PM_ABI_CATCH
 
 } // extern "C"
-
-// replay of syncword_wipeoff.hpp:53-75 over the tag list of one call: the spans of the syncword inside it
-// (base: offset of the channel's item 0 in the buffer the kernel indexes)
-static void wipe_replay(gr4pm_syncword_wipeoff* h, size_t n, const gr4pm_tag* tags, size_t n_tags, size_t base,
-                        std::vector<WipeSpan>& spans)
-{
-    size_t pos = 0, t = 0;
-    const size_t L = h->syncword.size();
-    while (pos < n) {
-        while (t < n_tags && tags[t].index < pos) ++t;
-        const bool has_tag = t < n_tags && tags[t].index == pos && (tags[t].flags & GR4PM_TAG_SYNCWORD);
-        if (!h->in_syncword && has_tag) {
-            h->in_syncword = true;
-            h->position = 0;
-        }
-        size_t end = n;
-        for (size_t u = t; u < n_tags; ++u)
-            if (tags[u].index > pos) {
-                end = std::min<size_t>(end, tags[u].index);
-                break;
-            }
-        if (h->in_syncword) {
-            const size_t m = std::min(end - pos, L - h->position);
-            spans.push_back({ base + pos, static_cast<unsigned>(h->position), static_cast<unsigned>(m) });
-            h->position += m;
-            if (h->position == L) h->in_syncword = false;
-        }
-        pos = end;
-        if (t < n_tags && tags[t].index < pos) ++t;
-    }
-}
 
 extern "C" {
 
@@ -2836,7 +2478,7 @@ try {
         return GR4PM_ERR_INVALID;
     }
     std::vector<WipeSpan> spans;
-    wipe_replay(h, n, tags, n_tags, 0, spans);
+    wipe_replay(*h, n, tags, n_tags, 0, spans);
     hipStream_t s = h->stream;
     if (in != out) // in place: only the syncword spans are touched
         hipLaunchKernelGGL(k_copy<cf>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s,
@@ -2867,7 +2509,7 @@ try {
             set_error("a launch that spans channels needs wipe-off blocks of one syncword and n <= stride");
             return GR4PM_ERR_INVALID;
         }
-        wipe_replay(h[c], n[c], tags[c], n_tags[c], c * stride, spans);
+        wipe_replay(*h[c], n[c], tags[c], n_tags[c], c * stride, spans);
     }
     hipStream_t s = h[0]->stream;
     if (!spans.empty()) {
@@ -3275,8 +2917,8 @@ static gr4pm_status cfc_plan_impl(gr4pm_rotator* cfc, size_t n_in, const gr4pm_t
         return GR4PM_ERR_INVALID;
     }
     if (n_in == 0) return GR4PM_OK;
-    std::vector<RotSeg> segs;
-    GR4PM_TRY(rotator_plan(cfc, n_in, tags_in, tag_channel, n_tags_in, segs, ring)); // checkpoints on the CFC's stream
+    static thread_local hostlogic::RotPlan rp; // (its vectors keep their capacity from call to call)
+    GR4PM_TRY(rotator_plan(cfc, n_in, tags_in, tag_channel, n_tags_in, rp, ring)); // checkpoints on the CFC's stream
     *plan = cfc->plan_cur;
     GR4PM_HIP_TRY(final_sync(cfc->stream));
     return GR4PM_OK;
@@ -3717,11 +3359,7 @@ gr4pm_status launch_gather(hipStream_t s, DevBuf<CopySpan>& buf, const std::vect
 
 // LLR mapping of one run of symbols with one constellation: BPSK scale * re, QPSK
 // (scale * re, scale * im) = a scaled copy of the interleaved floats
-struct LlrRun {
-    unsigned long long in0, out0, n_out;
-    int qpsk;
-    int pad;
-};
+using hostlogic::LlrRun; // hostlogic/packet_control.hpp
 __global__ __launch_bounds__(256) void k_llr(const LlrRun* __restrict__ runs, float scale,
                                              const float* __restrict__ in, float* __restrict__ out)
 {
@@ -3744,64 +3382,13 @@ struct gr4pm_syncword_remove : gr4pm::hostlogic::SrState {
     hipStream_t stream = nullptr;
     DevBuf<gr4pm::hostlogic::CopySpan> spans;
 };
-struct gr4pm_constellation_llr_decoder {
+struct gr4pm_constellation_llr_decoder : gr4pm::hostlogic::LlrState { // the constellation follows the tags: hostlogic/packet_control.hpp
     float noise_sigma, scale;
-    int constellation;
     hipStream_t stream;
     DevBuf<LlrRun> runs;
 };
 
-// the host half of ConstellationLLRDecoder::processBulk over one call (constellation_llr_decoder.hpp:84-130): runs of
-// symbols with one constellation, the tags re-indexed to LLR positions (:93-99); the block's constellation follows the tags
-static gr4pm_status llr_runs(gr4pm_constellation_llr_decoder* h, size_t n, size_t out_cap, const gr4pm_packet_tag* tags_in,
-                             size_t n_tags_in, gr4pm_packet_tag* tags_out, size_t tags_cap, size_t* n_tags_out, size_t* produced,
-                             std::vector<gr4pm::LlrRun>& runs)
-{
-    using gr4pm::LlrRun;
-    size_t pos = 0, opos = 0, n_pub = 0;
-    bool tag_overflow = false;
-    auto close_run = [&](size_t end) {
-        if (end <= pos) return;
-        LlrRun r{};
-        r.in0 = pos;
-        r.out0 = opos;
-        r.qpsk = h->constellation == 2;
-        r.n_out = (end - pos) * (r.qpsk ? 2 : 1);
-        runs.push_back(r);
-        opos += r.n_out;
-        pos = end;
-    };
-    for (size_t t = 0; t < n_tags_in; ++t) {
-        if (tags_in[t].index >= n) break;
-        close_run(static_cast<size_t>(tags_in[t].index));
-        if (tags_in[t].constellation >= 0) {
-            if (tags_in[t].constellation != 1 && tags_in[t].constellation != 2) {
-                gr4pm::set_error("constellation %d not supported", tags_in[t].constellation);
-                return GR4PM_ERR_INVALID;
-            }
-            h->constellation = tags_in[t].constellation;
-        }
-        if (tags_out && n_pub < tags_cap) { // :93-99
-            tags_out[n_pub] = tags_in[t];
-            tags_out[n_pub].index = opos;
-        } else {
-            tag_overflow = true;
-        }
-        ++n_pub;
-    }
-    close_run(n);
-    if (opos > out_cap) {
-        gr4pm::set_error("out_cap %zu < %zu LLRs", out_cap, opos);
-        return GR4PM_INSUFFICIENT_OUTPUT_ITEMS;
-    }
-    *produced = opos;
-    if (n_tags_out) *n_tags_out = n_pub;
-    if (tag_overflow) {
-        gr4pm::set_error("tags_cap too small");
-        return GR4PM_ERR_OVERFLOW;
-    }
-    return GR4PM_OK;
-}
+using gr4pm::hostlogic::llr_runs;
 // (library-internal) PayloadMetadataInsert::processBulk's host half: the state machine over the tags (hostlogic/packet_control.hpp)
 gr4pm_status gr4pm::payload_metadata_insert_plan(gr4pm_payload_metadata_insert* h, size_t n_in, size_t out_cap,
                                                  const gr4pm_tag* tags_in, size_t n_tags_in, const gr4pm_header_msg* headers,
@@ -3857,7 +3444,7 @@ gr4pm_status gr4pm::llr_decoder_plan(gr4pm_constellation_llr_decoder* h, size_t 
     std::vector<LlrRun> runs;
     *produced = 0;
     if (n_tags_out) *n_tags_out = 0;
-    const gr4pm_status st = llr_runs(h, n, static_cast<size_t>(-1), tags_in, n_tags_in, tags_out, tags_cap, n_tags_out, produced, runs);
+    const gr4pm_status st = llr_runs(*h, n, static_cast<size_t>(-1), tags_in, n_tags_in, tags_out, tags_cap, n_tags_out, produced, runs);
     *all_qpsk = true;
     for (const auto& r : runs) *all_qpsk = *all_qpsk && r.qpsk;
     *scale = h->scale;
@@ -4027,7 +3614,7 @@ try {
         return GR4PM_ERR_INVALID;
     }
     std::vector<LlrRun> runs;
-    const gr4pm_status st = llr_runs(h, n, out_cap, tags_in, n_tags_in, tags_out, tags_cap, n_tags_out, produced, runs);
+    const gr4pm_status st = llr_runs(*h, n, out_cap, tags_in, n_tags_in, tags_out, tags_cap, n_tags_out, produced, runs);
     if (st != GR4PM_OK && st != GR4PM_ERR_OVERFLOW) return st;
     GR4PM_TRY(upload_vec(h->runs, runs, h->stream));
     unsigned long long longest = 0;

@@ -19,7 +19,9 @@
 #include <vector>
 
 #include "gr4pm_oracle.h"
+#include "hostlogic/costas_plan.hpp"
 #include "hostlogic/packet_control.hpp"
+#include "hostlogic/rotator_plan.hpp"
 #include "hostlogic/sdf_gate.hpp"
 #include "hostlogic/slot_queue.hpp"
 #include "hostlogic/symbol_filter_replay.hpp"
@@ -804,18 +806,578 @@ static void tail_refusals()
           "a run cut into 2^30-symbol pieces was refused or cut wrongly (%zu pieces)", out.size());
 }
 
+// ---------------------------------------------------------------- the stream blocks' tag-driven planners
+// tags of one channel at ragged distances -- now and then exactly `exact` items apart (a CoarseFrequencyCorrection's
+// delay: the tag arrives on the item its predecessor's countdown ends on) --: syncword tags with a phase and a frequency
+// (exactly +-0 among them, and ones so small that cos(f) == 1 while sin(f) != 0), now and then one that carries other
+// keys only (the planners cut chunks there and nothing else)
+static std::vector<gr4pm_tag> ragged_tags(std::mt19937_64& rng, size_t n, size_t far, size_t near, size_t exact = 0)
+{
+    std::normal_distribution<float> g(0.f, 1.f);
+    std::vector<gr4pm_tag> tags;
+    for (uint64_t p = rng() % (far / 4 + 1); p < n; p += exact && rng() % 5 == 0 ? exact : 1 + rng() % (rng() % 3 ? far : near)) {
+        gr4pm_tag t{};
+        t.index = p;
+        t.amplitude = 1.f;
+        t.phase = g(rng);
+        const unsigned kind = static_cast<unsigned>(rng() % 8);
+        t.freq = kind < 2 ? (kind ? 0.0 : -0.0) : (kind == 2 ? 1e-5 : 0.02) * static_cast<double>(g(rng));
+        t.flags = (rng() % 7 == 0) ? GR4PM_TAG_OTHER : GR4PM_TAG_SYNCWORD;
+        tags.push_back(t);
+    }
+    return tags;
+}
+// the tags of [pos, pos + m), indices relative to pos
+static void tags_of_call(const std::vector<gr4pm_tag>& all, size_t pos, size_t m, uint32_t channel, std::vector<gr4pm_tag>& tin,
+                         std::vector<uint32_t>& tch)
+{
+    for (auto t : all)
+        if (t.index >= pos && t.index < pos + m) {
+            t.index -= pos;
+            tin.push_back(t);
+            tch.push_back(channel);
+        }
+}
+static void syncword_tags(const std::vector<gr4pm_tag>& all, std::vector<uint64_t>& index, std::vector<double>* freq, std::vector<float>* phase)
+{
+    for (const auto& t : all)
+        if (t.flags & GR4PM_TAG_SYNCWORD) {
+            index.push_back(t.index);
+            if (freq) freq->push_back(t.freq);
+            if (phase) phase->push_back(t.phase);
+        }
+}
+static cf cmul_cf(cf a, cf b) { return { a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x }; }
+static bool same_rot_tables(const RotPlan& a, const RotPlan& b)
+{
+    return a.segs.size() == b.segs.size() && (a.segs.empty() || std::memcmp(a.segs.data(), b.segs.data(), a.segs.size() * sizeof(RotSeg)) == 0) &&
+           a.seg_first == b.seg_first && a.order == b.order && a.const_list == b.const_list && a.n_indep == b.n_indep &&
+           a.n_writer == b.n_writer && a.dep_writes_state == b.dep_writes_state && a.longest_chain == b.longest_chain &&
+           a.longest_const == b.longest_const && a.ck_total == b.ck_total;
+}
+static bool same_carried(const RotCarried& a, const RotCarried& b)
+{
+    auto eq = [](const std::vector<cf>& u, const std::vector<cf>& v) {
+        return u.size() == v.size() && (u.empty() || std::memcmp(u.data(), v.data(), u.size() * sizeof(cf)) == 0);
+    };
+    return a.next_freq.size() == b.next_freq.size() &&
+           (a.next_freq.empty() || std::memcmp(a.next_freq.data(), b.next_freq.data(), a.next_freq.size() * sizeof(float)) == 0) &&
+           a.next_freq_delay == b.next_freq_delay && a.fixed == b.fixed && eq(a.fixed_exp, b.fixed_exp) && eq(a.fixed_incr, b.fixed_incr);
+}
+
+// Rotator / CoarseFrequencyCorrection: the segment table applied with a plain loop (what k_rot_checkpoints* and the
+// consumers of the checkpoints compute together) against the oracle's block run over the whole stream in one call
+static void rotator_plans(std::mt19937_64& rng)
+{
+    std::normal_distribution<float> g(0.f, 1.f);
+    RotHostState h;
+    h.mode = rng() % 4 ? 1 : 0;
+    h.n_channels = 1 + rng() % 4;
+    h.delay = h.mode == 1 && rng() % 2 ? 1 + rng() % 300 : 0;
+    const float phase_incr = rng() % 2 ? 0.0f : 0.05f * g(rng);
+    const bool no_fixed = rng() % 2, no_sort = rng() % 4 == 0;
+    const size_t C = h.n_channels, n = 20000 + rng() % 3000;
+    struct St {
+        cf exp, incr;
+        unsigned counter;
+    };
+    std::vector<St> st(C); // the device's RotState, as gr4pm_rotator_reset leaves it
+    for (auto& s : st) s = { { 1.0f, 0.0f }, h.mode == 0 ? cf{ std::cos(phase_incr), std::sin(phase_incr) } : cf{ 1.0f, 0.0f }, 0 };
+    rot_reset(h, st[0].exp, st[0].incr);
+    std::vector<std::vector<c64>> x(C), got(C);
+    std::vector<std::vector<gr4pm_tag>> tags(C);
+    for (size_t c = 0; c < C; ++c) {
+        x[c] = noise(rng, n);
+        got[c].assign(n, c64{ -1, -1 });
+        tags[c] = ragged_tags(rng, n, 3000, 40, h.delay); // (near: closer than most delays -- the countdown is overwritten)
+    }
+    RotPlan plans[2];
+    size_t pos = 0;
+    for (int call = 0; pos < n; ++call) {
+        const size_t m = std::min<size_t>(n - pos, 1 + rng() % (rng() % 3 ? 6000 : 300));
+        std::vector<gr4pm_tag> tin;
+        std::vector<uint32_t> tch;
+        for (size_t c = 0; c < C; ++c) tags_of_call(tags[c], pos, m, static_cast<uint32_t>(c), tin, tch);
+        if (rng() % 2) { // the channels' tags interleaved, each channel's still ascending
+            std::vector<size_t> idx(tin.size());
+            for (size_t i = 0; i < idx.size(); ++i) idx[i] = i;
+            std::stable_sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return tin[a].index < tin[b].index; });
+            std::vector<gr4pm_tag> t2;
+            std::vector<uint32_t> c2;
+            for (size_t i : idx) t2.push_back(tin[i]), c2.push_back(tch[i]);
+            tin.swap(t2), tch.swap(c2);
+        }
+        const uint32_t* tag_channel = C == 1 && rng() % 2 ? nullptr : tch.data();
+        // a call whose result is thrown away (a failed upload or launch), then the call again: the same tables, the
+        // handle's state untouched in between
+        RotPlan& thrown = plans[call & 1];
+        RotPlan& rp = plans[(call & 1) ^ 1];
+        const RotCarried before = h.carried;
+        rot_plan(h, m, tin.data(), tag_channel, tin.size(), no_fixed, no_sort, thrown);
+        CHECK(same_carried(h.carried, before), "rotator call at %zu: the planner changed the carried state", pos);
+        rot_plan(h, m, tin.data(), tag_channel, tin.size(), no_fixed, no_sort, rp);
+        CHECK(same_rot_tables(thrown, rp) && same_carried(thrown.carried, rp.carried), "rotator call at %zu: the repeated call gives other tables", pos);
+        // what the launches rely on
+        const unsigned n_segs = static_cast<unsigned>(rp.segs.size());
+        CHECK(rp.seg_first.size() == C + 1 && rp.seg_first[0] == 0 && rp.seg_first[C] == n_segs, "rotator call at %zu: seg_first", pos);
+        unsigned ck_end = 0;
+        bool dep_writes = false;
+        unsigned long long longest_chain = 0, longest_const = 0;
+        std::vector<unsigned> consts;
+        for (size_t c = 0; c < C && rp.seg_first.size() == C + 1; ++c) {
+            size_t at = 0;
+            unsigned n_dep = 0;
+            for (unsigned i = rp.seg_first[c]; i < rp.seg_first[c + 1]; ++i) {
+                const RotSeg& sg = rp.segs[i];
+                CHECK(sg.channel == c && sg.start == at && sg.len > 0, "rotator call at %zu: segment %u of channel %zu does not continue the tiling", pos, i, c);
+                CHECK(sg.last == (i + 1 == rp.seg_first[c + 1]), "rotator call at %zu: segment %u: last = %d", pos, i, sg.last);
+                CHECK(sg.ck0 % 2 == 0 && sg.ck0 >= ck_end, "rotator call at %zu: segment %u: slot %u behind %u", pos, i, sg.ck0, ck_end);
+                CHECK(!(no_fixed && sg.mode == 2), "rotator call at %zu: a fixed-point segment with the switch off", pos);
+                ck_end = sg.ck0 + static_cast<unsigned>((sg.len + kRotChunk - 1) / kRotChunk);
+                at += sg.len;
+                n_dep += sg.mode == 0;
+                dep_writes |= sg.mode == 0 && sg.last;
+                unsigned long long& longest = sg.mode == 2 ? longest_const : longest_chain;
+                longest = std::max(longest, sg.len);
+                if (sg.mode == 2) consts.push_back(i);
+            }
+            CHECK(at == m && n_dep <= 1, "rotator call at %zu: channel %zu covers %zu of %zu items, %u continuations", pos, c, at, m, n_dep);
+        }
+        CHECK(rp.ck_total >= ck_end && dep_writes == rp.dep_writes_state && longest_chain == rp.longest_chain &&
+                  longest_const == rp.longest_const && consts == rp.const_list, "rotator call at %zu: the plan's figures disagree with its table", pos);
+        {
+            std::vector<uint8_t> seen(n_segs, 0);
+            auto part = [&](unsigned a) { return rp.segs[a].mode == 0 ? 2u : rp.segs[a].last ? 1u : 0u; };
+            unsigned counts[3] = { 0, 0, 0 };
+            bool ok = rp.order.size() == n_segs;
+            for (unsigned i = 0; ok && i < n_segs; ++i) {
+                const unsigned a = rp.order[i];
+                ok = a < n_segs && !seen[a];
+                if (!ok) break;
+                seen[a] = 1;
+                counts[part(a)] += 1;
+                if (i > 0) {
+                    const unsigned b = rp.order[i - 1];
+                    ok = part(b) < part(a) || (part(b) == part(a) && (no_sort ? b < a : rp.segs[b].len > rp.segs[a].len || (rp.segs[b].len == rp.segs[a].len && b < a)));
+                }
+            }
+            CHECK(ok && counts[0] == rp.n_indep && counts[1] == rp.n_writer, "rotator call at %zu: order[] is no permutation in indep | writer | dep order", pos);
+        }
+        // the table, item by item
+        for (const RotSeg& sg : rp.segs) {
+            St& s = st[sg.channel];
+            cf e = sg.mode == 0 ? s.exp : sg.exp0, inc = sg.mode == 0 ? s.incr : sg.incr;
+            unsigned counter = sg.mode == 0 ? s.counter : 0;
+            if (sg.mode == 2) { // k_rot_const_fill writes exp0 into every checkpoint: one step, and a renormalisation, must change nothing
+                const cf e1 = cmul_cf(e, inc);
+                const float r = static_cast<float>(std::sqrt(static_cast<double>(e1.x) * e1.x + static_cast<double>(e1.y) * e1.y));
+                const cf e2 = { e1.x / r, e1.y / r };
+                CHECK(bits_eq(e1, e) && bits_eq(e2, e), "rotator call at %zu: (%g, %g) * (%g, %g) is no fixed point", pos, static_cast<double>(e.x),
+                      static_cast<double>(e.y), static_cast<double>(inc.x), static_cast<double>(inc.y));
+            }
+            for (unsigned long long j = 0; j < sg.len; ++j) {
+                const c64 v = x[sg.channel][pos + sg.start + j];
+                const cf y = cmul_cf({ v.re, v.im }, e);
+                got[sg.channel][pos + sg.start + j] = { y.x, y.y };
+                e = cmul_cf(e, inc);
+                if ((++counter & 511u) == 0) {
+                    const float r = static_cast<float>(std::sqrt(static_cast<double>(e.x) * e.x + static_cast<double>(e.y) * e.y));
+                    e = { e.x / r, e.y / r };
+                }
+            }
+            if (sg.last) s = { e, inc, sg.mode == 2 ? 0u : counter }; // (a fixed point's counter: see rot_checkpoints_generic)
+        }
+        std::swap(h.carried, rp.carried); // the call succeeded
+        pos += m;
+    }
+    for (size_t c = 0; c < C; ++c) {
+        std::vector<c64> want(n, c64{ -2, -2 });
+        if (h.mode == 1) {
+            std::vector<uint64_t> ti;
+            std::vector<double> tf;
+            syncword_tags(tags[c], ti, &tf, nullptr);
+            orc_cfc* ref = orc_cfc_create(h.delay);
+            orc_cfc_process(ref, x[c].data(), n, want.data(), ti.data(), tf.data(), ti.size());
+            orc_cfc_destroy(ref);
+        } else {
+            orc_rot* ref = orc_rot_create(phase_incr);
+            orc_rot_process(ref, x[c].data(), n, want.data());
+            orc_rot_destroy(ref);
+        }
+        CHECK(same_bits(got[c].data(), want.data(), n), "rotator: channel %zu of %zu differs (mode %d delay %zu phase_incr %g no_fixed %d)", c, C, h.mode,
+              h.delay, static_cast<double>(phase_incr), no_fixed);
+    }
+}
+
+// CostasLoop::process / process_ragged: the segments fed to the oracle one by one, in stream order, a fresh call each
+// -- a set_phase segment as a call with one tag on its first item -- against the oracle over the whole call
+static void costas_segment_tables(std::mt19937_64& rng)
+{
+    const size_t C = 1 + rng() % 3, n = 12000 + rng() % 2000;
+    const bool ragged = rng() % 2, no_sort = rng() % 4 == 0;
+    const int constellation = static_cast<int>(rng() % 3);
+    const double bw = 0.002 + 0.0001 * static_cast<double>(rng() % 300);
+    CostasHostState h;
+    h.loop_bandwidth = bw, h.constellation = constellation;
+    costas_coeffs(h);
+    std::vector<orc_costas*> by_seg(C), whole(C);
+    std::vector<std::vector<c64>> x(C);
+    std::vector<std::vector<gr4pm_tag>> tags(C);
+    std::vector<size_t> pos(C, 0);
+    for (size_t c = 0; c < C; ++c) {
+        by_seg[c] = orc_costas_create(bw, constellation);
+        whole[c] = orc_costas_create(bw, constellation);
+        x[c] = noise(rng, n);
+        tags[c] = ragged_tags(rng, n, 2500, 30);
+    }
+    float k1 = 0, k2 = 0;
+    orc_costas_coeffs(whole[0], &k1, &k2);
+    CHECK(bits_eq(k1, h.k1) && bits_eq(k2, h.k2), "costas: coefficients (%g, %g), the oracle's (%g, %g)", static_cast<double>(h.k1),
+          static_cast<double>(h.k2), static_cast<double>(k1), static_cast<double>(k2));
+    for (;;) {
+        std::vector<size_t> m(C);
+        size_t total = 0, m_all = 1 + rng() % 5000;
+        for (size_t c = 0; c < C; ++c) {
+            m[c] = std::min<size_t>(n - pos[c], ragged ? (rng() % 4 ? 1 + rng() % 5000 : 0) : m_all);
+            total += n - pos[c];
+        }
+        if (total == 0) break;
+        std::vector<gr4pm_tag> tin;
+        std::vector<uint32_t> tch;
+        for (size_t c = 0; c < C; ++c) tags_of_call(tags[c], pos[c], m[c], static_cast<uint32_t>(c), tin, tch);
+        const uint32_t* tag_channel = C == 1 && rng() % 2 ? nullptr : tch.data();
+        std::vector<CostasSeg> segs, plain;
+        costas_segments(C, [&](size_t c) { return m[c]; }, tin.data(), tag_channel, tin.size(), no_sort, segs);
+        costas_segments(C, [&](size_t c) { return m[c]; }, tin.data(), tag_channel, tin.size(), true, plain);
+        for (size_t i = 1; i < segs.size() && !no_sort; ++i)
+            CHECK(segs[i - 1].len >= segs[i].len, "costas: segment %zu (%u items) in front of a longer one (%u)", i - 1, segs[i - 1].len, segs[i].len);
+        // back into stream order: the same records as without the sort
+        std::stable_sort(segs.begin(), segs.end(), [](const CostasSeg& a, const CostasSeg& b) { return a.channel != b.channel ? a.channel < b.channel : a.start < b.start; });
+        CHECK(segs.size() == plain.size() && (segs.empty() || std::memcmp(segs.data(), plain.data(), segs.size() * sizeof(CostasSeg)) == 0),
+              "costas: the sorted table is no permutation of the segments");
+        size_t i = 0;
+        for (size_t c = 0; c < C; ++c) {
+            size_t at = 0, n_last = 0;
+            std::vector<c64> got(m[c] + 1, c64{ -1, -1 }), want(m[c] + 1, c64{ -1, -1 });
+            const size_t i0 = i;
+            for (; i < segs.size() && segs[i].channel == c; ++i) {
+                const CostasSeg& sg = segs[i];
+                CHECK(sg.start == at && (sg.len > 0 || m[c] == 0), "costas: segment %zu of channel %zu does not continue the tiling", i, c);
+                n_last += sg.last != 0;
+                CHECK(!sg.last || i + 1 == segs.size() || segs[i + 1].channel != c, "costas: a segment in front of the channel's end writes the state");
+                const uint64_t at0 = 0;
+                orc_costas_process(by_seg[c], x[c].data() + pos[c] + sg.start, sg.len, got.data() + sg.start, &at0, &sg.phase0, sg.mode == 1 ? 1 : 0);
+                at += sg.len;
+            }
+            CHECK(at == m[c] && n_last == 1 && (m[c] > 0 || i - i0 == 1), "costas: channel %zu: %zu of %zu items, %zu state writers, %zu segments", c, at, m[c],
+                  n_last, i - i0);
+            std::vector<uint64_t> ti;
+            std::vector<float> tp;
+            std::vector<gr4pm_tag> mine;
+            std::vector<uint32_t> unused;
+            tags_of_call(tags[c], pos[c], m[c], 0, mine, unused);
+            syncword_tags(mine, ti, nullptr, &tp);
+            orc_costas_process(whole[c], x[c].data() + pos[c], m[c], want.data(), ti.data(), tp.data(), ti.size());
+            CHECK(same_bits(got.data(), want.data(), m[c] + 1), "costas: channel %zu differs in the call at %zu (constellation %d)", c, pos[c], constellation);
+            pos[c] += m[c];
+        }
+        CHECK(i == segs.size(), "costas: %zu segments of no channel", segs.size() - i);
+    }
+    for (size_t c = 0; c < C; ++c) orc_costas_destroy(by_seg[c]), orc_costas_destroy(whole[c]);
+}
+
+// CostasLoop::process_packets: the chains' pieces fed to the oracle one by one -- the piece's settings, and the chain's
+// set_phase on its first piece, as one tag on the piece's first item -- against the oracle over the whole call; with the
+// loop's input in memory as it is, and scattered behind a span table
+static void costas_chain_tables(std::mt19937_64& rng)
+{
+    std::normal_distribution<float> g(0.f, 1.f);
+    const size_t n = 16000 + rng() % 2000;
+    const bool with_spans = rng() % 2;
+    const double bws[4] = { 0.02, 0.01, 0.005, 0.0123 };
+    std::vector<gr4pm_packet_tag> all; // a PayloadMetadataInsert-shaped tag stream, and tags that name nothing
+    for (uint64_t p = rng() % 200; p < n;) {
+        gr4pm_packet_tag t{};
+        t.index = p;
+        t.kind = GR4PM_PKT_SYNCWORD, t.constellation = 0, t.loop_bandwidth = bws[0];
+        t.syncword.flags = rng() % 9 ? GR4PM_TAG_SYNCWORD : GR4PM_TAG_OTHER;
+        t.syncword.phase = g(rng);
+        all.push_back(t);
+        t = gr4pm_packet_tag{};
+        t.index = p + 64;
+        t.kind = GR4PM_PKT_HEADER_START, t.constellation = 2, t.loop_bandwidth = bws[1];
+        all.push_back(t);
+        p += 64 + 128;
+        if (rng() % 5) {
+            t = gr4pm_packet_tag{};
+            t.index = p;
+            t.kind = GR4PM_PKT_PAYLOAD, t.constellation = rng() % 3 ? -1 : 1, t.loop_bandwidth = rng() % 4 ? bws[2 + rng() % 2] : -1.0;
+            all.push_back(t);
+            p += 4 * (5 + rng() % 300);
+        }
+        p += rng() % 3 ? 0 : rng() % 700;
+    }
+    while (!all.empty() && all.back().index >= n) all.pop_back();
+    const auto x = noise(rng, n);
+    CostasHostState h;
+    h.loop_bandwidth = 0.01, h.constellation = 1;
+    costas_coeffs(h);
+    orc_costas* by_piece = orc_costas_create(h.loop_bandwidth, h.constellation);
+    orc_costas* whole = orc_costas_create(h.loop_bandwidth, h.constellation);
+    double bw_now = h.loop_bandwidth; // the bandwidth behind a piece's k1 / k2: the last one a tag named
+    size_t pos = 0, ti = 0;
+    while (pos < n) {
+        const size_t m = std::min<size_t>(n - pos, 1 + rng() % (rng() % 3 ? 5000 : 200));
+        std::vector<gr4pm_packet_tag> tin;
+        for (auto t : all)
+            if (t.index >= pos && t.index < pos + m) {
+                t.index -= pos;
+                tin.push_back(t);
+            }
+        // the call's items scattered over a larger buffer, in ascending spans
+        std::vector<CopySpan> spans;
+        std::vector<c64> raw;
+        if (with_spans) {
+            for (size_t d = 0; d < m;) {
+                const size_t len = std::min<size_t>(m - d, 1 + rng() % 900), gap = rng() % 50;
+                raw.resize(raw.size() + gap, c64{ 9, 9 });
+                spans.push_back({ raw.size(), d, len });
+                raw.insert(raw.end(), x.begin() + static_cast<long>(pos + d), x.begin() + static_cast<long>(pos + d + len));
+                d += len;
+            }
+        }
+        const c64* in = with_spans ? raw.data() : x.data() + pos;
+        std::vector<CostasChain> chains;
+        std::vector<CostasPiece> pieces;
+        const gr4pm_status st = costas_packet_chains(h, with_spans ? spans.data() : nullptr, spans.size(), m, tin.data(), tin.size(), chains, pieces);
+        CHECK(st == GR4PM_OK && !chains.empty(), "costas chains at %zu: status %d (%s)", pos, st, gr4pm::g_error);
+        std::vector<c64> got(m + 1, c64{ -1, -1 }), want(m + 1, c64{ -1, -1 });
+        size_t at = 0, piece = 0;
+        for (size_t k = 0; k < chains.size(); ++k) {
+            const CostasChain& ch = chains[k];
+            CHECK(ch.piece0 == piece && ch.n_pieces > 0 && ch.last == (k + 1 == chains.size()) && (k == 0 || ch.mode == 1),
+                  "costas chains at %zu: chain %zu: pieces from %u (%zu expected), %u of them, last %d, mode %d", pos, k, ch.piece0, piece, ch.n_pieces, ch.last, ch.mode);
+            for (unsigned q = 0; q < ch.n_pieces && piece < pieces.size(); ++q, ++piece) {
+                const CostasPiece& pc = pieces[piece];
+                CHECK(pc.start == at && pc.len > 0, "costas chains at %zu: piece %zu does not continue the tiling", pos, piece);
+                while (ti < all.size() && all[ti].index <= pos + pc.start) {
+                    if (all[ti].loop_bandwidth >= 0.0) bw_now = all[ti].loop_bandwidth;
+                    ++ti;
+                }
+                gr4pm_packet_tag t{};
+                t.index = 0;
+                t.kind = q == 0 && ch.mode == 1 ? GR4PM_PKT_SYNCWORD : GR4PM_PKT_HEADER_START;
+                t.constellation = pc.constellation;
+                t.loop_bandwidth = bw_now;
+                t.syncword.flags = GR4PM_TAG_SYNCWORD;
+                t.syncword.phase = ch.phase0;
+                orc_costas_process_packets(by_piece, in + static_cast<long long>(pc.start) + pc.in_off, pc.len, got.data() + pc.start,
+                                           reinterpret_cast<const orc_ptag*>(&t), 1);
+                float k1 = 0, k2 = 0;
+                orc_costas_coeffs(by_piece, &k1, &k2);
+                CHECK(bits_eq(k1, pc.k1) && bits_eq(k2, pc.k2), "costas chains at %zu: piece %zu carries other coefficients than the oracle's", pos, piece);
+                at += pc.len;
+            }
+        }
+        CHECK(at == m && piece == pieces.size(), "costas chains at %zu: the pieces cover %zu of %zu items", pos, at, m);
+        orc_costas_process_packets(whole, x.data() + pos, m, want.data(), reinterpret_cast<const orc_ptag*>(tin.data()), tin.size());
+        CHECK(same_bits(got.data(), want.data(), m + 1), "costas chains at %zu: items differ (spans: %d)", pos, with_spans);
+        pos += m;
+    }
+    orc_costas_destroy(by_piece);
+    orc_costas_destroy(whole);
+}
+// what process_packets refuses, with the library's texts, and a piece longer than a record's 32-bit length (table
+// arithmetic only: no samples)
+static void costas_chain_refusals()
+{
+    std::vector<CostasChain> chains;
+    std::vector<CostasPiece> pieces;
+    CostasHostState h;
+    h.loop_bandwidth = 0.01, h.constellation = 1;
+    costas_coeffs(h);
+    const CopySpan hole[2] = { { 100, 0, 40 }, { 300, 50, 50 } }; // nothing for [40, 50)
+    gr4pm::g_error[0] = 0;
+    CHECK(costas_packet_chains(h, hole, 2, 100, nullptr, 0, chains, pieces) == GR4PM_ERR_INVALID &&
+              std::strcmp(gr4pm::g_error, "process_packets: the span table does not cover the stream") == 0,
+          "a span table with a hole: %s", gr4pm::g_error);
+    const CopySpan brief[1] = { { 100, 0, 40 } }; // ends in front of the stream's end
+    chains.clear(), pieces.clear();
+    CHECK(costas_packet_chains(h, brief, 1, 100, nullptr, 0, chains, pieces) == GR4PM_ERR_INVALID, "a span table that ends early was accepted");
+    // a constellation the loop does not have: refused, and the settings of the tags in front of it stay applied
+    gr4pm_packet_tag tags[2] = {};
+    tags[0].index = 10, tags[0].kind = GR4PM_PKT_HEADER_START, tags[0].constellation = 2, tags[0].loop_bandwidth = 0.02;
+    tags[1].index = 20, tags[1].kind = GR4PM_PKT_HEADER_START, tags[1].constellation = 3, tags[1].loop_bandwidth = 0.03;
+    CostasHostState want = h;
+    want.constellation = 2, want.loop_bandwidth = 0.02;
+    costas_coeffs(want);
+    chains.clear(), pieces.clear();
+    CHECK(costas_packet_chains(h, nullptr, 0, 100, tags, 2, chains, pieces) == GR4PM_ERR_INVALID && std::strcmp(gr4pm::g_error, "constellation 3") == 0,
+          "constellation 3: %s", gr4pm::g_error);
+    CHECK(h.constellation == 2 && h.loop_bandwidth == 0.02 && bits_eq(h.k1, want.k1) && bits_eq(h.k2, want.k2),
+          "the refused call did not leave the first tag's settings applied");
+    // 2^30 + 10 items without a tag: two pieces of one chain; behind one span, both with its offset
+    const size_t n = (size_t{ 1 } << 30) + 10;
+    const CopySpan one[1] = { { 5, 0, n } };
+    for (int with_span = 0; with_span < 2; ++with_span) {
+        chains.clear(), pieces.clear();
+        const gr4pm_status st = costas_packet_chains(h, with_span ? one : nullptr, with_span, n, nullptr, 0, chains, pieces);
+        CHECK(st == GR4PM_OK && chains.size() == 1 && chains[0].piece0 == 0 && chains[0].n_pieces == 2 && chains[0].mode == 0 && chains[0].last == 1 &&
+                  pieces.size() == 2 && pieces[0].start == 0 && pieces[0].len == (1u << 30) && pieces[1].start == (1ull << 30) && pieces[1].len == 10 &&
+                  pieces[0].in_off == 5 * with_span && pieces[1].in_off == 5 * with_span,
+              "a run of 2^30 + 10 items was cut wrongly (%zu pieces)", pieces.size());
+    }
+}
+
+// SyncwordWipeoff: the spans applied with a plain loop, the stream in calls cut at random (inside a syncword too)
+static void wipeoff_spans(std::mt19937_64& rng)
+{
+    std::normal_distribution<float> g(0.f, 1.f);
+    const size_t n = 20000 + rng() % 2000;
+    std::vector<float> syncword(1 + rng() % 96);
+    for (auto& v : syncword) v = rng() % 2 ? 1.0f : -1.0f + 0.001f * g(rng);
+    const auto x = noise(rng, n);
+    const auto tags = ragged_tags(rng, n, 1200, 30); // (near: a tag while the syncword in front of it is still being wiped)
+    WipeState h;
+    h.syncword_size = syncword.size();
+    std::vector<c64> got(n, c64{ -1, -1 }), want(n, c64{ -2, -2 });
+    size_t pos = 0;
+    while (pos < n) {
+        const size_t m = std::min<size_t>(n - pos, 1 + rng() % (rng() % 3 ? 4000 : 50));
+        std::vector<gr4pm_tag> tin;
+        std::vector<uint32_t> unused;
+        tags_of_call(tags, pos, m, 0, tin, unused);
+        const size_t base = rng() % 2 ? 0 : 1 + rng() % 1000; // (a channel's row inside a buffer of several)
+        std::vector<WipeSpan> spans;
+        wipe_replay(h, m, tin.data(), tin.size(), base, spans);
+        std::memcpy(got.data() + pos, x.data() + pos, m * sizeof(c64)); // k_copy, then k_wipe on the spans
+        for (const auto& w : spans) {
+            CHECK(w.start >= base && w.start - base + w.len <= m && w.first + w.len <= syncword.size() && w.len > 0, "wipeoff call at %zu: span outside the call", pos);
+            if (!(w.start >= base && w.start - base + w.len <= m && w.first + w.len <= syncword.size())) continue;
+            for (unsigned i = 0; i < w.len; ++i) {
+                const c64 v = x[pos + w.start - base + i];
+                got[pos + w.start - base + i] = { syncword[w.first + i] * v.re, syncword[w.first + i] * v.im };
+            }
+        }
+        pos += m;
+    }
+    std::vector<uint64_t> ti;
+    syncword_tags(tags, ti, nullptr, nullptr);
+    orc_wipe* ref = orc_wipe_create(syncword.data(), syncword.size());
+    orc_wipe_process(ref, x.data(), n, want.data(), ti.data(), ti.size());
+    orc_wipe_destroy(ref);
+    CHECK(same_bits(got.data(), want.data(), n), "wipeoff: items differ (syncword of %zu)", syncword.size());
+}
+
+// ConstellationLLRDecoder: the runs applied with scale * x, items and re-indexed tags, the stream in calls cut at random
+static void llr_run_tables(std::mt19937_64& rng)
+{
+    const size_t n = 15000 + rng() % 2000;
+    const float sigma = 0.5f + 0.001f * static_cast<float>(rng() % 1000), scale = 2.0f / (sigma * sigma);
+    std::vector<gr4pm_packet_tag> all;
+    for (uint64_t p = rng() % 300; p < n; p += rng() % 8 ? 1 + rng() % (rng() % 3 ? 1500 : 20) : 0) { // (several on one item among them)
+        gr4pm_packet_tag t{};
+        t.index = p;
+        t.kind = 1 + static_cast<int32_t>(rng() % 3);
+        t.constellation = rng() % 3 ? 1 + static_cast<int32_t>(rng() % 2) : -1;
+        t.loop_bandwidth = -1.0;
+        all.push_back(t);
+        if (all.size() > 4000) break;
+    }
+    const auto x = noise(rng, n);
+    LlrState h;
+    h.constellation = 1 + static_cast<int>(rng() % 2);
+    orc_llr* ref = orc_llr_create(sigma, h.constellation);
+    std::vector<float> got(2 * n + 1, -7.f), want(2 * n + 1, -7.f);
+    std::vector<gr4pm_packet_tag> gt, wt(all.size() + 1);
+    size_t pos = 0, opos = 0;
+    while (pos < n) {
+        const size_t m = std::min<size_t>(n - pos, 1 + rng() % (rng() % 3 ? 4000 : 40));
+        std::vector<gr4pm_packet_tag> tin, tout(all.size() + 1);
+        for (auto t : all)
+            if (t.index >= pos && t.index < pos + m) {
+                t.index -= pos;
+                tin.push_back(t);
+            }
+        std::vector<LlrRun> runs;
+        size_t n_pub = 0, produced = 0;
+        const gr4pm_status st = llr_runs(h, m, 2 * m, tin.data(), tin.size(), tout.data(), tout.size(), &n_pub, &produced, runs);
+        CHECK(st == GR4PM_OK && n_pub == tin.size(), "llr call at %zu: status %d (%s), %zu of %zu tags", pos, st, gr4pm::g_error, n_pub, tin.size());
+        size_t at_in = 0, at_out = 0;
+        const float* src = &x[pos].re;
+        for (const auto& r : runs) { // k_llr
+            const size_t n_sym = r.n_out / (r.qpsk ? 2 : 1);
+            CHECK(r.in0 == at_in && r.out0 == at_out && r.n_out > 0, "llr call at %zu: a run does not continue the tiling", pos);
+            if (r.in0 + n_sym > m || r.out0 + r.n_out > 2 * m) break;
+            for (unsigned long long i = 0; i < r.n_out; ++i) got[opos + r.out0 + i] = scale * src[2 * r.in0 + (r.qpsk ? i : 2 * i)];
+            at_in += n_sym, at_out += r.n_out;
+        }
+        CHECK(at_in == m && at_out == produced, "llr call at %zu: the runs cover %zu of %zu symbols, %zu of %zu LLRs", pos, at_in, m, at_out, produced);
+        for (size_t i = 0; i < std::min(n_pub, tout.size()); ++i) {
+            gt.push_back(tout[i]);
+            gt.back().index += opos;
+        }
+        pos += m;
+        opos += produced;
+    }
+    size_t wnt = 0;
+    const size_t wprod = orc_llr_process(ref, x.data(), n, want.data(), reinterpret_cast<const orc_ptag*>(all.data()), all.size(),
+                                         reinterpret_cast<orc_ptag*>(wt.data()), wt.size(), &wnt);
+    CHECK(opos == wprod && gt.size() == wnt, "llr: %zu/%zu LLRs, %zu/%zu tags", opos, wprod, gt.size(), wnt);
+    CHECK(std::memcmp(got.data(), want.data(), got.size() * sizeof(float)) == 0, "llr: items differ");
+    CHECK(same_ptags(gt.data(), wt.data(), std::min(gt.size(), wnt)), "llr: tags differ");
+    orc_llr_destroy(ref);
+}
+// what the decoder refuses, with the library's status and texts
+static void llr_refusals()
+{
+    LlrState h;
+    std::vector<LlrRun> runs;
+    gr4pm_packet_tag tags[2] = {}, out[2];
+    tags[0].index = 10, tags[0].constellation = 1;
+    tags[1].index = 20, tags[1].constellation = 3;
+    size_t n_pub = 0, produced = 0;
+    CHECK(llr_runs(h, 100, 200, tags, 2, out, 2, &n_pub, &produced, runs) == GR4PM_ERR_INVALID &&
+              std::strcmp(gr4pm::g_error, "constellation 3 not supported") == 0 && h.constellation == 1,
+          "constellation 3: %s", gr4pm::g_error);
+    tags[1].constellation = 0;
+    runs.clear();
+    CHECK(llr_runs(h, 100, 200, tags, 2, out, 2, &n_pub, &produced, runs) == GR4PM_ERR_INVALID &&
+              std::strcmp(gr4pm::g_error, "constellation 0 not supported") == 0,
+          "constellation 0: %s", gr4pm::g_error);
+    // 10 QPSK + 90 BPSK symbols are 110 LLRs
+    h.constellation = 2;
+    tags[1].constellation = -1;
+    runs.clear();
+    CHECK(llr_runs(h, 100, 109, tags, 2, out, 2, &n_pub, &produced, runs) == GR4PM_INSUFFICIENT_OUTPUT_ITEMS &&
+              std::strcmp(gr4pm::g_error, "out_cap 109 < 110 LLRs") == 0,
+          "out_cap: %s", gr4pm::g_error);
+    h.constellation = 2;
+    runs.clear();
+    CHECK(llr_runs(h, 100, 110, tags, 2, out, 1, &n_pub, &produced, runs) == GR4PM_ERR_OVERFLOW && n_pub == 2 && produced == 110 &&
+              std::strcmp(gr4pm::g_error, "tags_cap too small") == 0,
+          "tags_cap: %s", gr4pm::g_error);
+}
+
 int main(int argc, char** argv)
 {
     const int cases = argc > 1 ? atoi(argv[1]) : 20;
     const unsigned long long seed = argc > 2 ? strtoull(argv[2], nullptr, 10) : 4;
     std::mt19937_64 rng(seed);
     tail_refusals();
+    costas_chain_refusals();
+    llr_refusals();
     for (int c = 0; c < cases; ++c) {
         sdf_calls(rng);
         sdf_gate_vs_block(rng);
         symbol_filter(rng);
         control_blocks(rng);
         tail_compose(rng);
+        rotator_plans(rng);
+        costas_segment_tables(rng);
+        costas_chain_tables(rng);
+        wipeoff_spans(rng);
+        llr_run_tables(rng);
     }
     for (int c = 0; c < std::max(2, cases / 5); ++c) slot_pipeline(rng);
     for (int c = 0; c < std::max(2, cases / 10); ++c) zmtp_pub(rng);

@@ -1,6 +1,8 @@
 """The library's HIP-free host logic (gr4-packet-modem_amd/csrc/hostlogic/*.hpp -- the headers the .hip files include:
 SyncwordDetectionFilter's gate, SymbolFilter's tag replay / run table, the PayloadMetadataInsert / SyncwordRemove /
-HeaderPayloadSplit state machines, the receivers' slot rings and stage loop) built with g++ and no HIP under
+HeaderPayloadSplit state machines, the Rotator / CoarseFrequencyCorrection segment planner, the CostasLoop coefficients,
+segment and packet-chain planners, SyncwordWipeoff's spans, ConstellationLLRDecoder's runs, the composed tail, the
+receivers' slot rings and stage loop) built with g++ and no HIP under
 AddressSanitizer, UndefinedBehaviorSanitizer and ThreadSanitizer (tests/hostlogic/Makefile: `make SAN=...`, mirroring
 the reference's CMakeLists.txt:8-10,81-100) and checked against the CPU oracle on randomised streams.  No GPU."""
 import os
