@@ -6,6 +6,8 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <new>
 
 #include <vector>
@@ -167,6 +169,30 @@ struct PinnedBuf {
         return GR4PM_OK;
     }
 };
+
+// kernels that take more dynamic LDS than the default window of 48 KiB
+inline gr4pm_status raise_dynamic_lds(std::initializer_list<const void*> fns, size_t bytes, const char* name)
+{
+    for (const void* fn : fns)
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) != hipSuccess) {
+            set_error("%s: hipFuncSetAttribute(%zu bytes of LDS) failed", name, bytes);
+            return GR4PM_ERR_HIP;
+        }
+    return GR4PM_OK;
+}
+
+// the end of a create(): the uploads read host vectors that end with the call, so wait for them; then the handle
+// is the caller's.  Any earlier return deletes it with the unique_ptr.
+template <typename Handle>
+gr4pm_status finish_create(std::unique_ptr<Handle>& h, Handle** out, const char* name)
+{
+    if (hipStreamSynchronize(h->stream) != hipSuccess) {
+        set_error("%s: hipStreamSynchronize failed at create", name);
+        return GR4PM_ERR_HIP;
+    }
+    *out = h.release();
+    return GR4PM_OK;
+}
 
 inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 

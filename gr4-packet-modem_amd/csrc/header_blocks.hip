@@ -537,6 +537,7 @@ struct gr4pm_crc_check {
     gr4pm_crc_check_params p;
     unsigned long long table[256];
     unsigned long long mask;
+    hipStream_t stream = nullptr; // p.stream, typed (what finish_create and the calls use)
     DevBuf<unsigned long long> d_table;
     DevBuf<uint32_t> d_slice; // slicing-by-eight tables (k_crc_check_sliced); empty: the byte-wise kernel
     bool sliced = false;
@@ -585,7 +586,7 @@ try {
     if (!p || !out || (p->item_kind != 1 && p->item_kind != 2) || p->length > 63) return GR4PM_ERR_INVALID;
     *out = nullptr;
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_additive_scrambler;
+    std::unique_ptr<gr4pm_additive_scrambler> h(new (std::nothrow) gr4pm_additive_scrambler);
     if (!h) return GR4PM_ERR_NOMEM;
     h->mask = p->mask;
     h->seed = p->seed;
@@ -639,15 +640,9 @@ try {
     h->prefix = std::min<uint64_t>(mu, total - 1);
     h->period = total - h->prefix;
     h->table_len = total;
-    gr4pm_status s = h->seq.alloc(seq.size());
-    if (s == GR4PM_OK) s = h->seq.upload(seq.data(), seq.size(), h->stream);
-    if (s == GR4PM_OK && hipStreamSynchronize(h->stream) != hipSuccess) s = GR4PM_ERR_HIP;
-    if (s != GR4PM_OK) {
-        delete h;
-        return s;
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->seq.alloc(seq.size()));
+    GR4PM_TRY(h->seq.upload(seq.data(), seq.size(), h->stream));
+    return finish_create(h, out, "additive_scrambler");
 }
 GR4PM_ABI_CATCH
 void gr4pm_additive_scrambler_destroy(gr4pm_additive_scrambler* h)
@@ -703,11 +698,11 @@ try {
     if (!p || !out || p->header_size == 0) return GR4PM_ERR_INVALID;
     *out = nullptr;
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_header_payload_split;
+    std::unique_ptr<gr4pm_header_payload_split> h(new (std::nothrow) gr4pm_header_payload_split);
     if (!h) return GR4PM_ERR_NOMEM;
     h->header_size = p->header_size;
     h->stream = static_cast<hipStream_t>(p->stream);
-    *out = h;
+    *out = h.release(); // (nothing was queued on the stream: nothing to wait for)
     return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
@@ -887,7 +882,7 @@ try {
         corr[k] = static_cast<float>(std::log1p(std::exp(-k / 8.0)));
         if (p->arithmetic == 1) corr[k] = static_cast<float>(std::nearbyint(8.0 * std::log1p(std::exp(-k / 8.0))));
     }
-    auto* h = new (std::nothrow) gr4pm_header_fec_decoder;
+    std::unique_ptr<gr4pm_header_fec_decoder> h(new (std::nothrow) gr4pm_header_fec_decoder);
     if (!h) return GR4PM_ERR_NOMEM;
     h->arithmetic = p->arithmetic;
     h->n = n;
@@ -895,25 +890,15 @@ try {
     h->n_steps = static_cast<unsigned>(sched.size() / 64);
     h->max_iterations = p->max_iterations;
     h->stream = static_cast<hipStream_t>(p->stream);
-    gr4pm_status s = GR4PM_OK;
-    auto ok = [&](gr4pm_status r) {
-        if (s == GR4PM_OK) s = r;
-    };
-    ok(h->row_var.alloc(row_var.size()));
-    ok(h->row_deg.alloc(row_deg.size()));
-    ok(h->sched.alloc(sched.size()));
-    ok(h->corr.alloc(corr.size()));
-    if (s == GR4PM_OK) s = h->row_var.upload(row_var.data(), row_var.size(), h->stream);
-    if (s == GR4PM_OK) s = h->row_deg.upload(row_deg.data(), row_deg.size(), h->stream);
-    if (s == GR4PM_OK) s = h->sched.upload(sched.data(), sched.size(), h->stream);
-    if (s == GR4PM_OK) s = h->corr.upload(corr.data(), corr.size(), h->stream);
-    if (s == GR4PM_OK && hipStreamSynchronize(h->stream) != hipSuccess) s = GR4PM_ERR_HIP;
-    if (s != GR4PM_OK) {
-        delete h;
-        return s;
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->row_var.alloc(row_var.size()));
+    GR4PM_TRY(h->row_deg.alloc(row_deg.size()));
+    GR4PM_TRY(h->sched.alloc(sched.size()));
+    GR4PM_TRY(h->corr.alloc(corr.size()));
+    GR4PM_TRY(h->row_var.upload(row_var.data(), row_var.size(), h->stream));
+    GR4PM_TRY(h->row_deg.upload(row_deg.data(), row_deg.size(), h->stream));
+    GR4PM_TRY(h->sched.upload(sched.data(), sched.size(), h->stream));
+    GR4PM_TRY(h->corr.upload(corr.data(), corr.size(), h->stream));
+    return finish_create(h, out, "header_fec_decoder");
 }
 GR4PM_ABI_CATCH
 void gr4pm_header_fec_decoder_destroy(gr4pm_header_fec_decoder* h)
@@ -1082,9 +1067,10 @@ try {
         return GR4PM_ERR_INVALID;
     }
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_crc_check;
+    std::unique_ptr<gr4pm_crc_check> h(new (std::nothrow) gr4pm_crc_check);
     if (!h) return GR4PM_ERR_NOMEM;
     h->p = *p;
+    h->stream = static_cast<hipStream_t>(p->stream);
     h->mask = p->num_bits == 64 ? ~0ull : ((1ull << p->num_bits) - 1);
     // table, crc.hpp:84-116
     unsigned long long poly = p->poly;
@@ -1108,9 +1094,8 @@ try {
             i <<= 1;
         } while (i < 256);
     }
-    hipStream_t s = static_cast<hipStream_t>(p->stream);
-    gr4pm_status st = h->d_table.alloc(256);
-    if (st == GR4PM_OK) st = h->d_table.upload(h->table, 256, s);
+    GR4PM_TRY(h->d_table.alloc(256));
+    GR4PM_TRY(h->d_table.upload(h->table, 256, h->stream));
     // slice[k][b]: the register after byte b and k zero bytes (k_crc_check_sliced); GR4PM_CRC_BYTEWISE keeps the byte loop
     std::vector<uint32_t> slice;
     h->sliced = !getenv("GR4PM_CRC_BYTEWISE") && p->num_bits <= 32 && (p->input_reflected || p->num_bits == 32);
@@ -1125,22 +1110,16 @@ try {
                 slice[k * 256 + b] = v;
             }
         }
-        if (st == GR4PM_OK) st = h->d_slice.alloc(slice.size());
-        if (st == GR4PM_OK) st = h->d_slice.upload(slice.data(), slice.size(), s);
+        GR4PM_TRY(h->d_slice.alloc(slice.size()));
+        GR4PM_TRY(h->d_slice.upload(slice.data(), slice.size(), h->stream));
     }
-    if (st == GR4PM_OK && hipStreamSynchronize(s) != hipSuccess) st = GR4PM_ERR_HIP;
-    if (st != GR4PM_OK) {
-        delete h;
-        return st;
-    }
-    *out = h;
-    return GR4PM_OK;
+    return finish_create(h, out, "crc_check");
 }
 GR4PM_ABI_CATCH
 void gr4pm_crc_check_destroy(gr4pm_crc_check* h)
 try {
     if (!h) return;
-    (void)hipStreamSynchronize(static_cast<hipStream_t>(h->p.stream));
+    (void)hipStreamSynchronize(h->stream);
     delete h;
 }
 GR4PM_ABI_CATCH_VOID
@@ -1168,7 +1147,7 @@ try {
         set_error("null pointer");
         return GR4PM_ERR_INVALID;
     }
-    hipStream_t s = static_cast<hipStream_t>(h->p.stream);
+    hipStream_t s = h->stream;
     std::vector<CrcPacket> pk(n_packets);
     for (size_t i = 0; i < n_packets; ++i) {
         if (packet_len[i] == 0) {

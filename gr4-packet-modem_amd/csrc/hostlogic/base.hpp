@@ -23,7 +23,7 @@ struct CopySpan {
     unsigned long long src, dst, len;
 };
 
-// a complex item as the kernels see it (stream_blocks.hip's `cf` is this type): the planners' tables hold it and the
+// a complex item as the kernels see it (stream_blocks.hpp's `cf` is this type): the planners' tables hold it and the
 // kernels read those tables as they are
 struct cf {
     float x, y;

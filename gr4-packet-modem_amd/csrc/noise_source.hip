@@ -574,12 +574,8 @@ try {
         return GR4PM_ERR_INVALID;
     }
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_noise_source;
+    std::unique_ptr<gr4pm_noise_source> h(new (std::nothrow) gr4pm_noise_source);
     if (!h) return GR4PM_ERR_NOMEM;
-    auto bail = [&](gr4pm_status st) {
-        delete h;
-        return st;
-    };
     h->item = p->item_kind;
     h->type = p->noise_type;
     h->amplitude = p->amplitude;
@@ -613,7 +609,7 @@ try {
     u128 plow;
     if (!charpoly(&plow)) {
         set_error("noise source: the generator's minimal polynomial is not of degree 128");
-        return bail(GR4PM_ERR_INTERNAL);
+        return GR4PM_ERR_INTERNAL;
     }
     u128 xs = 1;
     for (int i = 0; i < h->draws * h->chunk; ++i) xs = mulx(xs, plow);
@@ -647,28 +643,23 @@ try {
             }
         if (via_poly != st2w(a) || via_mat != st2w(a)) {
             set_error("noise source: jump self-check failed");
-            return bail(GR4PM_ERR_INTERNAL);
+            return GR4PM_ERR_INTERNAL;
         }
     }
-    gr4pm_status st;
-    if ((st = h->d_jump.alloc(jump.size())) != GR4PM_OK || (st = h->d_poly.alloc(poly.size())) != GR4PM_OK ||
-        (st = h->d_pos.alloc(2)) != GR4PM_OK || (st = h->d_tile_state.alloc(h->max_tiles)) != GR4PM_OK)
-        return bail(st);
+    GR4PM_TRY(h->d_jump.alloc(jump.size()));
+    GR4PM_TRY(h->d_poly.alloc(poly.size()));
+    GR4PM_TRY(h->d_pos.alloc(2));
+    GR4PM_TRY(h->d_tile_state.alloc(h->max_tiles));
     if (h->gaussian()) {
         const size_t nt = h->max_tiles * kTpb;
-        if ((st = h->d_thread_state.alloc(nt)) != GR4PM_OK || (st = h->d_counts.alloc(nt)) != GR4PM_OK ||
-            (st = h->d_tile_counts.alloc(h->max_tiles)) != GR4PM_OK)
-            return bail(st);
+        GR4PM_TRY(h->d_thread_state.alloc(nt));
+        GR4PM_TRY(h->d_counts.alloc(nt));
+        GR4PM_TRY(h->d_tile_counts.alloc(h->max_tiles));
     }
-    if ((st = h->d_jump.upload(jump.data(), jump.size(), h->stream)) != GR4PM_OK ||
-        (st = h->d_poly.upload(poly.data(), poly.size(), h->stream)) != GR4PM_OK || (st = h->d_pos.zero(h->stream)) != GR4PM_OK)
-        return bail(st);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) {
-        set_error("noise source: hipStreamSynchronize failed at create");
-        return bail(GR4PM_ERR_HIP);
-    }
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_jump.upload(jump.data(), jump.size(), h->stream));
+    GR4PM_TRY(h->d_poly.upload(poly.data(), poly.size(), h->stream));
+    GR4PM_TRY(h->d_pos.zero(h->stream));
+    return finish_create(h, out, "noise source");
 }
 GR4PM_ABI_CATCH
 

@@ -373,12 +373,8 @@ try {
         return GR4PM_ERR_INVALID;
     }
     GR4PM_TRY(require_device());
-    auto* h = new (std::nothrow) gr4pm_packet_transmitter;
+    std::unique_ptr<gr4pm_packet_transmitter> h(new (std::nothrow) gr4pm_packet_transmitter);
     if (!h) return GR4PM_ERR_NOMEM;
-    auto bail = [&](gr4pm_status st) {
-        delete h;
-        return st;
-    };
     h->sps = static_cast<unsigned>(p->samples_per_symbol);
     h->stream_mode = p->stream_mode != 0;
     h->max_packets = p->max_packets;
@@ -390,7 +386,7 @@ try {
     // packet_transmitter_rrc_taps.hpp:8-28: the RRC scaled so that the largest polyphase |tap| sum is 0.9
     std::vector<float> rrc(sps * 11 + 1);
     const size_t n_rrc = gr4pm_firdes_root_raised_cosine(1.0, static_cast<double>(sps), 1.0, 0.35, sps * 11, rrc.data());
-    if (n_rrc == 0) return bail(GR4PM_ERR_NOMEM);
+    if (n_rrc == 0) return GR4PM_ERR_NOMEM;
     float worst = 0.0f;
     for (unsigned j = 0; j < sps; ++j) {
         float acc = 0.0f;
@@ -421,7 +417,7 @@ try {
     for (unsigned k = 1; k < 32; ++k) consts[kConstX2n + k] = multmodp(consts[kConstX2n + k - 1], consts[kConstX2n + k - 1]);
     if (!p->header_generator) {
         set_error("header_generator (96 rows of the LDPC(128,32) generator) is required");
-        return bail(GR4PM_ERR_INVALID);
+        return GR4PM_ERR_INVALID;
     }
     std::copy(p->header_generator, p->header_generator + 96, consts.begin() + kConstGen);
 
@@ -445,24 +441,21 @@ try {
     }
 
     const size_t tiles = 1; // grown per call
-    gr4pm_status st = h->d_consts.alloc(consts.size());
-    if (st == GR4PM_OK) st = h->d_consts.upload(consts.data(), consts.size(), h->stream);
-    if (st == GR4PM_OK) st = h->d_jump.alloc(h->jump.size());
-    if (st == GR4PM_OK) st = h->d_jump.upload(h->jump.data(), h->jump.size(), h->stream);
-    if (st == GR4PM_OK) st = h->d_taps.alloc(taps.size());
-    if (st == GR4PM_OK) st = h->d_taps.upload(taps.data(), taps.size(), h->stream);
-    if (st == GR4PM_OK) st = h->d_scr.alloc(scr.size());
-    if (st == GR4PM_OK) st = h->d_scr.upload(scr.data(), scr.size(), h->stream);
-    if (st == GR4PM_OK) st = h->d_pk.alloc(h->max_packets);
-    if (st == GR4PM_OK) st = h->d_pk.reserve_stage(h->max_packets);
-    if (st == GR4PM_OK) st = h->d_dv.alloc(h->max_packets);
-    if (st == GR4PM_OK) st = h->d_tiles.alloc(tiles);
-    if (st == GR4PM_OK) st = h->d_hist.alloc(h->stride);
-    if (st == GR4PM_OK) st = h->d_hist.zero(h->stream);
-    if (st == GR4PM_OK && hipStreamSynchronize(h->stream) != hipSuccess) st = GR4PM_ERR_HIP;
-    if (st != GR4PM_OK) return bail(st);
-    *out = h;
-    return GR4PM_OK;
+    GR4PM_TRY(h->d_consts.alloc(consts.size()));
+    GR4PM_TRY(h->d_consts.upload(consts.data(), consts.size(), h->stream));
+    GR4PM_TRY(h->d_jump.alloc(h->jump.size()));
+    GR4PM_TRY(h->d_jump.upload(h->jump.data(), h->jump.size(), h->stream));
+    GR4PM_TRY(h->d_taps.alloc(taps.size()));
+    GR4PM_TRY(h->d_taps.upload(taps.data(), taps.size(), h->stream));
+    GR4PM_TRY(h->d_scr.alloc(scr.size()));
+    GR4PM_TRY(h->d_scr.upload(scr.data(), scr.size(), h->stream));
+    GR4PM_TRY(h->d_pk.alloc(h->max_packets));
+    GR4PM_TRY(h->d_pk.reserve_stage(h->max_packets));
+    GR4PM_TRY(h->d_dv.alloc(h->max_packets));
+    GR4PM_TRY(h->d_tiles.alloc(tiles));
+    GR4PM_TRY(h->d_hist.alloc(h->stride));
+    GR4PM_TRY(h->d_hist.zero(h->stream));
+    return finish_create(h, out, "packet_transmitter");
 }
 GR4PM_ABI_CATCH
 

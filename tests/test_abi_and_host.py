@@ -198,7 +198,7 @@ def test_one_exchange_wave_fft_host_emulation(tmp_path):
 
 def test_glibc_sinf_cosf_restatement_matches_the_host_libm(tmp_path):
     """tests/sincosf_glibc_check.c: the double-precision sinf / cosf algorithm the Costas kernels use
-    (csrc/stream_blocks.hip: sincosf_glibc) against the host libm the reference calls, for EVERY float of
+    (csrc/costas_loop.hip: sincosf_glibc) against the host libm the reference calls, for EVERY float of
     |x| <= 3.2 (the loop phase lives in [-pi, pi)), with and without FMA contraction"""
     for fma in (1, 0):
         exe = tmp_path / f"sc{fma}"

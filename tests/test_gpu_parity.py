@@ -1253,7 +1253,7 @@ def test_headline_configuration_at_its_size_pipelined_equals_sequential_and_orac
     SURVEY 8(d) config 2's size): three 2^28-sample calls of NativePacketReceiver(pipelined, output_ring) on the bench's
     own burst ring (headline_ring: two windows presented alternately, each with its history in front), announced two
     calls ahead.  That is the path with the dynamic block hand-out beside the 32-VGPR PLL (k_costas_cap: calls of
-    >= 2^25 symbols while a later batch is in flight, stream_blocks.hip) and the switch to the fast PLL form on the
+    >= 2^25 symbols while a later batch is in flight, costas_loop.hip) and the switch to the fast PLL form on the
     last batch.  Checked against
       (1) the one-stream sequential receiver (pipelined = False: no look-ahead, every stage in the caller's thread, the
           112-VGPR PLL throughout): consumed, detector tags, gate decisions, re-timed tags and all 3 x 2^26 symbols bit
@@ -3463,6 +3463,84 @@ def test_receivers_survive_allocation_failures(pkg, mode):
     assert refused >= in_create // 2, (refused, in_create)
     errors, again = life(None)
     assert not errors and key(again) == key(want)
+
+
+def _alloc_case(pkg, name):
+    """(create, run) of one block for test_block_creates_survive_allocation_failures: run(handle) = the bytes of one
+    process_bulk on 1,024 items (the transmitter, whose input is packets: four of 64 bytes, its max_payload_bytes)"""
+    rng = np.random.default_rng(11)
+    x = dev((rng.standard_normal(1024) + 1j * rng.standard_normal(1024)).astype(np.complex64))
+    if name == "InterpolatingFirFilter":
+        taps = rng.standard_normal(33).astype(np.float32)
+        return (lambda: pkg.InterpolatingFirFilter(4, taps)), (lambda h: host(h.process_bulk(x)).tobytes())
+    if name == "PfbArbResampler":
+        def run(h):
+            y, consumed = h.process_bulk(x)
+            return consumed, host(y).tobytes()
+        return (lambda: pkg.PfbArbResampler(rate=1.25, filter_size=32)), run
+    if name == "SyncwordWipeoff":
+        bipolar = np.where(sig.SYNCWORD == 1, -1.0, 1.0).astype(np.float32)
+        tags = np.zeros(3, dtype=pkg.TAG_DTYPE)
+        tags["index"], tags["flags"] = [10, 500, 1000], pkg.TAG_SYNCWORD  # the last one runs past the call's end
+        return (lambda: pkg.SyncwordWipeoff(bipolar)), (lambda h: host(h.process_bulk(x, tags)).tobytes())
+    if name == "SyncwordDetectionFilter":
+        def run(h):
+            out = torch.zeros(1024, dtype=torch.complex64, device="cuda")
+            r = h.process_bulk(x, out, pkg.TAG_SYNCWORD, headers=[100])
+            return r, host(out).tobytes()
+        return (lambda: pkg.SyncwordDetectionFilter()), run
+    if name == "CrcCheck":
+        def run(h):
+            data = np.random.default_rng(12).integers(0, 256, 1024).astype(np.uint8)
+            for k in (0, 2):  # two of the four packets carry their CRC-32, the others fail the check
+                crc = h.compute(data[256 * k:256 * k + 252])
+                data[256 * k + 252:256 * (k + 1)] = np.frombuffer(crc.to_bytes(4, "big"), np.uint8)
+            out, out_len = h.process_bulk(dev(data), [256] * 4)
+            return host(out).tobytes(), out_len.tobytes()
+        return (lambda: pkg.CrcCheck()), run
+    if name == "NoiseSource":
+        return (lambda: pkg.NoiseSource(max_items=1 << 12)), (lambda h: host(h.process_bulk(1024)).tobytes())
+    assert name == "PacketTransmitter"
+    payloads = [rng.integers(0, 256, 64).astype(np.uint8).tobytes() for _ in range(4)]
+
+    def run(h):
+        y, offsets, lengths = h.process_bulk(payloads)
+        return host(y).tobytes(), offsets.tobytes(), lengths.tobytes()
+    return (lambda: pkg.PacketTransmitter(max_packets=8, max_payload_bytes=256)), run
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["InterpolatingFirFilter", "PfbArbResampler", "SyncwordWipeoff", "SyncwordDetectionFilter",
+                                  "CrcCheck", "NoiseSource", "PacketTransmitter"])
+def test_block_creates_survive_allocation_failures(pkg, name):
+    """The create functions of the blocks that no receiver instantiates (test_receivers_survive_allocation_failures
+    covers the others): every host allocation of one create call fails in turn (gr4pm_test_fail_allocations, TEST build
+    of the library: its own operator new only, nothing happens on the device).  A create that fails raises Gr4pmError
+    with the out-of-memory wording and hands no handle out; afterwards a handle created normally gives, on 1,024 items,
+    the bytes of a handle created before."""
+    pkg = ge.load_test_build()
+    L = pkg.lib()
+    create, run = _alloc_case(pkg, name)
+    c0 = L.gr4pm_test_allocation_count()
+    h = create()
+    in_create = L.gr4pm_test_allocation_count() - c0
+    want = run(h)
+    del h
+    assert in_create >= 1, in_create  # (the handle itself)
+    refused = 0
+    for k in range(in_create):
+        L.gr4pm_test_fail_allocations(k, 1)
+        try:
+            h = create()
+            del h
+        except pkg.Gr4pmError as e:
+            refused += 1
+            assert ("memory" in str(e)) or ("bad_alloc" in str(e)) or ("NOMEM" in str(e)) or ("-4" in str(e)), (k, str(e))
+        finally:
+            L.gr4pm_test_fail_allocations(-1, 0)
+    print(f"{name}: {in_create} allocations in create, {refused} refused")
+    assert refused == in_create, (refused, in_create)  # (these creates have no allocation they can do without)
+    assert run(create()) == want
 
 
 @pytest.mark.gpu
