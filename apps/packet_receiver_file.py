@@ -2,7 +2,8 @@
 """MI355X counterpart of the reference's apps/packet_receiver_file.cpp (apps/README.md:5-24):
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
-                            [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE --decimate N[/M]]
+                            [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
+                            [--scan [--scan-items N]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
 FileSource<c64> freads, file_source.hpp:32,53) at 4 samples/symbol, runs the whole receiver on
@@ -26,6 +27,13 @@ sample) in front of the receiver.  Combines with `--format` (
 counts are then in samples at the receiver's rate.  `--decimate N/M` (N >= M, for instance 25/4 for a 25 Msps file of a
 1 Msym/s carrier): N / M file samples per receiver sample, the same Ddc resampling by M / N in the same pass (DESIGN
 section 18), so any symbol rate lands on the receiver's 4 samples per symbol.
+
+`--scan [--scan-items N]`: where are the carriers?  The first N items of the file (default: all) go through a `Spectrum`
+(gr4pm_spectrum: Welch PSD of 2048 bins with a running maximum per bin; `--format` / `--scale` as
+above), `find_carriers` reads the maximum-hold spectrum, and the app prints one line per carrier (frequency in cycles
+per file sample, bandwidth, snr_db) and exits.  `--tune auto` runs the same scan and tunes to the carrier of greatest
+power.  A scan resolves one bin, 1 / 2048 cycles per sample; the detector behind the Ddc pulls in +-0.00673 / D, so
+`--decimate` of at most 13 keeps a bin inside it.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -61,6 +69,42 @@ def decimation(v):
     if m < 1 or (m > 1 and n < m):
         raise ValueError(f"--decimate: {v!r}: need N >= M >= 1 (file samples per receiver sample)")
     return n, m  # a plain integer goes to the Ddc as it is, which refuses what it cannot take
+
+
+def scan_file(path, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None):
+    """the file's first `items` items (None: all) through a Spectrum: returns (carriers: find_carriers' structured array
+    from the maximum-hold spectrum, the Spectrum's read(), items scanned)"""
+    pkg = pkg or ge.load_package()
+    file_dtype = FILE_DTYPES[fmt]
+    item_bytes = 8 if fmt == "cf32" else 2 * file_dtype.itemsize
+    n_file = os.path.getsize(path) // item_bytes
+    left = n_file if items is None else min(int(items), n_file)
+    sp = pkg.Spectrum()
+    done = 0
+    with open(path, "rb") as fh:
+        while left:
+            n = min(left, chunk_items)
+            host = torch.empty((n,) if fmt == "cf32" else (n, 2), dtype=file_dtype)
+            got = fh.readinto(memoryview(host.numpy().view(np.uint8))) // item_bytes
+            if not got:
+                break
+            x = host[:got].cuda()
+            sp.process_bulk(x) if fmt == "cf32" else sp.process_bulk(x, scale=scale)
+            left -= got
+            done += got
+    r = sp.read()
+    return pkg.find_carriers(r["max_hold"]), r, done
+
+
+def print_carriers(carriers, r, items):
+    print(f"{len(carriers)} carriers in {items} items ({r['segments']} segments of 2048, hop 1024)")
+    for c in carriers:
+        print(f"carrier frequency {c['frequency']:+.6f} bandwidth {c['bandwidth']:.6f} snr_db {c['snr_db']:.1f}")
+
+
+def tune_value(v):
+    """--tune: cycles per file sample, or `auto`"""
+    return "auto" if str(v).lower() == "auto" else float(v)
 
 
 def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
@@ -166,10 +210,24 @@ def main():
     ap.add_argument("--zmq-ports", type=int, nargs=2, metavar=("HEADER", "PAYLOAD"), help="... on these ports instead")
     ap.add_argument("--format", choices=list(FILE_DTYPES), default="cf32", help="the file's items (default: complex64)")
     ap.add_argument("--scale", type=float, help="of an integer format's components (default: 2^-15 for sc16, else 2^-7)")
-    ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Ddc in front)")
+    ap.add_argument("--tune", type=tune_value, metavar="CYCLES_PER_SAMPLE|auto",
+                    help="the carrier's offset in the file (a Ddc in front).  auto: scan the file as --scan does and tune to the "
+                         "carrier of greatest power; the value is as good as the scan's resolution of one PSD bin (1/2048), "
+                         "which stays inside the detector's pull-in range of 0.00673 / D for --decimate <= 13")
+    ap.add_argument("--scan", action="store_true", help="print one line per carrier (frequency, bandwidth, snr_db) and exit")
+    ap.add_argument("--scan-items", type=int, metavar="N", help="scan the first N items of the file only (default: all)")
     ap.add_argument("--decimate", type=decimation, metavar="N[/M]",  # argparse reports a type's ValueError as a usage error
                     help="file samples per receiver sample, an integer or a ratio such as 25/4 (a Ddc in front)")
     a = ap.parse_args()
+    if a.scan or a.tune == "auto":
+        carriers, spectrum, items = scan_file(a.input_file, a.format, a.scale, a.scan_items, a.chunk_items)
+        print_carriers(carriers, spectrum, items)
+        if a.scan:
+            return
+        if not len(carriers):
+            sys.exit("--tune auto: the scan found no carrier")
+        a.tune = float(carriers[int(np.argmax(carriers["power"]))]["frequency"])
+        print(f"--tune auto: {a.tune:+.6f}")
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
                      fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate)

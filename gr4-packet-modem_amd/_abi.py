@@ -220,6 +220,19 @@ class DucRationalParams(C.Structure):
     _fields_ = DucParams._fields_ + [("decimation", C.c_size_t)]
 
 
+class SpectrumParams(C.Structure):
+    _fields_ = [("fft_size", C.c_uint32), ("hop", C.c_uint32), ("window", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class CarrierParams(C.Structure):
+    _fields_ = [("threshold_db", C.c_double), ("max_gap_bins", C.c_size_t), ("min_width_bins", C.c_size_t)]
+
+
+# gr4pm_carrier
+CARRIER_DTYPE = np.dtype([("frequency", "<f8"), ("bandwidth", "<f8"), ("power", "<f8"), ("snr_db", "<f8"),
+                          ("first_bin", "<u8"), ("n_bins", "<u8")])
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -291,6 +304,9 @@ EXPORTS = [
     "gr4pm_duc_taps", "gr4pm_duc_create", "gr4pm_duc_destroy", "gr4pm_duc_reset", "gr4pm_duc_output_items",
     "gr4pm_duc_frequencies", "gr4pm_duc_process",
     "gr4pm_duc_rational_taps", "gr4pm_duc_create_rational",
+    "gr4pm_spectrum_window", "gr4pm_spectrum_float_run", "gr4pm_spectrum_create", "gr4pm_spectrum_destroy",
+    "gr4pm_spectrum_reset", "gr4pm_spectrum_process", "gr4pm_spectrum_process_iq", "gr4pm_spectrum_read",
+    "gr4pm_find_carriers",
 ]
 
 _lib = None
@@ -500,6 +516,17 @@ def lib():
     L.gr4pm_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
     L.gr4pm_ddc_rational_taps.argtypes = [sz, sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_ddc_create_rational.argtypes = [C.POINTER(DdcRationalParams), C.POINTER(vp)]
+    L.gr4pm_spectrum_window.argtypes = [C.c_uint32, vp]
+    L.gr4pm_spectrum_float_run.argtypes = []
+    L.gr4pm_spectrum_float_run.restype = C.c_uint32
+    L.gr4pm_spectrum_create.argtypes = [C.POINTER(SpectrumParams), C.POINTER(vp)]
+    L.gr4pm_spectrum_destroy.argtypes = [vp]
+    L.gr4pm_spectrum_destroy.restype = None
+    L.gr4pm_spectrum_reset.argtypes = [vp]
+    L.gr4pm_spectrum_process.argtypes = [vp, vp, sz]
+    L.gr4pm_spectrum_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz]
+    L.gr4pm_spectrum_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
+    L.gr4pm_find_carriers.argtypes = [vp, sz, C.POINTER(CarrierParams), vp, sz, szp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

@@ -2132,6 +2132,103 @@ class Duc:
         _destroy(self, "gr4pm_duc_destroy")
 
 
+def spectrum_window(n):
+    """gr4pm_spectrum_window: the periodic Hann window 0.5 - 0.5 cos(2 pi i / n) of the Spectrum block, computed in double
+    and rounded to float32 once (host only: works without a GPU)."""
+    out = np.zeros(max(int(n), 1), dtype=np.float32)
+    check(lib().gr4pm_spectrum_window(int(n), _np_ptr(out)), "spectrum_window")
+    return out[: int(n)]
+
+
+def find_carriers(psd, threshold_db=6.0, max_gap_bins=2, min_width_bins=4, cap=None):
+    """gr4pm_find_carriers: the carriers in a power spectrum of n bins in FFT order (host only: works without a GPU).
+    floor: the lower median of the bins; a bin is occupied above floor * 10^(threshold_db / 10); runs of occupied bins on
+    the circle of n bins, merged across at most max_gap_bins free bins, dropped below min_width_bins.  Returns a structured
+    array (frequency: the centroid above the floor in cycles per sample, folded to [-0.5, 0.5); bandwidth; power: the sum
+    above the floor; snr_db: peak over floor; first_bin; n_bins) in ascending frequency.  cap: at most so many rows, the
+    lowest frequencies (None: all; count_carriers() tells how many there are)."""
+    psd = np.ascontiguousarray(psd, dtype=np.float64).reshape(-1)
+    p = _abi.CarrierParams(float(threshold_db), int(max_gap_bins), int(min_width_bins))
+    n = C.c_size_t(0)
+    room = psd.size if cap is None else int(cap)
+    out = np.zeros(max(room, 1), dtype=_abi.CARRIER_DTYPE)
+    check(lib().gr4pm_find_carriers(_np_ptr(psd), psd.size, C.byref(p), _np_ptr(out), room, C.byref(n)), "find_carriers")
+    return out[: min(room, n.value)]
+
+
+def count_carriers(psd, threshold_db=6.0, max_gap_bins=2, min_width_bins=4):
+    """how many carriers find_carriers() finds, whatever its cap (gr4pm_find_carriers with room for none)"""
+    psd = np.ascontiguousarray(psd, dtype=np.float64).reshape(-1)
+    p = _abi.CarrierParams(float(threshold_db), int(max_gap_bins), int(min_width_bins))
+    n = C.c_size_t(0)
+    check(lib().gr4pm_find_carriers(_np_ptr(psd), psd.size, C.byref(p), None, 0, C.byref(n)), "find_carriers")
+    return n.value
+
+
+class Spectrum:
+    """gr4pm_spectrum: Welch power spectral density of one wideband stream on the device.  Segment s is x[s hop .. s hop +
+    2048) of all samples since the handle was made or reset (no zero prehistory); every segment is multiplied by the
+    window (2048 float32; None: spectrum_window(2048), periodic Hann), transformed (forward sign, FFT bin order:
+    .frequencies holds the bin centres in cycles per sample, folded to [-0.5, 0.5)) and its powers are summed and
+    maximised per bin.  process_bulk() takes any number of samples; the samples of the incomplete segment stay on the
+    device.  read() gives mean (white noise of power sigma^2 reads sigma^2 in every bin) and max_hold (for bursts: an
+    average over a mostly silent recording dilutes them).  The handle works on the stream that is current when it is
+    made."""
+
+    fft_size = 2048
+
+    def __init__(self, hop=1024, window=None, fft_size=2048):
+        self.hop, self.fft_size = int(hop), int(fft_size)
+        if window is not None:
+            window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+            if window.size != self.fft_size:
+                raise Gr4pmError(f"Spectrum: a window of {window.size} floats for {self.fft_size} points")
+        self.window = window if window is not None else spectrum_window(self.fft_size)
+        if not (0 <= self.hop < 1 << 32 and 0 <= self.fft_size < 1 << 32):
+            raise Gr4pmError("Spectrum: hop and fft_size must fit 32 unsigned bits")
+        k = np.arange(self.fft_size, dtype=np.float64) / max(self.fft_size, 1)
+        self.frequencies = k - np.floor(k + 0.5)
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.SpectrumParams(self.fft_size, self.hop, _np_ptr(self.window) if window is not None else None, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_spectrum_create(C.byref(p), C.byref(self._h)), "Spectrum")
+
+    def reset(self):
+        """back to the fresh stream: no segments, no carried samples"""
+        check(lib().gr4pm_spectrum_reset(self._h), "Spectrum.reset")
+
+    def process_bulk(self, x, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ: an int16 (sc16),
+        int8 (sc8) or uint8 (cu8) CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it
+        (gr4pm_spectrum_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns self."""
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        if fmt is None:
+            check(lib().gr4pm_spectrum_process(self._h, x.data_ptr(), n_in), "Spectrum.process")
+        else:
+            check(lib().gr4pm_spectrum_process_iq(self._h, x.data_ptr(), fmt, scale, n_in), "Spectrum.process_iq")
+        self._last = x  # the call does not wait: the input lives until the next call or read()
+        return self
+
+    def read(self):
+        """dict(mean: float64[2048], max_hold: float32[2048], segments); waits for the handle's stream"""
+        mean = np.zeros(self.fft_size, dtype=np.float64)
+        max_hold = np.zeros(self.fft_size, dtype=np.float32)
+        n = C.c_uint64(0)
+        check(lib().gr4pm_spectrum_read(self._h, _np_ptr(mean), _np_ptr(max_hold), C.byref(n)), "Spectrum.read")
+        self._last = None
+        return dict(mean=mean, max_hold=max_hold, segments=n.value)
+
+    def carriers(self, which="max_hold", threshold_db=6.0, max_gap_bins=2, min_width_bins=4):
+        """find_carriers() on read()[which] (which: "max_hold" or "mean")"""
+        if which not in ("max_hold", "mean"):
+            raise Gr4pmError(f"Spectrum.carriers: which is {which!r}, not 'max_hold' or 'mean'")
+        return find_carriers(self.read()[which], threshold_db, max_gap_bins, min_width_bins)
+
+    def __del__(self):
+        _destroy(self, "gr4pm_spectrum_destroy")
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

@@ -1278,6 +1278,75 @@ gr4pm_status gr4pm_iq_unpack(const void* in, size_t in_stride, int format, float
 gr4pm_status gr4pm_iq_pack(const gr4pm_c64* in, size_t in_stride, size_t rows, size_t n, int format, float gain,
                            void* out, size_t out_stride, unsigned long long* clipped, void* stream);
 
+/* ====================================================================================
+ * Spectrum -- Welch power spectral density of one wideband stream on the device, and a carrier finder
+ * made from it (the project's own block).  The stream is x[0], x[1], ... over all
+ * calls since create or reset; N = fft_size = 2048, 1 <= hop <= N:
+ *     segment s        x[s hop .. s hop + N); no zero prehistory: after T samples there are
+ *                      T < N ? 0 : (T - N) / hop + 1 segments
+ *     X_s            = FFT_N(w . x_s)     forward sign, unnormalised, FFT bin order (bin k: +k / N cycles
+ *                                         per sample, k > N / 2: negative frequencies)
+ *     acc[k]         = sum_s |X_s[k]|^2
+ *     mean[k]        = acc[k] / (segments sum_n w[n]^2)
+ *     max_hold[k]    = max_s |X_s[k]|^2 / sum_n w[n]^2
+ * so white noise with E|x|^2 = sigma^2 reads sigma^2 in every bin of mean.  A wave transforms a run of at
+ * most gr4pm_spectrum_float_run() consecutive segments and sums their powers in float32; the runs' sums
+ * are added in double, in stream order, with no floating-point atomic: the same calls give the same
+ * bits.  max_hold does not depend on how the stream is cut into calls at all.  process() takes any n,
+ * consumes all of it, enqueues on the handle's stream and does not wait; the samples of the segment that
+ * is not complete yet (fewer than N) stay on the device as complex64.
+ * ================================================================================== */
+typedef struct gr4pm_spectrum gr4pm_spectrum;
+typedef struct {
+    uint32_t fft_size;          /* N: 2048 */
+    uint32_t hop;               /* 1 .. N */
+    const float* window;        /* host: N floats, copied at create (NULL: the periodic Hann window) */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_spectrum_params;
+/* the periodic Hann window 0.5 - 0.5 cos(2 pi i / n), computed in double and rounded to float once (host only) */
+gr4pm_status gr4pm_spectrum_window(uint32_t n, float* out);
+/* segments a wave sums in float32 before its sum goes on in double: 64 */
+uint32_t gr4pm_spectrum_float_run(void);
+/* fft_size != 2048, hop == 0, hop > N or a window with a non-finite value: GR4PM_ERR_INVALID, no handle */
+gr4pm_status gr4pm_spectrum_create(const gr4pm_spectrum_params* params, gr4pm_spectrum** out);
+void gr4pm_spectrum_destroy(gr4pm_spectrum* h);
+/* back to the fresh stream: no segments, no carried samples */
+gr4pm_status gr4pm_spectrum_reset(gr4pm_spectrum* h);
+/* x: DEVICE, n complex64 samples (any number, 0 and 1 included; all are consumed) */
+gr4pm_status gr4pm_spectrum_process(gr4pm_spectrum* h, const void* x, size_t n);
+/* x: DEVICE, n items of an integer IQ format (gr4pm_iq_format; scale 0: the format's default).  The result of
+ * gr4pm_spectrum_process on gr4pm_iq_unpack(x) bit for bit: the samples are converted where the kernel loads
+ * them, the carried samples stay complex64, so calls of any format may be mixed on one handle. */
+gr4pm_status gr4pm_spectrum_process_iq(gr4pm_spectrum* h, const void* x, int format, float scale, size_t n);
+/* mean: N doubles, max_hold: N floats (host; either may be NULL), *segments: the count (may be NULL).  Waits
+ * for the handle's stream; the divisions happen in double on the host.  With no segment yet: zeros. */
+gr4pm_status gr4pm_spectrum_read(gr4pm_spectrum* h, double* mean, float* max_hold, uint64_t* segments);
+
+/* Carriers from a power spectrum of n bins in FFT order, host only.  floor: the lower median, element
+ * (n - 1) / 2 of the sorted bins.  A bin is occupied when it exceeds floor 10^(threshold_db / 10).  Runs of
+ * occupied bins are taken on the circle of n bins (a carrier across +-0.5 is one run); runs separated by at
+ * most max_gap_bins free bins merge, then runs shorter than min_width_bins are dropped.  Per run of n_bins
+ * bins from first_bin, over i = 0 .. n_bins - 1 in double, in index order:
+ *     c = sum i (psd - floor) / sum (psd - floor),  frequency = (first_bin + c) / n folded to [-0.5, 0.5),
+ *     bandwidth = n_bins / n,  power = sum (psd - floor),  snr_db = 10 log10(peak / floor)
+ * out: room for cap carriers; the first min(cap, *count) in ascending frequency are written, *count is the
+ * number found.  n == 0, a NULL psd or count, or threshold_db <= 0 (or NaN): GR4PM_ERR_INVALID. */
+typedef struct {
+    double threshold_db;        /* > 0 */
+    size_t max_gap_bins;
+    size_t min_width_bins;
+} gr4pm_carrier_params;
+typedef struct {
+    double frequency;           /* cycles per sample, [-0.5, 0.5) */
+    double bandwidth;           /* cycles per sample */
+    double power;               /* above the floor, summed over the run */
+    double snr_db;
+    uint64_t first_bin;
+    uint64_t n_bins;
+} gr4pm_carrier;
+gr4pm_status gr4pm_find_carriers(const double* psd, size_t n, const gr4pm_carrier_params* params, gr4pm_carrier* out,
+                                 size_t cap, size_t* count);
+
 #ifdef __cplusplus
 }
 #endif

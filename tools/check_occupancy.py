@@ -121,6 +121,9 @@ BUDGETS = [
     # its rational form: one real-tap accumulator per lane, the branch's taps in SGPRs, eight waves per SIMD (DESIGN
     # section 19)
     (r"k_duc_rational", dict(vgpr=64, scratch=0)),
+    # the Spectrum block: the correlator's eight exchange buffers and twiddles plus 8 KiB of window, two waves per SIMD
+    # 
+    (r"k_spectrum_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
 ]
 
 
