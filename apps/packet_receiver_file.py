@@ -3,7 +3,7 @@
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
                             [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
-                            [--scan [--scan-items N]]
+                            [--scan [--scan-items N] [--bursts] [--waterfall FILE.npy [--waterfall-average R]]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
 FileSource<c64> freads, file_source.hpp:32,53) at 4 samples/symbol, runs the whole receiver on
@@ -34,6 +34,14 @@ above), `find_carriers` reads the maximum-hold spectrum, and the app prints one 
 per file sample, bandwidth, snr_db) and exits.  `--tune auto` runs the same scan and tunes to the carrier of greatest
 power.  A scan resolves one bin, 1 / 2048 cycles per sample; the detector behind the Ddc pulls in +-0.00673 / D, so
 `--decimate` of at most 13 keeps a bin inside it.
+
+`--scan --bursts`: and when are they on the air?  After the carrier lines the scanned items go through a `Spectrogram`
+(gr4pm_spectrogram: PSD rows over time, hop 1024) chunk by chunk; the power of every carrier's band
+(`band_power`, on the device) is appended per chunk on the host, `find_bursts` reads each carrier's series, and the app
+prints one line per burst: `burst frequency F start S end E snr_db X`, S and E (exclusive) in file samples, a burst's
+edges being as fine as a row (`--waterfall-average` rows of hop 1024, 2048 samples wide).  `--waterfall FILE.npy` writes
+the rows of the scanned items (float32 [rows, 2048], FFT bin order, mean of `--waterfall-average` R segments per row,
+default 1) for a waterfall plot.  `--scan` alone prints what it always printed.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -71,16 +79,13 @@ def decimation(v):
     return n, m  # a plain integer goes to the Ddc as it is, which refuses what it cannot take
 
 
-def scan_file(path, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None):
-    """the file's first `items` items (None: all) through a Spectrum: returns (carriers: find_carriers' structured array
-    from the maximum-hold spectrum, the Spectrum's read(), items scanned)"""
-    pkg = pkg or ge.load_package()
+def file_chunks(path, fmt="cf32", items=None, chunk_items=1 << 24):
+    """the file's first `items` items (None: all) as device tensors of at most chunk_items items: complex64 [n], or the
+    integers as they are, [n, 2]"""
     file_dtype = FILE_DTYPES[fmt]
     item_bytes = 8 if fmt == "cf32" else 2 * file_dtype.itemsize
     n_file = os.path.getsize(path) // item_bytes
     left = n_file if items is None else min(int(items), n_file)
-    sp = pkg.Spectrum()
-    done = 0
     with open(path, "rb") as fh:
         while left:
             n = min(left, chunk_items)
@@ -88,12 +93,44 @@ def scan_file(path, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg
             got = fh.readinto(memoryview(host.numpy().view(np.uint8))) // item_bytes
             if not got:
                 break
-            x = host[:got].cuda()
-            sp.process_bulk(x) if fmt == "cf32" else sp.process_bulk(x, scale=scale)
+            yield host[:got].cuda()
             left -= got
-            done += got
+
+
+def scan_file(path, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None):
+    """the file's first `items` items (None: all) through a Spectrum: returns (carriers: find_carriers' structured array
+    from the maximum-hold spectrum, the Spectrum's read(), items scanned)"""
+    pkg = pkg or ge.load_package()
+    sp = pkg.Spectrum()
+    done = 0
+    for x in file_chunks(path, fmt, items, chunk_items):
+        sp.process_bulk(x) if fmt == "cf32" else sp.process_bulk(x, scale=scale)
+        done += x.shape[0]
     r = sp.read()
     return pkg.find_carriers(r["max_hold"]), r, done
+
+
+def scan_rows(path, carriers, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, average=1, keep_rows=False, pkg=None):
+    """the same items through a Spectrogram (hop 1024, the mean of `average` segments per row), chunk by chunk: returns
+    (the Spectrogram, float64 [len(carriers), rows]: the power of every carrier's band per row, the rows themselves as
+    float32 [rows, 2048] if keep_rows else None)"""
+    pkg = pkg or ge.load_package()
+    sg = pkg.Spectrogram(hop=1024, average=average)
+    power, rows = [np.zeros((len(carriers), 0))], [np.zeros((0, sg.fft_size), dtype=np.float32)]
+    for x in file_chunks(path, fmt, items, chunk_items):
+        r = sg.process_bulk(x) if fmt == "cf32" else sg.process_bulk(x, scale=scale)
+        if len(carriers):
+            power.append(np.concatenate([sg.band_power(r, carriers[i:i + 64]).cpu().numpy()  # a call takes 64 bands
+                                         for i in range(0, len(carriers), 64)]))
+        if keep_rows:
+            rows.append(r.cpu().numpy())
+    return sg, np.concatenate(power, axis=1), np.concatenate(rows) if keep_rows else None
+
+
+def print_bursts(sg, carriers, power):
+    for c, p in zip(carriers, power):
+        for b in (sg.bursts(p) if p.size else []):
+            print(f"burst frequency {c['frequency']:+.6f} start {b['start_sample']} end {b['end_sample']} snr_db {b['snr_db']:.1f}")
 
 
 def print_carriers(carriers, r, items):
@@ -216,12 +253,26 @@ def main():
                          "which stays inside the detector's pull-in range of 0.00673 / D for --decimate <= 13")
     ap.add_argument("--scan", action="store_true", help="print one line per carrier (frequency, bandwidth, snr_db) and exit")
     ap.add_argument("--scan-items", type=int, metavar="N", help="scan the first N items of the file only (default: all)")
+    ap.add_argument("--bursts", action="store_true",
+                    help="with --scan: a second pass through a Spectrogram, then one line per burst of every carrier "
+                         "(frequency, start and end in file samples, snr_db)")
+    ap.add_argument("--waterfall", metavar="FILE.npy", help="with --scan: write the Spectrogram's rows (float32 [rows, 2048], FFT bin order)")
+    ap.add_argument("--waterfall-average", type=int, default=1, metavar="R", help="segments per row of --bursts and --waterfall (1 .. 64, default 1)")
     ap.add_argument("--decimate", type=decimation, metavar="N[/M]",  # argparse reports a type's ValueError as a usage error
                     help="file samples per receiver sample, an integer or a ratio such as 25/4 (a Ddc in front)")
     a = ap.parse_args()
+    if (a.bursts or a.waterfall) and not a.scan:
+        ap.error("--bursts and --waterfall belong to --scan")
     if a.scan or a.tune == "auto":
         carriers, spectrum, items = scan_file(a.input_file, a.format, a.scale, a.scan_items, a.chunk_items)
         print_carriers(carriers, spectrum, items)
+        if a.scan and (a.bursts or a.waterfall):
+            sg, power, rows = scan_rows(a.input_file, carriers if a.bursts else carriers[:0], a.format, a.scale, a.scan_items,
+                                        a.chunk_items, a.waterfall_average, keep_rows=bool(a.waterfall))
+            if a.bursts:
+                print_bursts(sg, carriers, power)
+            if a.waterfall:
+                np.save(a.waterfall, rows)
         if a.scan:
             return
         if not len(carriers):

@@ -233,6 +233,21 @@ CARRIER_DTYPE = np.dtype([("frequency", "<f8"), ("bandwidth", "<f8"), ("power", 
                           ("first_bin", "<u8"), ("n_bins", "<u8")])
 
 
+class SpectrogramParams(C.Structure):
+    _fields_ = [("fft_size", C.c_uint32), ("hop", C.c_uint32), ("average", C.c_uint32), ("detector", C.c_uint32),
+                ("window", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class BurstParams(C.Structure):
+    _fields_ = [("threshold_db", C.c_double), ("floor", C.c_double), ("max_gap_rows", C.c_size_t), ("min_rows", C.c_size_t)]
+
+
+SPECTROGRAM_DETECTORS = {"mean": 0, "max": 1}  # GR4PM_SPECTROGRAM_MEAN, GR4PM_SPECTROGRAM_MAX
+# gr4pm_band, gr4pm_burst
+BAND_DTYPE = np.dtype([("first_bin", "<u4"), ("n_bins", "<u4")])
+BURST_DTYPE = np.dtype([("first_row", "<u8"), ("n_rows", "<u8"), ("peak_row", "<u8"), ("power", "<f8"), ("snr_db", "<f8")])
+
+
 # every symbol include/gr4pm_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "gr4pm_last_error", "gr4pm_version", "gr4pm_device_count", "gr4pm_set_deferred_sync", "gr4pm_sincosf", "gr4pm_costas_phase_wrap",
@@ -307,6 +322,8 @@ EXPORTS = [
     "gr4pm_spectrum_window", "gr4pm_spectrum_float_run", "gr4pm_spectrum_create", "gr4pm_spectrum_destroy",
     "gr4pm_spectrum_reset", "gr4pm_spectrum_process", "gr4pm_spectrum_process_iq", "gr4pm_spectrum_read",
     "gr4pm_find_carriers",
+    "gr4pm_spectrogram_create", "gr4pm_spectrogram_destroy", "gr4pm_spectrogram_reset", "gr4pm_spectrogram_rows",
+    "gr4pm_spectrogram_process", "gr4pm_spectrogram_process_iq", "gr4pm_spectrogram_band_power", "gr4pm_find_bursts",
 ]
 
 _lib = None
@@ -527,6 +544,15 @@ def lib():
     L.gr4pm_spectrum_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz]
     L.gr4pm_spectrum_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
     L.gr4pm_find_carriers.argtypes = [vp, sz, C.POINTER(CarrierParams), vp, sz, szp]
+    L.gr4pm_spectrogram_create.argtypes = [C.POINTER(SpectrogramParams), C.POINTER(vp)]
+    L.gr4pm_spectrogram_destroy.argtypes = [vp]
+    L.gr4pm_spectrogram_destroy.restype = None
+    L.gr4pm_spectrogram_reset.argtypes = [vp]
+    L.gr4pm_spectrogram_rows.argtypes = [vp, sz, szp]
+    L.gr4pm_spectrogram_process.argtypes = [vp, vp, sz, vp, sz, szp]
+    L.gr4pm_spectrogram_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, szp]
+    L.gr4pm_spectrogram_band_power.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.gr4pm_find_bursts.argtypes = [vp, sz, C.POINTER(BurstParams), vp, sz, szp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

@@ -2229,6 +2229,133 @@ class Spectrum:
         _destroy(self, "gr4pm_spectrum_destroy")
 
 
+def find_bursts(power, threshold_db=6.0, max_gap_rows=1, min_rows=2, floor=None, cap=None):
+    """gr4pm_find_bursts: the bursts in a band's power over time, rows in time order (host only: works without a GPU).
+    floor: the noise level of a row (None: the lower median of the rows, which holds while the band is silent in more
+    than half of them); a row is active above floor * 10^(threshold_db / 10); runs of active rows, merged across at most
+    max_gap_rows inactive rows, dropped below min_rows.  Returns a structured array (first_row, n_rows, peak_row; power:
+    the mean above the floor; snr_db: peak over floor) in ascending time.  cap: at most so many (None: all)."""
+    power = np.ascontiguousarray(power, dtype=np.float64).reshape(-1)
+    p = _abi.BurstParams(float(threshold_db), 0.0 if floor is None else float(floor), int(max_gap_rows), int(min_rows))
+    n = C.c_size_t(0)
+    room = power.size if cap is None else int(cap)
+    out = np.zeros(max(room, 1), dtype=_abi.BURST_DTYPE)
+    check(lib().gr4pm_find_bursts(_np_ptr(power), power.size, C.byref(p), _np_ptr(out), room, C.byref(n)), "find_bursts")
+    return out[: min(room, n.value)]
+
+
+class Spectrogram:
+    """gr4pm_spectrogram: PSD rows over time of one wideband stream on the device.  The segments are the Spectrum's
+    (segment s is x[s hop .. s hop + 2048) of all samples since the handle was made or reset, windowed and transformed);
+    row t is the mean (detector "mean") or the maximum ("max") per bin of the powers of the `average` = R segments
+    t R .. t R + R - 1, divided by the window's power, so white noise of power sigma^2 reads sigma^2 in every bin of a
+    mean row.  Row t covers the samples [t row_advance, t row_advance + row_span).  process_bulk() takes any number of
+    samples and returns the rows they complete; the samples of the incomplete segment and the sums of the incomplete row
+    stay on the device, and the rows do not depend on how the stream is cut into calls, bit for bit.  The handle works
+    on the stream that is current when it is made."""
+
+    fft_size = 2048
+
+    def __init__(self, hop=1024, average=1, detector="mean", window=None, fft_size=2048):
+        self.hop, self.average, self.fft_size = int(hop), int(average), int(fft_size)
+        if detector not in _abi.SPECTROGRAM_DETECTORS:
+            raise Gr4pmError(f"Spectrogram: detector is {detector!r}, not 'mean' or 'max'")
+        self.detector = detector
+        if window is not None:
+            window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+            if window.size != self.fft_size:
+                raise Gr4pmError(f"Spectrogram: a window of {window.size} floats for {self.fft_size} points")
+        self.window = window if window is not None else spectrum_window(self.fft_size)
+        if not all(0 <= v < 1 << 32 for v in (self.hop, self.average, self.fft_size)):
+            raise Gr4pmError("Spectrogram: hop, average and fft_size must fit 32 unsigned bits")
+        k = np.arange(self.fft_size, dtype=np.float64) / max(self.fft_size, 1)
+        self.frequencies = k - np.floor(k + 0.5)
+        self.row_advance = self.average * self.hop
+        self.row_span = (self.average - 1) * self.hop + self.fft_size
+        self.rows_done = 0
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.SpectrogramParams(self.fft_size, self.hop, self.average, _abi.SPECTROGRAM_DETECTORS[detector],
+                                   _np_ptr(self.window) if window is not None else None, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_spectrogram_create(C.byref(p), C.byref(self._h)), "Spectrogram")
+
+    def reset(self):
+        """back to the fresh stream: no segments, no carried samples, no carried row"""
+        check(lib().gr4pm_spectrogram_reset(self._h), "Spectrogram.reset")
+        self.rows_done = 0
+
+    def rows(self, n):
+        """gr4pm_spectrogram_rows: the rows a call of n samples would complete now"""
+        r = C.c_size_t(0)
+        check(lib().gr4pm_spectrogram_rows(self._h, int(n), C.byref(r)), "Spectrogram.rows")
+        return r.value
+
+    def process_bulk(self, x, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ: an int16 (sc16),
+        int8 (sc8) or uint8 (cu8) CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it
+        (the same rows bit for bit; calls of any format mix on one handle).  Returns the rows the call completes, a CUDA
+        float32 tensor [rows, 2048] in FFT bin order (zero rows for a call that completes none).  Does not wait."""
+        torch = _torch()
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        want = self.rows(n_in)
+        out = torch.empty((want, self.fft_size), dtype=torch.float32, device=x.device)
+        got = C.c_size_t(0)
+        if fmt is None:
+            check(lib().gr4pm_spectrogram_process(self._h, x.data_ptr(), n_in, out.data_ptr(), want, C.byref(got)),
+                  "Spectrogram.process")
+        else:
+            check(lib().gr4pm_spectrogram_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), want, C.byref(got)),
+                  "Spectrogram.process_iq")
+        if got.value != want:
+            raise Gr4pmError(f"Spectrogram: the call made {got.value} rows, gr4pm_spectrogram_rows said {want}")
+        self._last = x  # the call does not wait: the input lives until the next call
+        self.rows_done += want
+        return out
+
+    def band_power(self, rows, bands):
+        """gr4pm_spectrogram_band_power: rows: a CUDA float32 tensor [n, 2048] (process_bulk's, or several of them
+        joined); bands: find_carriers' structured array (its first_bin and n_bins) or a list of (first_bin, n_bins), at
+        most 64, the bins first_bin .. first_bin + n_bins - 1 mod 2048.  Returns a CUDA float64 tensor [K, n]: the sum of
+        each band's bins of each row, added in double in a fixed order (the same call gives the same bits)."""
+        torch = _torch()
+        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2
+                and rows.shape[1] == self.fft_size and rows.is_contiguous()):
+            raise TypeError(f"rows must be a contiguous CUDA float32 tensor [n, {self.fft_size}]")
+        if isinstance(bands, np.ndarray) and bands.dtype.names and {"first_bin", "n_bins"} <= set(bands.dtype.names):
+            pairs = [(int(b["first_bin"]), int(b["n_bins"])) for b in bands.reshape(-1)]
+        else:
+            pairs = [(int(a), int(b)) for a, b in bands]
+        if not all(0 <= a < 1 << 32 and 0 <= b < 1 << 32 for a, b in pairs):
+            raise Gr4pmError("Spectrogram.band_power: first_bin and n_bins must fit 32 unsigned bits")
+        b = np.array(pairs, dtype=_abi.BAND_DTYPE).reshape(-1)
+        if torch.cuda.current_stream(rows.device).cuda_stream != self._stream:
+            _inputs_ready(rows)
+        out = torch.empty((len(pairs), rows.shape[0]), dtype=torch.float64, device=rows.device)
+        check(lib().gr4pm_spectrogram_band_power(self._h, rows.data_ptr(), rows.shape[0], _np_ptr(b) if len(pairs) else None,
+                                                 len(pairs), out.data_ptr()), "Spectrogram.band_power")
+        return out
+
+    def bursts(self, power_row, first_row=0, **kw):
+        """find_bursts(power_row, **kw) for one row of band_power() (a tensor or an array; row 0 of it is the stream's row
+        first_row), with the samples each burst covers: a structured array of find_bursts' fields plus start_sample =
+        (first_row + burst first_row) row_advance and end_sample = (first_row + burst first_row + n_rows - 1)
+        row_advance + row_span (exclusive)."""
+        if hasattr(power_row, "cpu"):
+            power_row = power_row.cpu().numpy()
+        found = find_bursts(power_row, **kw)
+        out = np.zeros(len(found), dtype=np.dtype(_abi.BURST_DTYPE.descr + [("start_sample", "<u8"), ("end_sample", "<u8")]))
+        for f in _abi.BURST_DTYPE.names:
+            out[f] = found[f]
+        first = int(first_row) + found["first_row"].astype(np.uint64)
+        out["start_sample"] = first * np.uint64(self.row_advance)
+        out["end_sample"] = (first + found["n_rows"] - np.uint64(1)) * np.uint64(self.row_advance) + np.uint64(self.row_span)
+        return out
+
+    def __del__(self):
+        _destroy(self, "gr4pm_spectrogram_destroy")
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

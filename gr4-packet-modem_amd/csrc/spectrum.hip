@@ -26,8 +26,7 @@
 // hop but end N later, which is no multiple of hop in general.
 // Built with FFT_FLAGS: the transform may contract to FMA.  iq_format.hpp's unpack is one product (cu8: a difference, then
 // one product), in which there is nothing to contract, so it is gr4pm_iq_unpack's expression bit for bit here too.
-#include "stream_tail.hpp"
-#include "correlate_w64.hpp"
+#include "spectrum_segment.hpp"
 #include "hostlogic/carrier_find.hpp"
 #include "hostlogic/spectrum_plan.hpp"
 
@@ -43,7 +42,6 @@ using gr4pm::hostlogic::SpectrumPlan;
 
 constexpr uint32_t kFloatRun = 64; // segments a wave sums in float32: the error bound of DESIGN.md section 20 rests on it
 constexpr size_t kN = kFftN;
-constexpr size_t kMaxWaves = 2048; // of one launch: 32 MiB of partials
 
 struct SpecArgs {
     const float2* hist; // the H carried samples in front of in[0]
@@ -89,31 +87,9 @@ __global__ __launch_bounds__(kW64Threads, 2) void k_spectrum_w64(SpecArgs a)
         sum[j] = 0.0f;
         mx[j] = 0.0f;
     }
-    // segment `seg` of the launch: virtual items v0 + lane + 64 j
+    // segment `seg` of the launch begins at the virtual item (seg0 + seg) hop
     auto load_half = [&](cf* dst, uint64_t seg, int h) {
-        const size_t v0 = (a.seg0 + seg) * a.hop;
-        int ln = lane;
-        asm volatile("" : "+v"(ln)); // addresses are formed here, not hoisted out of the segment loop
-        if (v0 >= a.H) { // uniform: the whole segment lies in the input
-            const size_t i0 = v0 - a.H + ln;
-            if constexpr (F == iq::kC64) {
-                const cf* x = static_cast<const cf*>(a.in) + i0;
-#pragma unroll
-                for (int j = 16 * h; j < 16 * h + 16; ++j) dst[j] = x[64 * j];
-            } else {
-#pragma unroll
-                for (int j = 16 * h; j < 16 * h + 16; ++j) {
-                    const float2 s = iq::unpack_item<F>(iq::load_item<F>(a.in, i0 + 64 * j), a.scale);
-                    dst[j] = mk(s.x, s.y);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 16 * h; j < 16 * h + 16; ++j) {
-                const float2 s = iq::vsample<F>(a.hist, a.H, a.in, a.scale, v0 + ln + 64 * j);
-                dst[j] = mk(s.x, s.y);
-            }
-        }
+        load_half_segment<F>(dst, a.hist, a.H, a.in, a.scale, (a.seg0 + seg) * a.hop, lane, h);
     };
 
     cf X[32];
@@ -180,26 +156,17 @@ __global__ __launch_bounds__(64) void k_spectrum_reduce(const float* __restrict_
     mx[k] = m;
 }
 
-void hann(uint32_t n, float* out)
-{
-    for (uint32_t i = 0; i < n; ++i)
-        out[i] = static_cast<float>(0.5 - 0.5 * std::cos(2.0 * M_PI * static_cast<double>(i) / static_cast<double>(n)));
-}
-
 } // namespace
 
 struct gr4pm_spectrum {
     size_t hop = 0;
     uint64_t taken = 0;    // T: samples since create or reset
     uint64_t segments = 0;
-    double window_power = 0.0; // sum w[n]^2
-    size_t max_waves = kMaxWaves;
     hipStream_t stream = nullptr;
-    gr4pm::StreamTail tail; // keep = 0, frame = N: the samples of the incomplete segment
-    gr4pm::DevBuf<float> d_window, d_part, d_max;
+    gr4pm::SegmentTransform tf; // the window and its power, the transform's tables, the waves of one launch
+    gr4pm::StreamTail tail;     // keep = 0, frame = N: the samples of the incomplete segment
+    gr4pm::DevBuf<float> d_part, d_max;
     gr4pm::DevBuf<double> d_acc;
-    gr4pm::DevBuf<float4> d_tT;
-    gr4pm::DevBuf<cf> d_cc;
 };
 
 // process() and process_iq(): format iq::kC64 for complex64 samples
@@ -220,13 +187,13 @@ static gr4pm_status process_any(gr4pm_spectrum* h, const void* x, int format, fl
                                 p.tail_new, p.tail_new};
     SpecArgs a = {};
     a.hist = t.hist, a.in = x, a.H = p.tail;
-    a.window = h->d_window.p, a.tT = h->d_tT.p, a.cc = h->d_cc.p, a.part = h->d_part.p;
+    a.window = h->tf.d_window.p, a.tT = h->tf.d_tT.p, a.cc = h->tf.d_cc.p, a.part = h->d_part.p;
     a.hop = static_cast<uint32_t>(h->hop), a.scale = scale;
     iq::with_format(format, [&](auto f) {
         for (size_t done = 0; done < p.n_segments;) {
             const size_t left = p.n_segments - done;
-            const size_t run = hostlogic::spectrum_run(left, h->max_waves, kFloatRun);
-            const size_t waves = std::min(h->max_waves, (left + run - 1) / run);
+            const size_t run = hostlogic::spectrum_run(left, h->tf.max_waves, kFloatRun);
+            const size_t waves = std::min(h->tf.max_waves, (left + run - 1) / run);
             const size_t segs = std::min(left, waves * run);
             a.seg0 = done, a.n_seg = static_cast<uint32_t>(segs), a.run = static_cast<uint32_t>(run);
             hipLaunchKernelGGL(k_spectrum_w64<decltype(f)::value>, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)),
@@ -272,46 +239,14 @@ try {
         set_error("spectrum: hop %u, need 1 .. %zu", p->hop, kN);
         return GR4PM_ERR_INVALID;
     }
-    std::vector<float> window(kN);
-    if (p->window)
-        std::copy(p->window, p->window + kN, window.begin());
-    else
-        hann(kN, window.data());
-    double power = 0.0;
-    for (size_t i = 0; i < kN; ++i) {
-        if (!std::isfinite(window[i])) {
-            set_error("spectrum: window[%zu] is not finite", i);
-            return GR4PM_ERR_INVALID;
-        }
-        power += static_cast<double>(window[i]) * static_cast<double>(window[i]);
-    }
-    GR4PM_TRY(require_device());
     std::unique_ptr<gr4pm_spectrum> h(new (std::nothrow) gr4pm_spectrum);
     if (!h) return GR4PM_ERR_NOMEM;
     h->hop = p->hop;
-    h->window_power = power;
     h->stream = static_cast<hipStream_t>(p->stream);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        h->max_waves = std::min(kMaxWaves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
-    std::vector<float4> tT(kW64TwFloat4);
-    std::vector<cf> cc(64);
-    build_w64_tables(
-        [](int k) {
-            const double ang = -2.0 * M_PI * k / kFftN;
-            return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
-        },
-        tT.data(), cc.data());
-    GR4PM_TRY(h->d_window.alloc(kN));
-    GR4PM_TRY(h->d_tT.alloc(tT.size()));
-    GR4PM_TRY(h->d_cc.alloc(cc.size()));
-    GR4PM_TRY(h->d_part.alloc(h->max_waves * 2 * kN));
+    GR4PM_TRY(h->tf.create(p->window, h->stream, "spectrum"));
+    GR4PM_TRY(h->d_part.alloc(h->tf.max_waves * 2 * kN));
     GR4PM_TRY(h->d_acc.alloc(kN));
     GR4PM_TRY(h->d_max.alloc(kN));
-    GR4PM_TRY(h->d_window.upload(window.data(), kN, h->stream));
-    GR4PM_TRY(h->d_tT.upload(tT.data(), tT.size(), h->stream));
-    GR4PM_TRY(h->d_cc.upload(cc.data(), cc.size(), h->stream));
     GR4PM_TRY(h->d_acc.zero(h->stream));
     GR4PM_TRY(h->d_max.zero(h->stream));
     GR4PM_TRY(h->tail.alloc(0, kN, 1, h->stream));
@@ -364,10 +299,10 @@ try {
     GR4PM_HIP_TRY(hipMemcpyAsync(mx.data(), h->d_max.p, kN * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     GR4PM_HIP_TRY(hipStreamSynchronize(h->stream));
     if (segments) *segments = h->segments;
-    const double per_mean = static_cast<double>(h->segments) * h->window_power;
+    const double per_mean = static_cast<double>(h->segments) * h->tf.window_power;
     for (size_t k = 0; k < kN; ++k) {
         if (mean) mean[k] = h->segments ? acc[k] / per_mean : 0.0;
-        if (max_hold) max_hold[k] = h->segments ? static_cast<float>(static_cast<double>(mx[k]) / h->window_power) : 0.0f;
+        if (max_hold) max_hold[k] = h->segments ? static_cast<float>(static_cast<double>(mx[k]) / h->tf.window_power) : 0.0f;
     }
     return GR4PM_OK;
 }

@@ -1347,6 +1347,88 @@ typedef struct {
 gr4pm_status gr4pm_find_carriers(const double* psd, size_t n, const gr4pm_carrier_params* params, gr4pm_carrier* out,
                                  size_t cap, size_t* count);
 
+/* ====================================================================================
+ * Spectrogram -- PSD rows over time of one wideband stream on the device, the power of bands of those rows,
+ * and a burst finder made from it (the project's own block).  Segments and X_s are
+ * exactly the Spectrum's above (N = fft_size = 2048, 1 <= hop <= N, no zero prehistory).  With
+ * R = average, 1 <= R <= gr4pm_spectrum_float_run() (64):
+ *     row t            is made of the segments t R .. t R + R - 1 and exists once segment t R + R - 1 is
+ *                      complete: after S segments there are S / R rows.  Row t covers the samples
+ *                      [t R hop, t R hop + (R - 1) hop + N).
+ *     mean detector    row[t][k] = fl32( (sum_s |X_s[k]|^2) inv ),  inv = fl32(1 / (R sum_n w[n]^2));
+ *                      the sum in float32, in segment order, starting from the first power itself
+ *     max detector     row[t][k] = fl32( (max_s |X_s[k]|^2) inv ),  inv = fl32(1 / sum_n w[n]^2)
+ * inv is computed in double on the host and rounded once; the product at the store is the only one.  White
+ * noise with E|x|^2 = sigma^2 reads sigma^2 in every bin of a mean row.  Between calls the handle keeps the
+ * samples of the incomplete segment, as the Spectrum does, and the incomplete row: 2048 float32 sums or
+ * maxima on the device and the count S mod R.  A row that goes on from them adds or maximises the same
+ * values in the same order, so THE ROWS DO NOT DEPEND ON HOW THE STREAM IS CUT INTO CALLS, BIT FOR BIT.
+ * ================================================================================== */
+typedef struct gr4pm_spectrogram gr4pm_spectrogram;
+enum { GR4PM_SPECTROGRAM_MEAN = 0, GR4PM_SPECTROGRAM_MAX = 1 };
+typedef struct {
+    uint32_t fft_size;          /* N: 2048 */
+    uint32_t hop;               /* 1 .. N */
+    uint32_t average;           /* R: segments per row, 1 .. gr4pm_spectrum_float_run() */
+    uint32_t detector;          /* GR4PM_SPECTROGRAM_MEAN or GR4PM_SPECTROGRAM_MAX */
+    const float* window;        /* host: N floats, copied at create (NULL: the periodic Hann window) */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_spectrogram_params;
+/* fft_size != 2048, hop == 0, hop > N, a window with a non-finite value, average == 0, average > 64 or an
+ * unknown detector: GR4PM_ERR_INVALID, no handle */
+gr4pm_status gr4pm_spectrogram_create(const gr4pm_spectrogram_params* params, gr4pm_spectrogram** out);
+void gr4pm_spectrogram_destroy(gr4pm_spectrogram* h);
+/* back to the fresh stream: no segments, no carried samples, no carried row */
+gr4pm_status gr4pm_spectrogram_reset(gr4pm_spectrogram* h);
+/* *rows: the rows a call of n samples would complete now */
+gr4pm_status gr4pm_spectrogram_rows(const gr4pm_spectrogram* h, size_t n, size_t* rows);
+/* x: DEVICE, n complex64 samples (any number, 0 included; all are consumed).  rows: DEVICE, room for rows_cap
+ * rows of N floats; the call writes the *n_rows rows it completes (gr4pm_spectrogram_rows' count), in FFT bin
+ * order.  Enqueues on the handle's stream and does not wait.  rows_cap below that count: GR4PM_ERR_OVERFLOW,
+ * and the handle is as it was.  n_rows may be NULL. */
+gr4pm_status gr4pm_spectrogram_process(gr4pm_spectrogram* h, const void* x, size_t n, float* rows, size_t rows_cap,
+                                       size_t* n_rows);
+/* x: DEVICE, n items of an integer IQ format (gr4pm_iq_format; scale 0: the format's default).  The result of
+ * gr4pm_spectrogram_process on gr4pm_iq_unpack(x) bit for bit; calls of any format may be mixed on one handle. */
+gr4pm_status gr4pm_spectrogram_process_iq(gr4pm_spectrogram* h, const void* x, int format, float scale, size_t n,
+                                          float* rows, size_t rows_cap, size_t* n_rows);
+/* The power of bands of rows.  rows: DEVICE, n_rows rows of N floats (what process wrote, or any such array).
+ * bands: HOST, n_bands <= 64 bands of the bins first_bin .. first_bin + n_bins - 1 mod N (first_bin < N,
+ * 1 <= n_bins <= N: a band across +-0.5 is one band).  out: DEVICE, double out[n_bands][n_rows]: the sum of the
+ * band's bins of each row, in double.  One wave per row adds in a fixed order and there is no atomic: the same
+ * call gives the same bits.  Enqueues on the handle's stream and does not wait. */
+typedef struct {
+    uint32_t first_bin;
+    uint32_t n_bins;
+} gr4pm_band;
+gr4pm_status gr4pm_spectrogram_band_power(gr4pm_spectrogram* h, const float* rows, size_t n_rows, const gr4pm_band* bands,
+                                          size_t n_bands, double* out);
+
+/* Bursts from a band's power over time, n rows in time order, host only.  floor: params->floor if > 0, else the
+ * lower median, element (n - 1) / 2 of the sorted rows.  A row is active when it exceeds
+ * floor 10^(threshold_db / 10).  Runs of active rows are taken in time order (nothing wraps); runs separated by
+ * at most max_gap_rows inactive rows merge, then runs shorter than min_rows are dropped (the length counts the
+ * bridged rows).  Per run of n_rows rows from first_row, in double, in index order:
+ *     power = the mean of (p - floor),  peak_row = the first row of the maximum,  snr_db = 10 log10(peak / floor)
+ * out: room for cap bursts; the first min(cap, *count) in ascending time are written, *count is the number
+ * found.  n == 0, a NULL power, params or count, threshold_db <= 0 (or NaN), a negative or non-finite floor:
+ * GR4PM_ERR_INVALID. */
+typedef struct {
+    double threshold_db;        /* > 0 */
+    double floor;               /* > 0: the noise level of a row; 0: the lower median of the rows */
+    size_t max_gap_rows;
+    size_t min_rows;
+} gr4pm_burst_params;
+typedef struct {
+    uint64_t first_row;
+    uint64_t n_rows;
+    uint64_t peak_row;
+    double power;               /* above the floor, the mean over the run */
+    double snr_db;
+} gr4pm_burst;
+gr4pm_status gr4pm_find_bursts(const double* power, size_t n, const gr4pm_burst_params* params, gr4pm_burst* out,
+                               size_t cap, size_t* count);
+
 #ifdef __cplusplus
 }
 #endif

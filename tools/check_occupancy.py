@@ -124,6 +124,9 @@ BUDGETS = [
     # the Spectrum block: the correlator's eight exchange buffers and twiddles plus 8 KiB of window, two waves per SIMD
     # 
     (r"k_spectrum_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
+    # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
+    # section 21)
+    (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
 ]
 
 
