@@ -315,7 +315,7 @@ EXPORTS = [
     "gr4pm_iq_unpack", "gr4pm_iq_pack",
     "gr4pm_ddc_taps", "gr4pm_ddc_create", "gr4pm_ddc_destroy", "gr4pm_ddc_reset", "gr4pm_ddc_output_items",
     "gr4pm_ddc_frequencies", "gr4pm_ddc_process", "gr4pm_ddc_process_iq",
-    "gr4pm_ddc_rational_taps", "gr4pm_ddc_create_rational",
+    "gr4pm_ddc_rational_taps", "gr4pm_ddc_create_rational", "gr4pm_ddc_extract", "gr4pm_ddc_extract_iq",
     "gr4pm_duc_taps", "gr4pm_duc_create", "gr4pm_duc_destroy", "gr4pm_duc_reset", "gr4pm_duc_output_items",
     "gr4pm_duc_frequencies", "gr4pm_duc_process",
     "gr4pm_duc_rational_taps", "gr4pm_duc_create_rational",
@@ -533,6 +533,8 @@ def lib():
     L.gr4pm_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
     L.gr4pm_ddc_rational_taps.argtypes = [sz, sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_ddc_create_rational.argtypes = [C.POINTER(DdcRationalParams), C.POINTER(vp)]
+    L.gr4pm_ddc_extract.argtypes = [vp, vp, sz, C.c_uint64, vp, sz, vp, sz, sz]
+    L.gr4pm_ddc_extract_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, C.c_uint64, vp, sz, vp, sz, sz]
     L.gr4pm_spectrum_window.argtypes = [C.c_uint32, vp]
     L.gr4pm_spectrum_float_run.argtypes = []
     L.gr4pm_spectrum_float_run.restype = C.c_uint32

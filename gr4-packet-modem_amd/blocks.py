@@ -1922,6 +1922,27 @@ def ddc_rational_taps(interpolation, decimation, taps_per_phase=12, passband=0.2
     return out[:n]
 
 
+def ddc_burst_span(start_sample, end_sample, decimation, n_taps, start_index=0, margin_frames=0):
+    """hostlogic/extract_plan.hpp's burst_span in Python integers (host only: works without a GPU): (first_frame,
+    n_frames) of the frames of a Ddc(decimation, n_taps taps, start_index) that see the samples [start_sample,
+    end_sample), widened by margin_frames on either side.  From max(0, floor((start_sample - start_index) / decimation)
+    - margin_frames), the first frame whose newest sample is at or after start_sample, to ceil((end_sample - start_index
+    + n_taps - 1) / decimation) + margin_frames, a frame whose oldest sample is at or after end_sample; both clamped to
+    the frames whose sample indices fit 64 bits.  An empty burst gives (0, 0)."""
+    start, end, D, L, s0, m = (int(v) for v in (start_sample, end_sample, decimation, n_taps, start_index, margin_frames))
+    if D < 1 or L < 1 or m < 0 or min(start, end, s0) < 0 or max(start, end, s0) >= 1 << 64:
+        raise Gr4pmError("ddc_burst_span: decimation and n_taps from 1, no negative margin, indices of 64 unsigned bits")
+    most = (1 << 64) - 2 - max(s0, L - 1)
+    if end <= start or most // D < 1:
+        return 0, 0
+    first = max(0, (start - s0) // D - m) if start > s0 else 0
+    last = min(-(-max(0, end - s0 + L - 1) // D) + m, most // D - 1)
+    first = min(first, last)
+    if last - first + 1 >= 1 << 32:
+        raise Gr4pmError(f"ddc_burst_span: {last - first + 1} frames do not fit a span's 32 bits")
+    return first, last - first + 1
+
+
 class Ddc:
     """gr4pm_ddc: tunable down-converter.  One wideband complex64 stream at fs becomes len(frequencies) channels at
     fs / decimation: row k is the band centred on frequencies[k] (cycles per input sample, any real value, quantised to
@@ -2001,6 +2022,73 @@ class Ddc:
             check(lib().gr4pm_ddc_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), stride, out.shape[1],
                                              C.byref(n)), "Ddc.process_iq")
         return out[:, : n.value]
+
+    SPAN_DTYPE = np.dtype([("channel", np.uint32), ("n_frames", np.uint32), ("first_frame", np.uint64)])  # gr4pm_ddc_span
+    SPANS_PER_CALL = 64
+
+    def _spans(self, spans):
+        """spans as a contiguous SPAN_DTYPE array: from one, or from a sequence of (channel, first_frame, n_frames)"""
+        if isinstance(spans, np.ndarray) and spans.dtype.names:
+            if set(spans.dtype.names) != set(self.SPAN_DTYPE.names):
+                raise Gr4pmError(f"Ddc.extract: a structured spans array has the fields {self.SPAN_DTYPE.names}")
+            rec = np.zeros(spans.shape, dtype=self.SPAN_DTYPE)
+            for name in self.SPAN_DTYPE.names:
+                rec[name] = spans[name]
+            return np.ascontiguousarray(rec.reshape(-1))
+        rec = np.zeros(len(spans), dtype=self.SPAN_DTYPE)
+        for b, (channel, first_frame, n_frames) in enumerate(spans):
+            channel, first_frame, n_frames = int(channel), int(first_frame), int(n_frames)
+            if not (0 <= channel < 1 << 32 and 0 <= first_frame < 1 << 64 and 0 <= n_frames < 1 << 32):
+                raise Gr4pmError(f"Ddc.extract: spans[{b}] = ({channel}, {first_frame}, {n_frames}) does not fit "
+                                 "(uint32 channel, uint64 first_frame, uint32 n_frames)")
+            rec[b] = (channel, n_frames, first_frame)
+        return rec
+
+    def extract(self, x, spans, n_cols=None, x_index=None, out=None, scale=None):
+        """gr4pm_ddc_extract: spans of the handle's output, computed from a recording on their own.  x: the recording (or
+        a window of it), complex64 or integer IQ exactly as in process_bulk; x_index: the absolute index of x[0] (None:
+        the handle's start_index).  The stream is x inside [x_index, x_index + len(x)) and zero elsewhere, and before
+        start_index.  spans: a sequence of (channel, first_frame, n_frames), or a structured array of SPAN_DTYPE; frames
+        are numbered from start_index as process_bulk numbers them from a fresh handle.  Returns (rows, lengths): rows
+        is CUDA complex64 [len(spans), n_cols] (n_cols None: the longest span) with rows[b, :n_frames] the bits of
+        process_bulk's [channel, first_frame : first_frame + n_frames] and +0 behind them -- the layout
+        NativeMultiChannelReceiver.submit takes; lengths is the spans' n_frames (numpy, int64).  out: an optional CUDA
+        complex64 [len(spans), >= n_cols] tensor with contiguous rows.  The handle's stream is not touched: a later
+        process_bulk gives what it would have given.  Any number of spans: 64 go into one launch.  A handle with
+        interpolation > 1 is refused."""
+        rec = self._spans(spans)
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        if n_cols is None:
+            n_cols = int(rec["n_frames"].max()) if rec.size else 0
+        n_cols = int(n_cols)
+        if n_cols < 0:
+            raise Gr4pmError("Ddc.extract: n_cols must not be negative")
+        x_index = self.start_index if x_index is None else int(x_index)
+        if not 0 <= x_index < 1 << 64:
+            raise Gr4pmError("Ddc.extract: x_index must fit 64 unsigned bits")
+        out = _rows_output(out, rec.size, n_cols, x.device, "Ddc.extract")
+        for lo in range(0, max(rec.size, 1), self.SPANS_PER_CALL):  # no span: one call, which refuses what it refuses
+            part = rec[lo:lo + self.SPANS_PER_CALL]
+            rows = out[lo:lo + part.size]
+            stride = rows.stride(0) if part.size > 1 else max(rows.shape[1], n_cols)
+            if fmt is None:
+                check(lib().gr4pm_ddc_extract(self._h, x.data_ptr(), n_in, x_index, _np_ptr(part), part.size, rows.data_ptr(),
+                                              stride, n_cols), "Ddc.extract")
+            else:
+                check(lib().gr4pm_ddc_extract_iq(self._h, x.data_ptr(), fmt, scale, n_in, x_index, _np_ptr(part), part.size,
+                                                 rows.data_ptr(), stride, n_cols), "Ddc.extract_iq")
+        return out[:, :n_cols], rec["n_frames"].astype(np.int64)
+
+    def burst_spans(self, bursts, channel, margin_frames=0):
+        """the spans of `channel` that see the bursts Spectrogram.bursts() found: per record the frames from
+        max(0, floor((start_sample - start_index) / decimation) - margin_frames), the first whose newest sample is at or
+        after start_sample, to ceil((end_sample - start_index + len(taps) - 1) / decimation) + margin_frames, one whose
+        oldest sample is at or after end_sample (host only).  Returns a list of (channel, first_frame, n_frames) for
+        extract()."""
+        if self.interpolation > 1:
+            raise Gr4pmError("Ddc.burst_spans: needs a handle with interpolation 1")
+        return [(int(channel),) + ddc_burst_span(int(b["start_sample"]), int(b["end_sample"]), self.decimation,
+                                                 int(self.taps.size), self.start_index, margin_frames) for b in bursts]
 
     def __del__(self):
         _destroy(self, "gr4pm_ddc_destroy")

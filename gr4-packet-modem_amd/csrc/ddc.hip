@@ -38,7 +38,13 @@
 //   I = 1 does not come here: such a handle runs k_ddc.  The tile is rddc_geometry()'s, the position in the stream
 //   hostlogic/resample_position.hpp's with lead = D - 1: 64-bit integers on the host, by value to the kernel.
 // Both creates are one create(): gr4pm_ddc_create's is the ratio 1 / D.
+//
+// Burst spans of a recording (gr4pm_ddc_extract): since a result is a function of (channel, frame,
+// stream) only, k_ddc_extract computes up to 64 (channel, first frame, frame count) spans of an integer-D handle's output on
+// their own, each into a zero-padded row, with ddc_tile's stage and loop for one channel: the bits of the stream's slices.
+// The stream state is not touched; hostlogic/extract_plan.hpp validates the call and states the kernel's indices.
 #include "freq_xlate.hpp"
+#include "hostlogic/extract_plan.hpp"
 #include "hostlogic/resample_position.hpp"
 #include "kaiser_design.hpp"
 #include "stream_tail.hpp"
@@ -127,6 +133,83 @@ __global__ __launch_bounds__(kNt) void k_ddc(DdcArgs a)
 {
     extern __shared__ float2 s_ddc[];
     gr4pm::with_channels(a.K - blockIdx.y * kGroup, [&](auto nc) { ddc_tile<decltype(nc)::value, F>(a, s_ddc); });
+}
+
+struct ExtractArgs {
+    const void* in;       // the buffer's first sample at or after the handle's start: item 0 is the kernel's index lo
+    float2* out;          // [spans][out_stride]
+    const float2* g;      // the handle's rotated taps
+    const uint32_t* w;    // [K] frequency words
+    uint64_t lo, hi;      // the buffer in the kernel's indices (hostlogic/extract_plan.hpp); zero outside
+    uint64_t start;       // the handle's start_index
+    size_t out_stride;
+    size_t n_cols;
+    unsigned K, D, L;
+    DdcTile tile;
+    float scale;
+    ExtractSpan spans[kMaxExtractSpans];
+};
+
+// blockIdx.y: the span, blockIdx.x: a tile of T columns of its row; one channel per workgroup, so the span, the
+// channel and the tile's first frame are wave-uniform.  ddc_tile's stage and loop with NC = 1 over the channel's
+// column of its group's interleaved table, restated because the tile here is made of a span's frames.
+template <int F>
+__global__ __launch_bounds__(kNt) void k_ddc_extract(ExtractArgs a)
+{
+    extern __shared__ float2 s_ext[];
+    float2* s = s_ext;
+    const unsigned tid = threadIdx.x;
+    const unsigned D = a.D, L = a.L, T = a.tile.T, RS = a.tile.RS;
+    const ExtractSpan span = a.spans[blockIdx.y];
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * T; // the tile's first column
+    const unsigned nv = extract_tile_frames(c0, span.n_frames, T);
+    float2* __restrict__ row = a.out + static_cast<size_t>(blockIdx.y) * a.out_stride;
+    if (nv == 0) { // wholly at or behind the span's end
+        if (tid < T && c0 + tid < a.n_cols) row[c0 + tid] = float2{0.0f, 0.0f};
+        return;
+    }
+    const unsigned k = span.channel, k0 = k / kGroup * kGroup;
+    const unsigned nc = a.K - k0 < static_cast<unsigned>(kGroup) ? a.K - k0 : static_cast<unsigned>(kGroup);
+    const float2* __restrict__ g = a.g + static_cast<size_t>(k0) * L + (k - k0); // tap t: g[t nc]
+    const uint64_t f0 = span.first_frame + c0;
+
+    float2 acc = {0.0f, 0.0f};
+    for (unsigned t0 = 0; t0 < L; t0 += a.tile.Lc) {
+        const unsigned lc = L - t0 < a.tile.Lc ? L - t0 : a.tile.Lc;
+        // stage item j: sample vb + j; frame f0 + n takes tap t from item n D + (t0 + lc - 1 - t)
+        const uint64_t vb = extract_stage_base(L, D, f0, t0, lc);
+        if (t0) __syncthreads(); // the previous chunk has been read
+        gr4pm::stage_by_phase(s, static_cast<unsigned>(extract_stage_items(D, nv, lc)), kNt, D, a.tile.rcpD, RS, vb, a.hi,
+                              [&](size_t u) {
+                                  if (u < a.lo) return float2{0.0f, 0.0f};
+                                  if constexpr (F == iq::kC64)
+                                      return static_cast<const float2*>(a.in)[u - a.lo];
+                                  else
+                                      return iq::unpack_item<F>(iq::load_item<F>(a.in, u - a.lo), a.scale);
+                              });
+        __syncthreads();
+        if (tid < nv) {
+            unsigned t = t0;
+            unsigned col = (lc - 1) / D, r0 = (lc - 1) - col * D;
+            for (;;) {
+                const float2* sp = s + r0 * RS + col + tid;
+#pragma unroll 4
+                for (unsigned r = 0; r <= r0; ++r, sp -= RS, ++t) cmac(acc, g[static_cast<size_t>(t) * nc], *sp);
+                if (col == 0) break;
+                --col;
+                r0 = D - 1;
+            }
+        }
+    }
+
+    if (tid < T && c0 + tid < a.n_cols) {
+        float2 y = {0.0f, 0.0f};
+        if (tid < nv) {
+            const uint32_t i = static_cast<uint32_t>(a.start + (f0 + tid) * D + (D - 1)); // the low 32 bits are all the phase needs
+            cmac(y, gr4pm::mixer<-1>(a.w[k], i), acc);
+        }
+        row[c0 + tid] = y;
+    }
 }
 
 struct RddcArgs {
@@ -321,8 +404,66 @@ static gr4pm_status process_any(gr4pm_ddc* h, const void* in, int format, float 
     return GR4PM_OK;
 }
 
+// extract() and extract_iq(): format iq::kC64 for complex64 samples.  hostlogic/extract_plan.hpp decides; the handle's
+// stream state (tail, args.pos) is neither read nor written
+static gr4pm_status extract_any(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, uint64_t in_index,
+                                const gr4pm_ddc_span* spans, size_t n_spans, gr4pm_c64* out, size_t out_stride, size_t n_cols)
+{
+    if (!h) return GR4PM_ERR_INVALID;
+    const size_t L = h->I > 1 ? 1 : h->args.L;
+    const ExtractPlan p = extract_plan(h->I, h->K, h->D, L, h->args.tile.T, h->start_index, in != nullptr, n_in, in_index,
+                                       spans, n_spans, out != nullptr, out_stride, n_cols);
+    switch (p.why) {
+    case ExtractRefusal::none: break;
+    case ExtractRefusal::nothing: return GR4PM_OK;
+    case ExtractRefusal::rational:
+        set_error("ddc: extract needs a handle with interpolation 1, this one resamples by %zu / %zu", h->I, h->D);
+        return GR4PM_ERR_INVALID;
+    case ExtractRefusal::spans:
+        set_error("ddc: extract takes 1 .. %zu spans a call from a span array, not %zu", kMaxExtractSpans, n_spans);
+        return GR4PM_ERR_INVALID;
+    case ExtractRefusal::channel:
+        set_error("ddc: spans[%zu].channel is %u, the handle has %zu channels", p.at, spans[p.at].channel, h->K);
+        return GR4PM_ERR_INVALID;
+    case ExtractRefusal::room:
+        set_error("ddc: spans[%zu] has %u frames, a row has %zu columns", p.at, spans[p.at].n_frames, n_cols);
+        return GR4PM_ERR_OVERFLOW;
+    case ExtractRefusal::stride:
+        set_error("ddc: a row stride of %zu items for %zu columns", out_stride, n_cols);
+        return GR4PM_ERR_INVALID;
+    case ExtractRefusal::overflow:
+        if (p.at < n_spans)
+            set_error("ddc: spans[%zu] (%u frames from frame %llu) reaches a sample index beyond 64 bits", p.at,
+                      spans[p.at].n_frames, static_cast<unsigned long long>(spans[p.at].first_frame));
+        else
+            set_error("ddc: extract of %zu columns from %zu samples at index %llu does not fit the index range", n_cols, n_in,
+                      static_cast<unsigned long long>(in_index));
+        return GR4PM_ERR_OVERFLOW;
+    case ExtractRefusal::input: set_error("ddc: no input array"); return GR4PM_ERR_INVALID;
+    case ExtractRefusal::output: set_error("ddc: no output array"); return GR4PM_ERR_INVALID;
+    }
+    ExtractArgs a = {};
+    const size_t item = format == iq::kC64 ? sizeof(float2) : iq::item_bytes(format);
+    a.in = in ? static_cast<const char*>(in) + p.skip * item : nullptr;
+    a.out = reinterpret_cast<float2*>(out);
+    a.g = h->args.g, a.w = h->args.w;
+    a.lo = p.lo, a.hi = p.hi;
+    a.start = h->start_index;
+    a.out_stride = out_stride;
+    a.n_cols = n_cols;
+    a.K = h->args.K, a.D = h->args.D, a.L = h->args.L;
+    a.tile = h->args.tile;
+    a.scale = scale;
+    for (size_t b = 0; b < n_spans; ++b) a.spans[b] = spans[b];
+    iq::with_format(format, [&](auto f) {
+        hipLaunchKernelGGL(k_ddc_extract<decltype(f)::value>, dim3(p.grid_x, p.grid_y), dim3(kNt), h->smem, h->stream, a);
+    });
+    GR4PM_HIP_TRY(hipGetLastError());
+    return GR4PM_OK;
+}
+
 // every format's instantiation of a kernel
-#define GR4PM_DDC_ALL_FORMATS(kernel)                                                                                        \
+#define GR4PM_DDC_ALL_FORMATS(kernel)                                                                                       \
     {reinterpret_cast<const void*>(&kernel<iq::kC64>), reinterpret_cast<const void*>(&kernel<GR4PM_IQ_SC16>),                \
      reinterpret_cast<const void*>(&kernel<GR4PM_IQ_SC8>), reinterpret_cast<const void*>(&kernel<GR4PM_IQ_CU8>)}
 
@@ -374,8 +515,10 @@ static gr4pm_status create(const gr4pm_ddc_rational_params* p, gr4pm_ddc** out)
         a.K = Ku, a.D = Du, a.L = Lu;
         const DdcGeometry geo = ddc_geometry(D, L);
         a.tile = geo.tile, h->smem = geo.smem;
-        if (h->smem > 48 * 1024)
+        if (h->smem > 48 * 1024) {
             GR4PM_TRY(raise_dynamic_lds(GR4PM_DDC_ALL_FORMATS(k_ddc), kDdcStageItems * sizeof(float2), "ddc"));
+            GR4PM_TRY(raise_dynamic_lds(GR4PM_DDC_ALL_FORMATS(k_ddc_extract), kDdcStageItems * sizeof(float2), "ddc"));
+        }
     }
     // the rotated taps, a group's as [branch][s][channel]: tap s of a branch for all its channels side by side
     // (I = 1: one branch of L = P taps, tap t of all its channels side by side)
@@ -486,6 +629,26 @@ try {
     }
     return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
                        n_frames);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_extract(gr4pm_ddc* h, const gr4pm_c64* in, size_t n_in, uint64_t in_index, const gr4pm_ddc_span* spans,
+                               size_t n_spans, gr4pm_c64* out, size_t out_stride, size_t n_cols)
+try {
+    return extract_any(h, in, iq::kC64, 0.0f, n_in, in_index, spans, n_spans, out, out_stride, n_cols);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_ddc_extract_iq(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, uint64_t in_index,
+                                  const gr4pm_ddc_span* spans, size_t n_spans, gr4pm_c64* out, size_t out_stride,
+                                  size_t n_cols)
+try {
+    if (!iq::valid(format)) {
+        set_error("ddc: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
+        return GR4PM_ERR_INVALID;
+    }
+    return extract_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, in_index, spans, n_spans, out,
+                       out_stride, n_cols);
 }
 GR4PM_ABI_CATCH
 

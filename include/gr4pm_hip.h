@@ -1126,6 +1126,42 @@ gr4pm_status gr4pm_ddc_rational_taps(size_t interpolation, size_t decimation, si
                                      double stopband, float* out);
 gr4pm_status gr4pm_ddc_create_rational(const gr4pm_ddc_rational_params* params, gr4pm_ddc** out);
 
+/* ------------------------------------------------------------------------------------
+ * Ddc, burst spans of a recording.  A Ddc item is a function of (k, n, stream) only,
+ * so any stretch of any channel's output can be computed on its own: one call computes n_spans spans
+ * (channel, first frame, frame count) of an integer-D handle's output, each into a row of its own, in
+ * the [rows, n] layout gr4pm_multichannel_receiver_submit takes.
+ *   in[0] is the stream's sample with the absolute index in_index.  For this call the stream is `in`
+ *   inside [in_index, in_index + n_in) and zero everywhere else, including everything before the
+ *   handle's start_index.  Frames are numbered as the streaming handle numbers them: frame n of channel
+ *   k is y_k[n] above, with i = start_index + n D + D - 1, whatever the handle has processed so far.
+ *     out[b out_stride + c] = y_{spans[b].channel}[spans[b].first_frame + c]   for c < spans[b].n_frames
+ *     out[b out_stride + c] = +0                                               for n_frames <= c < n_cols
+ *   so that `out` may be uninitialised and a row can go to a receiver as it is.  The evaluation is the
+ *   streaming one (the handle's rotated-tap table and frequency words, one accumulator, t ascending, the
+ *   same fmaf): a row has the bits of the streaming output's slice.
+ * The call does not touch the handle's stream state: a process() after it gives what it would have
+ * given without it.  It enqueues on the handle's stream, does not wait and reads nothing back.
+ * Refused, with gr4pm_last_error set and nothing enqueued: a handle with interpolation > 1, more than 64
+ * spans in a call, channel >= K, n_spans > 1 with out_stride < n_cols, a NULL spans / out / (with
+ * n_in > 0) in, an invalid format (all GR4PM_ERR_INVALID); n_frames > n_cols, and a span or a buffer
+ * whose last sample's index does not fit 64 bits: (first_frame + n_frames) D + max(start_index, L - 1)
+ * > 2^64 - 2 or in_index + n_in > 2^64 - 1 (both GR4PM_ERR_OVERFLOW).  n_spans = 0 or n_cols = 0: OK, nothing done.
+ * ---------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t channel;     /* < K */
+    uint32_t n_frames;    /* <= n_cols; 0: the row is all zeros */
+    uint64_t first_frame; /* counted from the handle's start_index */
+} gr4pm_ddc_span;
+/* in: DEVICE, n_in samples.  spans: HOST, n_spans items (copied by the call).  out: DEVICE, n_spans rows. */
+gr4pm_status gr4pm_ddc_extract(gr4pm_ddc* h, const gr4pm_c64* in, size_t n_in, uint64_t in_index, const gr4pm_ddc_span* spans,
+                               size_t n_spans, gr4pm_c64* out, size_t out_stride, size_t n_cols);
+/* in: DEVICE, n_in items of an integer IQ format (scale 0: the format's default), converted where the
+ * kernel loads them: the result of gr4pm_ddc_extract on gr4pm_iq_unpack(in), bit for bit. */
+gr4pm_status gr4pm_ddc_extract_iq(gr4pm_ddc* h, const void* in, int format, float scale, size_t n_in, uint64_t in_index,
+                                  const gr4pm_ddc_span* spans, size_t n_spans, gr4pm_c64* out, size_t out_stride,
+                                  size_t n_cols);
+
 /* ====================================================================================
  * Duc -- tunable up-converter, the mirror of the Ddc: K complex64 rows at fs / I become ONE wideband
  * stream at fs (the project's own block).  Any integer interpolation I in [1, 1024], K in [1, 64] rows

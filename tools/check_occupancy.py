@@ -113,6 +113,9 @@ BUDGETS = [
     (r"k_correlate_4096ILi1E", dict(vgpr=128, scratch=0)),     # four waves per SIMD
     # the down-converter: eight channel accumulators and the double-precision rotator, six waves per SIMD
     (r"k_ddcILi", dict(vgpr=80, scratch=0)),
+    # its span form: one channel accumulator per lane, so k_ddc's 78 registers bound it with room for the span lookup
+    # 
+    (r"k_ddc_extractILi", dict(vgpr=80, scratch=0)),
     # its rational form: the same loop per polyphase branch, one branch per wave at a time, seven waves per SIMD (DESIGN
     # section 18)
     (r"k_ddc_rationalILi", dict(vgpr=72, scratch=0)),
