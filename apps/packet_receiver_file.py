@@ -3,6 +3,7 @@
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
                             [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
+                            [--refine] [--decimate auto]
                             [--scan [--scan-items N] [--bursts] [--waterfall FILE.npy [--waterfall-average R]]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
@@ -42,6 +43,14 @@ prints one line per burst: `burst frequency F start S end E snr_db X`, S and E (
 edges being as fine as a row (`--waterfall-average` rows of hop 1024, 2048 samples wide).  `--waterfall FILE.npy` writes
 the rows of the scanned items (float32 [rows, 2048], FFT bin order, mean of `--waterfall-average` R segments per row,
 default 1) for a waterfall plot.  `--scan` alone prints what it always printed.
+
+`--refine` (with `--tune`, a value or `auto`) and `--decimate auto`: the blind receiver.  The first `--scan-items` items
+(at most one chunk) are scanned as above; the tuned carrier's bursts (`Spectrogram`, `find_bursts`) are down-converted
+on their own at a provisional decimation of floor(0.4 / bandwidth) (`Ddc.extract`), and a `LineSpectrum` (DESIGN section
+23) reads from those rows the residual carrier offset (the line of x^4) and the symbol rate (the line of |x|^2), both
+the median over the rows whose carrier line stands 6 dB above everything else it was searched among.  `--refine` adds
+the offset to the tuned frequency and prints it; `--decimate auto` turns the rate into the simplest N/M that puts 4
+samples on a symbol (`resample_ratio`), prints it and uses it.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -137,6 +146,49 @@ def print_carriers(carriers, r, items):
     print(f"{len(carriers)} carriers in {items} items ({r['segments']} segments of 2048, hop 1024)")
     for c in carriers:
         print(f"carrier frequency {c['frequency']:+.6f} bandwidth {c['bandwidth']:.6f} snr_db {c['snr_db']:.1f}")
+
+
+def decimation_or_auto(v):
+    """--decimate: `auto`, or what decimation() takes"""
+    return "auto" if str(v).lower() == "auto" else decimation(v)
+
+
+def refine_file(path, tune, bandwidth, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None, min_margin_db=6.0):
+    """the carrier at `tune` (cycles per file sample, `bandwidth` wide) in the file's first min(items, chunk_items) items,
+    looked at through a LineSpectrum at the provisional decimation: returns dict(decimation: D0, rows, offset: the median
+    residual offset in cycles per FILE sample or None, rate: the median symbol rate in symbols per FILE sample or None);
+    only rows whose carrier line has margin_db >= min_margin_db count, for both"""
+    pkg = pkg or ge.load_package()
+    x = next(file_chunks(path, fmt, items, chunk_items), None)
+    if x is None:
+        return dict(decimation=1, rows=0, offset=None, rate=None)
+    kw = {} if fmt == "cf32" else dict(scale=scale)
+    d0 = pkg.provisional_decimation(bandwidth)
+    ddc = pkg.Ddc([tune], d0, max_frames=-(-x.shape[0] // d0) + 1)
+    sg = pkg.Spectrogram(hop=512, average=4)
+    half = max(2, int(np.ceil(0.5 * bandwidth * sg.fft_size)))
+    band = [((int(round(tune * sg.fft_size)) - half) % sg.fft_size, 2 * half + 1)]
+    power = sg.band_power(sg.process_bulk(x, **kw), band)[0]
+    found = sg.bursts(power) if power.numel() else []
+    if len(found):
+        spans = ddc.burst_spans(found, 0, margin_frames=-(-sg.row_span // d0))
+        rows, lengths = ddc.extract(x, spans, **kw)
+    else:  # no burst stands out (a continuous carrier, or a scan too short to see its floor): the whole stretch as one row
+        rows = ddc.process_bulk(x, **kw)
+        lengths = np.array([rows.shape[1]], dtype=np.int64)
+    # hop 256: a burst may be shorter than a segment, and a dozen placements of it average better than two.  The offset
+    # is searched within four bins of the scan (one PSD bin is d0 / 2048 cycles per item): the fewer bins, the fewer
+    # chances the self-noise of x^4 has to beat the line
+    ls = pkg.LineSpectrum(hop=256)
+    max_offset = min(0.1, 4.0 * d0 / sg.fft_size)
+
+    offsets = ls.carrier_offset(rows, lengths, max_offset=max_offset)
+    good = offsets["margin_db"] >= min_margin_db  # the rows that show a carrier line: the symbol rate is read from the same
+    if not good.any():
+        return dict(decimation=d0, rows=int(rows.shape[0]), offset=None, rate=None)
+    rates = ls.symbol_rate(rows, lengths)
+    return dict(decimation=d0, rows=int(rows.shape[0]), offset=float(np.median(offsets["offset"][good])) / d0,
+                rate=float(np.median(rates["rate"][good])) / d0)
 
 
 def tune_value(v):
@@ -236,7 +288,7 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
     return {"packets": packets, "items": done, "file_items": n_file, "seconds": dt, **stats}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("input_file")
     ap.add_argument("syncword_freq_bins", nargs="?", type=int, default=4)   # packet_receiver_file.cpp:25
@@ -258,12 +310,20 @@ def main():
                          "(frequency, start and end in file samples, snr_db)")
     ap.add_argument("--waterfall", metavar="FILE.npy", help="with --scan: write the Spectrogram's rows (float32 [rows, 2048], FFT bin order)")
     ap.add_argument("--waterfall-average", type=int, default=1, metavar="R", help="segments per row of --bursts and --waterfall (1 .. 64, default 1)")
-    ap.add_argument("--decimate", type=decimation, metavar="N[/M]",  # argparse reports a type's ValueError as a usage error
-                    help="file samples per receiver sample, an integer or a ratio such as 25/4 (a Ddc in front)")
-    a = ap.parse_args()
+    ap.add_argument("--decimate", type=decimation_or_auto, metavar="N[/M]|auto",  # argparse reports a type's ValueError as a usage error
+                    help="file samples per receiver sample, an integer or a ratio such as 25/4 (a Ddc in front).  auto: measure "
+                         "the tuned carrier's symbol rate on its bursts (LineSpectrum) and take the simplest ratio that puts 4 "
+                         "samples on a symbol; needs --tune")
+    ap.add_argument("--refine", action="store_true",
+                    help="with --tune: add the residual carrier offset a LineSpectrum finds on the carrier's bursts (the line of "
+                         "x^4, good to a small fraction of the scan's bin) to the tuned frequency")
+    a = ap.parse_args(argv)
     if (a.bursts or a.waterfall) and not a.scan:
         ap.error("--bursts and --waterfall belong to --scan")
-    if a.scan or a.tune == "auto":
+    blind = a.refine or a.decimate == "auto"
+    if blind and a.tune is None:
+        ap.error("--refine and --decimate auto need --tune (a value or auto)")
+    if a.scan or a.tune == "auto" or blind:
         carriers, spectrum, items = scan_file(a.input_file, a.format, a.scale, a.scan_items, a.chunk_items)
         print_carriers(carriers, spectrum, items)
         if a.scan and (a.bursts or a.waterfall):
@@ -276,9 +336,27 @@ def main():
         if a.scan:
             return
         if not len(carriers):
-            sys.exit("--tune auto: the scan found no carrier")
-        a.tune = float(carriers[int(np.argmax(carriers["power"]))]["frequency"])
-        print(f"--tune auto: {a.tune:+.6f}")
+            sys.exit("--tune auto: the scan found no carrier" if a.tune == "auto" else "--refine / --decimate auto: the scan found no carrier")
+        if a.tune == "auto":
+            carrier = carriers[int(np.argmax(carriers["power"]))]
+            a.tune = float(carrier["frequency"])
+            print(f"--tune auto: {a.tune:+.6f}")
+        else:  # the carrier the given frequency means: the nearest on the circle
+            away = np.abs(carriers["frequency"] - a.tune)
+            carrier = carriers[int(np.argmin(np.minimum(away, 1.0 - away)))]
+        if blind:
+            r = refine_file(a.input_file, a.tune, float(carrier["bandwidth"]), a.format, a.scale, a.scan_items, a.chunk_items)
+            if a.refine:
+                if r["offset"] is None:
+                    sys.exit(f"--refine: none of the {r['rows']} rows at decimation {r['decimation']} shows a line 6 dB above the rest")
+                a.tune += r["offset"]
+                print(f"--refine: {r['offset']:+.3e} from {r['rows']} rows at decimation {r['decimation']}: --tune {a.tune:+.7f}")
+            if a.decimate == "auto":
+                if r["rate"] is None:
+                    sys.exit(f"--decimate auto: none of the {r['rows']} rows at decimation {r['decimation']} shows a carrier line to read the symbol rate beside")
+                interp, dec = ge.load_package().resample_ratio(r["rate"])
+                a.decimate = (dec, interp)
+                print(f"--decimate auto: {r['rate']:.6f} symbols per file sample: --decimate {dec}/{interp}")
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
                      fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate)

@@ -242,6 +242,20 @@ class BurstParams(C.Structure):
     _fields_ = [("threshold_db", C.c_double), ("floor", C.c_double), ("max_gap_rows", C.c_size_t), ("min_rows", C.c_size_t)]
 
 
+class LineSpectrumParams(C.Structure):
+    _fields_ = SpectrumParams._fields_
+
+
+class LineParams(C.Structure):
+    _fields_ = [("first_bin", C.c_uint64), ("n_bins", C.c_uint64), ("guard_bins", C.c_uint64)]
+
+
+# GR4PM_LINE_ENVELOPE, GR4PM_LINE_SQUARE, GR4PM_LINE_FOURTH
+LINE_STATISTICS = {"envelope": 0, "square": 1, "fourth": 2}
+# gr4pm_line
+LINE_DTYPE = np.dtype([("frequency", "<f8"), ("snr_db", "<f8"), ("margin_db", "<f8"), ("peak", "<f8"), ("floor", "<f8"),
+                       ("bin", "<u8"), ("found", "<u8")])
+
 SPECTROGRAM_DETECTORS = {"mean": 0, "max": 1}  # GR4PM_SPECTROGRAM_MEAN, GR4PM_SPECTROGRAM_MAX
 # gr4pm_band, gr4pm_burst
 BAND_DTYPE = np.dtype([("first_bin", "<u4"), ("n_bins", "<u4")])
@@ -324,6 +338,8 @@ EXPORTS = [
     "gr4pm_find_carriers",
     "gr4pm_spectrogram_create", "gr4pm_spectrogram_destroy", "gr4pm_spectrogram_reset", "gr4pm_spectrogram_rows",
     "gr4pm_spectrogram_process", "gr4pm_spectrogram_process_iq", "gr4pm_spectrogram_band_power", "gr4pm_find_bursts",
+    "gr4pm_line_spectrum_float_run", "gr4pm_line_spectrum_create", "gr4pm_line_spectrum_destroy", "gr4pm_line_spectrum_process",
+    "gr4pm_find_line", "gr4pm_simplest_ratio",
 ]
 
 _lib = None
@@ -555,6 +571,15 @@ def lib():
     L.gr4pm_spectrogram_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, szp]
     L.gr4pm_spectrogram_band_power.argtypes = [vp, vp, sz, vp, sz, vp]
     L.gr4pm_find_bursts.argtypes = [vp, sz, C.POINTER(BurstParams), vp, sz, szp]
+    L.gr4pm_line_spectrum_float_run.argtypes = []
+    L.gr4pm_line_spectrum_float_run.restype = C.c_uint32
+    L.gr4pm_line_spectrum_create.argtypes = [C.POINTER(LineSpectrumParams), C.POINTER(vp)]
+    L.gr4pm_line_spectrum_destroy.argtypes = [vp]
+    L.gr4pm_line_spectrum_destroy.restype = None
+    L.gr4pm_line_spectrum_process.argtypes = [vp, vp, sz, sz, vp, sz, vp, C.c_int, vp]
+    L.gr4pm_find_line.argtypes = [vp, sz, C.POINTER(LineParams), vp]
+    L.gr4pm_simplest_ratio.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32)]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

@@ -2444,6 +2444,184 @@ class Spectrogram:
         _destroy(self, "gr4pm_spectrogram_destroy")
 
 
+def find_line(spectrum, first_bin=0, n_bins=None, guard_bins=2):
+    """gr4pm_find_line: the line of a spectrum of n bins in FFT order (host only: works without a GPU).  The search
+    window is the n_bins bins (first_bin + i) mod n (None: all n), 2 guard_bins + 3 <= n_bins <= n.  Returns one record
+    of LINE_DTYPE: bin (the first maximum in window order), peak, floor (the window's lower median), snr_db = 10 log10(peak
+    / floor), margin_db = 10 log10(peak / the largest window bin farther than guard_bins from the peak on the circle):
+    the confidence measure, near 0 dB for noise whatever the number of segments; frequency = (bin + d) / n folded to
+    [-0.5, 0.5), d from the parabola through the logarithms of the peak and its two circular neighbours, clamped to
+    +-0.5 (0 when one of them is <= 0 or the curvature is not negative); found = peak > 0."""
+    spectrum = np.ascontiguousarray(spectrum, dtype=np.float64).reshape(-1)
+    n_bins = spectrum.size if n_bins is None else int(n_bins)
+    first_bin, guard_bins = int(first_bin), int(guard_bins)
+    if not all(0 <= v < 1 << 64 for v in (first_bin, n_bins, guard_bins)):
+        raise Gr4pmError("find_line: first_bin, n_bins and guard_bins must fit 64 unsigned bits")
+    p = _abi.LineParams(first_bin, n_bins, guard_bins)
+    out = np.zeros(1, dtype=_abi.LINE_DTYPE)
+    check(lib().gr4pm_find_line(_np_ptr(spectrum), spectrum.size, C.byref(p), _np_ptr(out)), "find_line")
+    return out[0]
+
+
+def simplest_ratio(value, rel_tol, max_num, max_den):
+    """gr4pm_simplest_ratio: (num, den), the fraction with the smallest denominator (of several: the smallest numerator)
+    inside [value (1 - rel_tol), value (1 + rel_tol)] with num <= max_num and den <= max_den, in lowest terms (host
+    only).  Gr4pmError when there is none or the arguments are not finite and positive."""
+    max_num, max_den = int(max_num), int(max_den)
+    if not (0 <= max_num < 1 << 32 and 0 <= max_den < 1 << 32):
+        raise Gr4pmError("simplest_ratio: max_num and max_den must fit 32 unsigned bits")
+    num, den = C.c_uint32(0), C.c_uint32(0)
+    check(lib().gr4pm_simplest_ratio(float(value), float(rel_tol), max_num, max_den, C.byref(num), C.byref(den)),
+          "simplest_ratio")
+    return num.value, den.value
+
+
+def resample_ratio(symbols_per_wide_sample, samples_per_symbol=4, rel_tol=2e-3, max_interpolation=64, max_decimation=1024):
+    """(I, D) for Ddc(frequencies, D, interpolation=I): the simplest I / D within rel_tol of samples_per_symbol *
+    symbols_per_wide_sample, so that the rows have samples_per_symbol items per symbol.  A rate rho symbols per item
+    measured on the rows of a handle with ratio I0 / D0 (LineSpectrum.symbol_rate) is rho I0 / D0 symbols per wideband
+    sample.  rel_tol: the rate estimate is good to 2e-4 with at least three segments at high SNR (DESIGN.md section 23);
+    2e-3 leaves a factor of ten, and around 4 / 25 no simpler fraction lies inside it."""
+    return simplest_ratio(float(samples_per_symbol) * float(symbols_per_wide_sample), rel_tol, max_interpolation, max_decimation)
+
+
+def provisional_decimation(bandwidth):
+    """max(1, floor(0.4 / bandwidth)): the decimation at which a carrier of `bandwidth` cycles per wideband sample
+    (find_carriers' field) is looked at before its symbol rate is known.  It then occupies at most +-0.2 of the row rate:
+    inside the default taps' 0.25 passband, band edges included, which the envelope line needs, and its symbol rate stays
+    below 0.5 cycles per item."""
+    bandwidth = float(bandwidth)
+    if not (bandwidth > 0.0 and math.isfinite(bandwidth)):
+        raise Gr4pmError(f"provisional_decimation: bandwidth is {bandwidth}, need a positive number")
+    return max(1, int(math.floor(0.4 / bandwidth)))
+
+
+class LineSpectrum:
+    """gr4pm_line_spectrum: per row of channel items (Ddc.process_bulk's or Ddc.extract's [rows, n]) the Welch spectrum
+    of a memoryless nonlinearity, whose spectral line gives what a blind receiver lacks: "fourth" ((g x)^4: a line at
+    four times the residual carrier offset of a QPSK burst), "square" ((g x)^2: twice the offset, BPSK) and "envelope"
+    (|g x|^2: a line at the symbol rate).  Row r has lengths[r] items; behind them the row counts as zero and is never
+    read.  Segment s is y[s hop .. s hop + 2048), the last one zero-filled, so a short burst still has one;
+    out[r] = sum_s |FFT(w y_s)|^2 / (S_r sum w^2) in FFT bin order (.frequencies: the bin centres in cycles per item), a
+    CUDA float64 tensor.  A row's result depends on that row alone, bit for bit.  The handle works on the stream that is
+    current when it is made.
+
+    Frequency bookkeeping: a row offset of delta cycles per item of a handle with ratio I / D (Ddc(f, D,
+    interpolation=I)) is delta I / D cycles per wideband sample, to be ADDED to that channel's frequency; a rate of rho
+    symbols per item is rho I / D symbols per wideband sample (resample_ratio takes that)."""
+
+    fft_size = 2048
+    ROWS_PER_CALL = 64
+
+    def __init__(self, hop=1024, window=None, fft_size=2048):
+        self.hop, self.fft_size = int(hop), int(fft_size)
+        if window is not None:
+            window = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+            if window.size != self.fft_size:
+                raise Gr4pmError(f"LineSpectrum: a window of {window.size} floats for {self.fft_size} points")
+        self.window = window if window is not None else spectrum_window(self.fft_size)
+        if not (0 <= self.hop < 1 << 32 and 0 <= self.fft_size < 1 << 32):
+            raise Gr4pmError("LineSpectrum: hop and fft_size must fit 32 unsigned bits")
+        k = np.arange(self.fft_size, dtype=np.float64) / max(self.fft_size, 1)
+        self.frequencies = k - np.floor(k + 0.5)
+        stream = _stream_handle()
+        self._stream = stream.value
+        p = _abi.LineSpectrumParams(self.fft_size, self.hop, _np_ptr(self.window) if window is not None else None, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_line_spectrum_create(C.byref(p), C.byref(self._h)), "LineSpectrum")
+
+    def _lengths(self, x, lengths):
+        if lengths is None:
+            return np.full(x.shape[0], x.shape[1], dtype=np.uint64)
+        lengths = np.asarray(lengths).reshape(-1)
+        if lengths.size != x.shape[0]:
+            raise Gr4pmError(f"LineSpectrum: {lengths.size} lengths for {x.shape[0]} rows")
+        if lengths.size and (int(lengths.min()) < 0 or int(lengths.max()) >= 1 << 64):
+            raise Gr4pmError("LineSpectrum: lengths must fit 64 unsigned bits")
+        return np.ascontiguousarray(lengths.astype(np.uint64))
+
+    def process_rows(self, x, lengths=None, statistic="fourth", normalize=True):
+        """gr4pm_line_spectrum_process: x: a CUDA complex64 tensor [R, n] with contiguous rows (any row stride >= n);
+        lengths: R item counts <= n (None: n each).  statistic: "fourth", "square" or "envelope".  normalize: the row's
+        gain is 1 / sqrt(mean |x|^2 over the row's length), computed with torch on the device without a readback (False:
+        1; the fourth power leaves float32's range for |x| outside about 1e-4 .. 1e4).  Any number of rows: 64 go into
+        one call.  Returns a CUDA float64 tensor [R, 2048]; does not wait."""
+        torch = _torch()
+        if statistic not in _abi.LINE_STATISTICS:
+            raise Gr4pmError(f"LineSpectrum: statistic is {statistic!r}, not 'envelope', 'square' or 'fourth'")
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
+                (x.shape[1] <= 1 or x.stride(1) == 1) and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
+            raise TypeError("x must be a [rows, n] complex64 CUDA tensor with contiguous rows")
+        n_rows, n_cols = x.shape
+        lengths = self._lengths(x, lengths)
+        if lengths.size and int(lengths.max()) > n_cols:
+            raise Gr4pmError(f"LineSpectrum: a length of {int(lengths.max())} items, the rows have {n_cols}")
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        gains = None
+        if normalize and n_rows and n_cols:
+            ln = torch.as_tensor(lengths.astype(np.int64), device=x.device)
+            live = torch.arange(n_cols, device=x.device)[None, :] < ln[:, None]
+            xr = torch.view_as_real(x)
+            power = torch.where(live, xr[..., 0] * xr[..., 0] + xr[..., 1] * xr[..., 1], 0.0).sum(dim=1, dtype=torch.float64)
+            mean = power / ln.clamp(min=1).to(torch.float64)
+            gains = torch.where(mean > 0, mean.rsqrt(), 1.0).to(torch.float32).contiguous()
+            if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+                _inputs_ready(gains)
+        out = torch.empty((n_rows, self.fft_size), dtype=torch.float64, device=x.device)
+        stat = _abi.LINE_STATISTICS[statistic]
+        for lo in range(0, n_rows, self.ROWS_PER_CALL):
+            rows, part = x[lo:lo + self.ROWS_PER_CALL], lengths[lo:lo + self.ROWS_PER_CALL]
+            stride = rows.stride(0) if rows.shape[0] > 1 else max(n_cols, 1)
+            check(lib().gr4pm_line_spectrum_process(
+                self._h, rows.data_ptr(), stride, n_cols, _np_ptr(part), part.size,
+                gains[lo:lo + self.ROWS_PER_CALL].data_ptr() if gains is not None else None, stat,
+                out[lo:lo + self.ROWS_PER_CALL].data_ptr()), "LineSpectrum.process_rows")
+        self._last = (x, gains)  # the calls do not wait: the inputs live until the next call
+        return out
+
+    def _lines(self, spectra, first_bin, n_bins, scale, field):
+        spectra = spectra.cpu().numpy()
+        out = np.zeros(spectra.shape[0], dtype=np.dtype([(field, "<f8"), ("snr_db", "<f8"), ("margin_db", "<f8")]))
+        for r, row in enumerate(spectra):
+            line = find_line(row, first_bin, n_bins)
+            out[r] = (line["frequency"] * scale, line["snr_db"], line["margin_db"])
+        return out
+
+    def carrier_offset(self, x, lengths=None, order=4, max_offset=0.1):
+        """the residual carrier offset of every row: the line of the "fourth" (order 4: QPSK) or "square" (order 2:
+        BPSK) spectrum inside |order f| <= order max_offset, divided by `order`.  max_offset < 0.5 / order: beyond it
+        the line aliases.  Returns a structured array per row: offset (cycles per item; with a handle of ratio I / D add
+        offset I / D to the channel's frequency), snr_db, margin_db (find_line's; trust a row with margin_db >= 6).
+        Waits for the result."""
+        if order not in (2, 4):
+            raise Gr4pmError(f"LineSpectrum.carrier_offset: order is {order!r}, not 2 or 4")
+        if not 0.0 < float(max_offset) < 0.5 / order:
+            raise Gr4pmError(f"LineSpectrum.carrier_offset: max_offset is {max_offset}, need 0 < max_offset < {0.5 / order}")
+        half = min(int(math.floor(order * float(max_offset) * self.fft_size)), self.fft_size // 2 - 1)
+        half = max(half, 3)
+        spectra = self.process_rows(x, lengths, "fourth" if order == 4 else "square")
+        return self._lines(spectra, (self.fft_size - half) % self.fft_size, 2 * half + 1, 1.0 / order, "offset")
+
+    def symbol_rate(self, x, lengths=None, min_rate=0.05, max_rate=0.45):
+        """the symbol rate of every row: the line of the "envelope" spectrum inside [min_rate, max_rate] cycles per item
+        (0 < min_rate < max_rate < 0.5; the spectrum is symmetric, the positive half is searched).  Returns a structured
+        array per row: rate (symbols per item; with a handle of ratio I / D that is rate I / D symbols per wideband
+        sample), snr_db, margin_db.  Waits for the result."""
+        min_rate, max_rate = float(min_rate), float(max_rate)
+        if not 0.0 < min_rate < max_rate < 0.5:
+            raise Gr4pmError(f"LineSpectrum.symbol_rate: need 0 < min_rate < max_rate < 0.5, not {min_rate}, {max_rate}")
+        first = int(math.ceil(min_rate * self.fft_size))
+        last = int(math.floor(max_rate * self.fft_size))
+        if last - first + 1 < 7:
+            raise Gr4pmError("LineSpectrum.symbol_rate: the range holds fewer than 7 bins")
+        spectra = self.process_rows(x, lengths, "envelope")
+        return self._lines(spectra, first, last - first + 1, 1.0, "rate")
+
+    def __del__(self):
+        _destroy(self, "gr4pm_line_spectrum_destroy")
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

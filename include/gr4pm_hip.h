@@ -1465,6 +1465,90 @@ typedef struct {
 gr4pm_status gr4pm_find_bursts(const double* power, size_t n, const gr4pm_burst_params* params, gr4pm_burst* out,
                                size_t cap, size_t* count);
 
+/* ====================================================================================
+ * LineSpectrum -- the Welch spectrum of a memoryless nonlinearity of rows of channel items, whose spectral
+ * line gives a burst's residual carrier offset (x^4, x^2) or its symbol rate (|x|^2); a line finder and a
+ * rational approximation made for it (the project's own block).  N = fft_size = 2048,
+ * 1 <= hop <= N, the window as gr4pm_spectrum_params'.  One call takes R <= 64 rows x[r stride + i] of a DEVICE
+ * complex64 array (what gr4pm_ddc_extract or gr4pm_ddc_process wrote).  For row r with n_r = lengths[r] items
+ * and u[i] = gains[r] x[r, i] (one float32 product per component):
+ *     y[i]           = |u[i]|^2 (GR4PM_LINE_ENVELOPE, real), u[i]^2 (GR4PM_LINE_SQUARE) or (u[i]^2)^2
+ *                      (GR4PM_LINE_FOURTH) for i < n_r, and 0 for i >= n_r.  ITEMS AT OR BEYOND n_r ARE NEVER
+ *                      LOADED: a row may end at its buffer's last byte and may hold anything behind n_r.
+ *     segments       S_r = 0 if n_r = 0, else 1 + ceil(max(n_r - N, 0) / hop); segment s is y[s hop .. s hop + N),
+ *                      so the last one is zero-filled and a burst shorter than N items still has one
+ *     square, fourth acc[k] = sum_s |FFT_N(w y_s)[k]|^2
+ *     envelope       Z_p = FFT_N(w (y_2p + i y_2p+1)), an odd last segment pairs with zero;
+ *                      acc[k] = sum_p (|Z_p[k]|^2 + |Z_p[(N - k) mod N]|^2) / 2, which is sum_s |Y_s[k]|^2 because y
+ *                      is real; the fold happens in double, so the row is bit-symmetric in k <-> N - k
+ *     out[r][k]      = acc[k] / (S_r sum_n w[n]^2), zeros when S_r = 0; FFT bin order (bin k: +k / N cycles per item)
+ * A wave transforms a run of at most gr4pm_line_spectrum_float_run() (64) consecutive transforms of ONE row and
+ * sums their powers in float32; the run length is fixed, and a row's runs are added in double, in order, with
+ * no floating-point atomic: A ROW'S RESULT DEPENDS ON THAT ROW ALONE, BIT FOR BIT, not on the other rows of the
+ * call or on R.  The kernel does not normalise: the powers are float32, so keep |gains[r] x| within about
+ * 1e-4 .. 1e4 for GR4PM_LINE_FOURTH (1e-9 .. 1e9 for the other two); that is what `gains` is for.
+ * ================================================================================== */
+typedef struct gr4pm_line_spectrum gr4pm_line_spectrum;
+enum { GR4PM_LINE_ENVELOPE = 0, GR4PM_LINE_SQUARE = 1, GR4PM_LINE_FOURTH = 2 };
+typedef struct {
+    uint32_t fft_size;          /* N: 2048 */
+    uint32_t hop;               /* 1 .. N */
+    const float* window;        /* host: N floats, copied at create (NULL: the periodic Hann window) */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_line_spectrum_params;
+/* transforms a wave sums in float32 before its sum goes on in double: 64 */
+uint32_t gr4pm_line_spectrum_float_run(void);
+/* fft_size != 2048, hop == 0, hop > N or a window with a non-finite value: GR4PM_ERR_INVALID, no handle */
+gr4pm_status gr4pm_line_spectrum_create(const gr4pm_line_spectrum_params* params, gr4pm_line_spectrum** out);
+void gr4pm_line_spectrum_destroy(gr4pm_line_spectrum* h);
+/* x: DEVICE, R rows of n_cols items, `stride` items apart.  lengths: HOST, R items, copied by the call (NULL:
+ * every row has n_cols items).  gains: DEVICE, R floats (NULL: 1).  out: DEVICE, double out[R][N].  Enqueues on
+ * the handle's stream, does not wait and reads nothing back.  Refused with GR4PM_ERR_INVALID, gr4pm_last_error
+ * set and nothing enqueued: R > 64, a length above n_cols, R > 1 with stride < n_cols, an unknown statistic, a
+ * NULL x when any length is not zero, a NULL out; a row of more than 2^40 items: GR4PM_ERR_OVERFLOW.  R = 0: OK,
+ * nothing done. */
+gr4pm_status gr4pm_line_spectrum_process(gr4pm_line_spectrum* h, const gr4pm_c64* x, size_t stride, size_t n_cols,
+                                         const uint64_t* lengths, size_t n_rows, const float* gains, int statistic,
+                                         double* out);
+
+/* The line of a spectrum of n bins in FFT order, host only.  The search window is the n_bins bins
+ * (first_bin + i) mod n, i = 0 .. n_bins - 1, on the circle of n bins; first_bin < n,
+ * 2 guard_bins + 3 <= n_bins <= n.
+ *     peak        the first maximum in window order, at `bin`
+ *     floor       the lower median of the window's bins: element (n_bins - 1) / 2 of them sorted
+ *     snr_db    = 10 log10(peak / floor)
+ *     margin_db = 10 log10(peak / other), other: the largest window bin whose circular distance to `bin` is
+ *                 above guard_bins.  This is the confidence measure: the snr_db of pure noise grows with the
+ *                 number of bins searched and shrinks with the segments averaged, margin_db stays near 0 dB.
+ *     frequency = (bin + d) / n folded to [-0.5, 0.5), with the parabola through the natural logarithms of the
+ *                 peak (lb) and its circular neighbours bin - 1 (la) and bin + 1 (lc), inside the window or not:
+ *                 d = 0.5 (la - lc) / (la - 2 lb + lc), clamped to +-0.5; d = 0 if any of the three is <= 0 or the
+ *                 curvature la - 2 lb + lc is not negative
+ *     found     = peak > 0; without it frequency is the bin's and snr_db = margin_db = 0
+ * n == 0, a NULL pointer, first_bin >= n, n_bins out of range: GR4PM_ERR_INVALID. */
+typedef struct {
+    uint64_t first_bin;
+    uint64_t n_bins;
+    uint64_t guard_bins;        /* the Python default is 2 */
+} gr4pm_line_params;
+typedef struct {
+    double frequency;           /* cycles per item, [-0.5, 0.5) */
+    double snr_db;
+    double margin_db;
+    double peak;
+    double floor;
+    uint64_t bin;
+    uint64_t found;             /* 0 or 1 */
+} gr4pm_line;
+gr4pm_status gr4pm_find_line(const double* spectrum, size_t n, const gr4pm_line_params* params, gr4pm_line* out);
+
+/* The fraction num / den with the smallest denominator (of several: the smallest numerator) inside
+ * [value (1 - rel_tol), value (1 + rel_tol)], 1 <= num <= max_num, 1 <= den <= max_den, in lowest terms; host
+ * only, a Stern-Brocot walk in integers.  None exists, or value, rel_tol not finite, value <= 0, rel_tol < 0 or
+ * >= 1, a zero maximum: GR4PM_ERR_INVALID (num and den are then 0). */
+gr4pm_status gr4pm_simplest_ratio(double value, double rel_tol, uint32_t max_num, uint32_t max_den, uint32_t* num,
+                                  uint32_t* den);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,10 @@ BUDGETS = [
     # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
     # section 21)
     (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
+    # the LineSpectrum block: the same LDS image, 32 sums and (envelope) both segments of a pair in flight, two waves per
+    # SIMD
+    (r"k_line_spectrum_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
+    (r"k_line_spectrum_reduceILb", dict(vgpr=64, scratch=0)),
 ]
 
 
