@@ -3,7 +3,7 @@
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
                             [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
-                            [--refine] [--decimate auto]
+                            [--refine] [--decimate auto] [--burst-rows]
                             [--scan [--scan-items N] [--bursts] [--waterfall FILE.npy [--waterfall-average R]]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
@@ -51,6 +51,14 @@ on their own at a provisional decimation of floor(0.4 / bandwidth) (`Ddc.extract
 the median over the rows whose carrier line stands 6 dB above everything else it was searched among.  `--refine` adds
 the offset to the tuned frequency and prints it; `--decimate auto` turns the rate into the simplest N/M that puts 4
 samples on a symbol (`resample_ratio`), prints it and uses it.
+
+`--burst-rows` (with `--tune` and `--decimate`, each a value or `auto`): the burst chain to the end.  The file, which has
+to fit one chunk (`--chunk-items`), is scanned, the tuned carrier's bursts are extracted at the provisional decimation
+and read by the `LineSpectrum` as above, and a `RowResampler` brings every burst row to 4 samples per
+symbol and removes its residual offset ON THE ROWS, each row with its own measured rate (`--decimate auto`) or the typed
+N/M, and its own offset; a row whose carrier line stands less than 6 dB above the rest takes the carrier's medians.  The
+receiver takes the rows.  No streaming `Ddc` runs over the file, and the rate need not be a simple fraction.  If no row
+shows a carrier line, the app says so and falls back to the streaming path.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -153,15 +161,16 @@ def decimation_or_auto(v):
     return "auto" if str(v).lower() == "auto" else decimation(v)
 
 
-def refine_file(path, tune, bandwidth, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None, min_margin_db=6.0):
-    """the carrier at `tune` (cycles per file sample, `bandwidth` wide) in the file's first min(items, chunk_items) items,
-    looked at through a LineSpectrum at the provisional decimation: returns dict(decimation: D0, rows, offset: the median
-    residual offset in cycles per FILE sample or None, rate: the median symbol rate in symbols per FILE sample or None);
-    only rows whose carrier line has margin_db >= min_margin_db count, for both"""
+def burst_rows_of_file(path, tune, bandwidth, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None, min_margin_db=6.0):
+    """the bursts of the carrier at `tune` (cycles per file sample, `bandwidth` wide) in the file's first min(items,
+    chunk_items) items as rows at the provisional decimation, and what a LineSpectrum reads from them: returns
+    dict(decimation: D0, rows: the CUDA tensor [R, n] or None without a sample, lengths, offsets: carrier_offset's
+    records, good: the rows whose carrier line has margin_db >= min_margin_db, rates: symbol_rate's records, or None when
+    no row is good)"""
     pkg = pkg or ge.load_package()
     x = next(file_chunks(path, fmt, items, chunk_items), None)
     if x is None:
-        return dict(decimation=1, rows=0, offset=None, rate=None)
+        return dict(decimation=1, rows=None, lengths=None, offsets=None, good=None, rates=None)
     kw = {} if fmt == "cf32" else dict(scale=scale)
     d0 = pkg.provisional_decimation(bandwidth)
     ddc = pkg.Ddc([tune], d0, max_frames=-(-x.shape[0] // d0) + 1)
@@ -184,11 +193,66 @@ def refine_file(path, tune, bandwidth, fmt="cf32", scale=None, items=None, chunk
 
     offsets = ls.carrier_offset(rows, lengths, max_offset=max_offset)
     good = offsets["margin_db"] >= min_margin_db  # the rows that show a carrier line: the symbol rate is read from the same
+    rates = ls.symbol_rate(rows, lengths) if good.any() else None
+    return dict(decimation=d0, rows=rows, lengths=lengths, offsets=offsets, good=good, rates=rates)
+
+
+def refine_file(path, tune, bandwidth, fmt="cf32", scale=None, items=None, chunk_items=1 << 24, pkg=None, min_margin_db=6.0):
+    """the carrier at `tune` (cycles per file sample, `bandwidth` wide) in the file's first min(items, chunk_items) items,
+    looked at through a LineSpectrum at the provisional decimation: returns dict(decimation: D0, rows, offset: the median
+    residual offset in cycles per FILE sample or None, rate: the median symbol rate in symbols per FILE sample or None);
+    only rows whose carrier line has margin_db >= min_margin_db count, for both"""
+    b = burst_rows_of_file(path, tune, bandwidth, fmt, scale, items, chunk_items, pkg, min_margin_db)
+    if b["rows"] is None:
+        return dict(decimation=1, rows=0, offset=None, rate=None)
+    d0, good = b["decimation"], b["good"]
     if not good.any():
-        return dict(decimation=d0, rows=int(rows.shape[0]), offset=None, rate=None)
-    rates = ls.symbol_rate(rows, lengths)
-    return dict(decimation=d0, rows=int(rows.shape[0]), offset=float(np.median(offsets["offset"][good])) / d0,
-                rate=float(np.median(rates["rate"][good])) / d0)
+        return dict(decimation=d0, rows=int(b["rows"].shape[0]), offset=None, rate=None)
+    return dict(decimation=d0, rows=int(b["rows"].shape[0]), offset=float(np.median(b["offsets"]["offset"][good])) / d0,
+                rate=float(np.median(b["rates"]["rate"][good])) / d0)
+
+
+def receive_burst_rows(b, syncword_freq_bins=4, syncword_threshold=9.5, rate=None, out=None, pkg=None):
+    """burst_rows_of_file()'s rows through a RowResampler to 4 samples per symbol with their residual offsets removed, and
+    through the receiver, row by row.  rate: symbols per row item for every row (a typed --decimate), or None: each good
+    row's own measured rate.  A row that is not good takes the medians of the good ones, for the rate and for the offset.
+    Returns receive_file()'s dict; its items are the resampled rows' items."""
+    pkg = pkg or ge.load_package()
+    good, offsets = b["good"], b["offsets"]["offset"].copy()
+    offsets[~good] = np.median(offsets[good])
+    if rate is None:
+        rates = b["rates"]["rate"].copy()
+        rates[~good] = np.median(rates[good])
+    else:
+        rates = np.full(offsets.size, float(rate))
+    t0 = time.perf_counter()
+    rs = pkg.RowResampler()
+    # one block of 2048 zeros behind the longest row: the receiver delivers a packet once the block after it has come
+    longest = int(rs.output_lengths(b["lengths"], rs.steps_for(rates)).max())
+    n_cols = (-(-longest // 2048) + 1) * 2048
+    rows, lengths = rs.to_samples_per_symbol(b["rows"], b["lengths"], rates, offsets, n_cols=n_cols)
+    packets, stats = [], {"headers": 0, "invalid_headers": 0, "crc_failures": 0}
+    for r in range(rows.shape[0]):
+        rx = pkg.NativePacketReceiver(4, syncword_freq_bins, syncword_threshold, max_items=n_cols, tags_cap=n_cols // 768 + 64,
+                                      decode_headers=True, packets_only=True)
+        res = rx.process_bulk(rows[r].contiguous())
+        m, lens = res["header_messages"], res["packet_lengths"]
+        stats["headers"] += int(m.size)
+        stats["invalid_headers"] += int(np.sum(m["invalid_header"] != 0))
+        stats["crc_failures"] += int(np.sum(lens == 0))
+        data, pos = res["packets"].cpu().numpy(), 0
+        for n in lens[lens > 0]:
+            packets.append(data[pos:pos + int(n)].tobytes())
+            pos += int(n)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if out:
+        with open(out, "wb") as f:
+            for p in packets:
+                f.write(len(p).to_bytes(2, "big"))
+                f.write(p)
+    items = int(np.sum(lengths))
+    return {"packets": packets, "items": items, "file_items": items, "seconds": dt, "rates": rates, "offsets": offsets, **stats}
 
 
 def tune_value(v):
@@ -317,10 +381,17 @@ def main(argv=None):
     ap.add_argument("--refine", action="store_true",
                     help="with --tune: add the residual carrier offset a LineSpectrum finds on the carrier's bursts (the line of "
                          "x^4, good to a small fraction of the scan's bin) to the tuned frequency")
+    ap.add_argument("--burst-rows", action="store_true",
+                    help="with --tune and --decimate (values or auto): extract the carrier's bursts, bring every burst row to 4 "
+                         "samples per symbol and remove its residual offset with a RowResampler, each row by its own "
+                         "LineSpectrum reading, and receive the rows; no streaming Ddc runs over the file, which has to fit "
+                         "one chunk")
     a = ap.parse_args(argv)
+    if a.burst_rows and (a.tune is None or a.decimate is None or a.scan or a.zmq or a.zmq_ports):
+        ap.error("--burst-rows needs --tune and --decimate (values or auto) and goes with neither --scan nor --zmq")
     if (a.bursts or a.waterfall) and not a.scan:
         ap.error("--bursts and --waterfall belong to --scan")
-    blind = a.refine or a.decimate == "auto"
+    blind = a.refine or a.decimate == "auto" or a.burst_rows
     if blind and a.tune is None:
         ap.error("--refine and --decimate auto need --tune (a value or auto)")
     if a.scan or a.tune == "auto" or blind:
@@ -344,7 +415,23 @@ def main(argv=None):
         else:  # the carrier the given frequency means: the nearest on the circle
             away = np.abs(carriers["frequency"] - a.tune)
             carrier = carriers[int(np.argmin(np.minimum(away, 1.0 - away)))]
-        if blind:
+        if a.burst_rows:
+            item_bytes = 8 if a.format == "cf32" else 2 * FILE_DTYPES[a.format].itemsize
+            if os.path.getsize(a.input_file) // item_bytes > a.chunk_items:
+                sys.exit(f"--burst-rows: the file has more than --chunk-items = {a.chunk_items} items")
+            b = burst_rows_of_file(a.input_file, a.tune, float(carrier["bandwidth"]), a.format, a.scale, None, a.chunk_items)
+            if b["rows"] is not None and b["good"].any():
+                d0 = b["decimation"]
+                rate = None if a.decimate == "auto" else d0 * a.decimate[1] / (4.0 * a.decimate[0])  # symbols per row item
+                r = receive_burst_rows(b, a.syncword_freq_bins, a.syncword_threshold, rate, a.out)
+                print(f"--burst-rows: {b['rows'].shape[0]} rows at decimation {d0} ({int(b['good'].sum())} with a carrier line), "
+                      f"symbols per file sample {np.round(r['rates'] / d0, 7).tolist()}, offsets "
+                      f"{[float(f'{v / d0:+.3e}') for v in r['offsets']]}: resampled row by row, no streaming pass over the file")
+                print(f"{r['items']} row samples in {r['seconds']:.3f} s; headers {r['headers']} ({r['invalid_headers']} invalid), "
+                      f"packets {len(r['packets'])} ({r['crc_failures']} CRC failures), {sum(len(p) for p in r['packets'])} bytes")
+                return
+            print("--burst-rows: no burst row shows a carrier line 6 dB above the rest: falling back to the streaming path")
+        if a.refine or a.decimate == "auto":
             r = refine_file(a.input_file, a.tune, float(carrier["bandwidth"]), a.format, a.scale, a.scan_items, a.chunk_items)
             if a.refine:
                 if r["offset"] is None:

@@ -250,6 +250,14 @@ class LineParams(C.Structure):
     _fields_ = [("first_bin", C.c_uint64), ("n_bins", C.c_uint64), ("guard_bins", C.c_uint64)]
 
 
+class RowResamplerParams(C.Structure):
+    _fields_ = [("phases", C.c_uint32), ("taps_per_phase", C.c_uint32), ("taps", C.c_void_p), ("stream", C.c_void_p)]
+
+
+# gr4pm_row_record: 24 bytes, the last four are padding
+ROW_RECORD_DTYPE = np.dtype({"names": ["step", "phase0", "freq"], "formats": ["<u8", "<u8", "<i4"], "offsets": [0, 8, 16],
+                             "itemsize": 24})
+
 # GR4PM_LINE_ENVELOPE, GR4PM_LINE_SQUARE, GR4PM_LINE_FOURTH
 LINE_STATISTICS = {"envelope": 0, "square": 1, "fourth": 2}
 # gr4pm_line
@@ -340,6 +348,8 @@ EXPORTS = [
     "gr4pm_spectrogram_process", "gr4pm_spectrogram_process_iq", "gr4pm_spectrogram_band_power", "gr4pm_find_bursts",
     "gr4pm_line_spectrum_float_run", "gr4pm_line_spectrum_create", "gr4pm_line_spectrum_destroy", "gr4pm_line_spectrum_process",
     "gr4pm_find_line", "gr4pm_simplest_ratio",
+    "gr4pm_row_resampler_taps", "gr4pm_row_resampler_create", "gr4pm_row_resampler_destroy",
+    "gr4pm_row_resampler_output_lengths", "gr4pm_row_resampler_tile_items", "gr4pm_row_resampler_process",
 ]
 
 _lib = None
@@ -580,6 +590,14 @@ def lib():
     L.gr4pm_find_line.argtypes = [vp, sz, C.POINTER(LineParams), vp]
     L.gr4pm_simplest_ratio.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                        C.POINTER(C.c_uint32)]
+    L.gr4pm_row_resampler_taps.argtypes = [sz, sz, C.c_double, C.c_double, C.c_double, vp]
+    L.gr4pm_row_resampler_create.argtypes = [C.POINTER(RowResamplerParams), C.POINTER(vp)]
+    L.gr4pm_row_resampler_destroy.argtypes = [vp]
+    L.gr4pm_row_resampler_destroy.restype = None
+    L.gr4pm_row_resampler_output_lengths.argtypes = [sz, sz, vp, vp, sz, sz, vp]
+    L.gr4pm_row_resampler_tile_items.argtypes = [sz, C.c_uint64]
+    L.gr4pm_row_resampler_tile_items.restype = C.c_uint32
+    L.gr4pm_row_resampler_process.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, sz, sz, vp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

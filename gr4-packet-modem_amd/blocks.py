@@ -2622,6 +2622,170 @@ class LineSpectrum:
         _destroy(self, "gr4pm_line_spectrum_destroy")
 
 
+def row_resampler_taps(phases=32, taps_per_phase=12, max_step=1.0, passband=0.25, stopband=0.75):
+    """gr4pm_row_resampler_taps: the RowResampler's prototype at the virtual rate `phases` per input item, the Kaiser
+    design of ddc_taps with DC gain `phases` (host only: works without a GPU).  passband / stopband: the band edges in
+    units of the lower of the input rate and the output rate at max_step input items per output item: they are divided
+    by max(1, max_step), and there are ceil(taps_per_phase * max(1, max_step)) taps per phase, so a decimating handle
+    keeps the design's span in output items.  Returns phases * that many float32 taps."""
+    phases, per, max_step = int(phases), int(taps_per_phase), float(max_step)
+    if not (0 <= phases < 1 << 32 and 0 <= per < 1 << 32):
+        raise Gr4pmError("row_resampler_taps: phases and taps_per_phase must fit 32 unsigned bits")
+    span = int(math.ceil(per * max(1.0, max_step))) if math.isfinite(max_step) else 0
+    n = phases * span
+    out = np.zeros(n if 0 < n <= 4096 else 1, dtype=np.float32)  # beyond 4096 taps the design is refused before it writes
+    check(lib().gr4pm_row_resampler_taps(phases, per, max_step, float(passband), float(stopband), _np_ptr(out)),
+          "row_resampler_taps")
+    return out[:n]
+
+
+class RowResampler:
+    """gr4pm_row_resampler: rows of channel items (Ddc.extract's [rows, n]) to any real rate with the residual carrier
+    removed, every row with a step and a frequency word of its own: what acts on LineSpectrum's per-row symbol rate and
+    carrier offset on the rows themselves, so the wideband recording is read once.  phases: Q, a power of two 2 .. 256;
+    taps: Q * P float32 prototype taps at the virtual rate Q per input item (None: row_resampler_taps(phases,
+    taps_per_phase, max_step)); Q * P <= 4096.  Output item m of row r sits at pos = phase0 + m * step input items (Q32.32
+    integers, exact), takes the P input items up to floor(pos) through coefficients interpolated linearly between the
+    two nearest of the Q phases, and is then turned by exp(-2 pi j floor(freq * pos / 2^32) / 2^32): the mix comes after
+    the filter, so the block is for residual offsets well inside the prototype's passband.  A row's result depends on
+    that row alone, bit for bit, and not on where a call begins in it.  .delay_items: a tone appears (Q P - 1) / (2 Q)
+    input items late.  The handle is made on first use, on the stream that is current then; output_lengths, delay_items
+    and tile_items work without a GPU."""
+
+    ROWS_PER_CALL = 64
+    COLUMN_GRAIN = 2048
+
+    def __init__(self, phases=32, taps_per_phase=12, taps=None, max_step=1.0):
+        self.phases = int(phases)
+        if taps is None:
+            taps = row_resampler_taps(self.phases, taps_per_phase, max_step)
+        self.taps = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        if not (2 <= self.phases <= 256 and self.phases & (self.phases - 1) == 0):
+            raise Gr4pmError(f"RowResampler: {self.phases} phases, need a power of two in [2, 256]")
+        if not self.taps.size or self.taps.size % self.phases or self.taps.size > 4096:
+            raise Gr4pmError(f"RowResampler: {self.taps.size} taps for {self.phases} phases: need a multiple of the phases, "
+                             "1 .. 4096 in all")
+        if not np.all(np.isfinite(self.taps)):
+            raise Gr4pmError("RowResampler: a tap is not finite")
+        self.taps_per_phase = self.taps.size // self.phases
+        self.delay_items = fractions.Fraction(self.taps.size - 1, 2 * self.phases)
+        self._h = None
+        self._stream = None
+
+    def _handle(self):
+        if not self._h:
+            stream = _stream_handle()
+            self._stream = stream.value
+            p = _abi.RowResamplerParams(self.phases, self.taps_per_phase, _np_ptr(self.taps), stream)
+            h = C.c_void_p()
+            check(lib().gr4pm_row_resampler_create(C.byref(p), C.byref(h)), "RowResampler")
+            self._h = h
+        return self._h
+
+    def _records(self, n_rows, steps, phase0, freqs):
+        def column(values, what, lo, hi, default):
+            if values is None:
+                values = [default] * n_rows
+            values = [int(v) for v in (values.tolist() if isinstance(values, np.ndarray) else values)]
+            if len(values) != n_rows:
+                raise Gr4pmError(f"RowResampler: {len(values)} {what} for {n_rows} rows")
+            if any(not lo <= v < hi for v in values):
+                raise Gr4pmError(f"RowResampler: {what} must lie in [{lo}, {hi})")
+            return values
+        rec = np.zeros(n_rows, dtype=_abi.ROW_RECORD_DTYPE)
+        rec["step"] = np.array(column(steps, "steps", 0, 1 << 64, 1 << 32), dtype=np.uint64)
+        rec["phase0"] = np.array(column(phase0, "phase0", 0, 1 << 64, 0), dtype=np.uint64)
+        rec["freq"] = np.array(column(freqs, "freqs", -(1 << 31), 1 << 31, 0), dtype=np.int32)
+        return rec
+
+    @staticmethod
+    def _row_lengths(n_rows, n_cols, lengths):
+        if lengths is None:
+            return np.full(n_rows, n_cols, dtype=np.uint64)
+        lengths = np.asarray(lengths).reshape(-1)
+        if lengths.size != n_rows:
+            raise Gr4pmError(f"RowResampler: {lengths.size} lengths for {n_rows} rows")
+        if lengths.size and (int(lengths.min()) < 0 or int(lengths.max()) >= 1 << 64):
+            raise Gr4pmError("RowResampler: lengths must fit 64 unsigned bits")
+        return np.ascontiguousarray(lengths.astype(np.uint64))
+
+    def output_lengths(self, lengths, steps, phase0=None, n_cols=None):
+        """M_r per row (numpy int64; host only): the output items m whose newest input item floor(phase0 + m step) is at
+        most lengths[r] + P - 2, so the filter runs out over the row's end; cut at n_cols where given."""
+        lengths = self._row_lengths(len(lengths), 1 << 63, lengths)
+        rec = self._records(lengths.size, steps, phase0, None)
+        out = np.zeros(lengths.size, dtype=np.uint64)
+        cap = 1 << 31 if n_cols is None else int(n_cols)
+        for lo in range(0, lengths.size, self.ROWS_PER_CALL):
+            part, rows = lengths[lo:lo + self.ROWS_PER_CALL], rec[lo:lo + self.ROWS_PER_CALL]
+            check(lib().gr4pm_row_resampler_output_lengths(self.taps_per_phase, int(part.max()), _np_ptr(part), _np_ptr(rows),
+                                                           part.size, cap, _np_ptr(out[lo:lo + self.ROWS_PER_CALL])),
+                  "RowResampler.output_lengths")
+        return out.astype(np.int64)
+
+    def tile_items(self, steps):
+        """the output items of one tile of a call with these steps (host only): nothing but the time depends on it"""
+        return int(lib().gr4pm_row_resampler_tile_items(self.taps_per_phase, max(int(s) for s in steps)))
+
+    def process_rows(self, x, lengths, steps, phase0=None, freqs=None, n_cols=None, out=None):
+        """gr4pm_row_resampler_process: x: a CUDA complex64 tensor [R, n] with contiguous rows (any row stride >= n);
+        lengths: R item counts <= n (None: n each); steps, phase0 (None: 0): R Python or numpy integers in Q32.32, input
+        items per output item and the position of output item 0; freqs (None: 0): R signed frequency words, cycles per
+        input item times 2^32.  Returns (rows, out_lengths): rows is CUDA complex64 [R, n_cols] (None: the smallest
+        multiple of 2048 that holds the longest row) with rows[r, :out_lengths[r]] the resampled row and +0 behind it,
+        the layout NativeMultiChannelReceiver.submit takes; out_lengths is numpy int64.  out: an optional CUDA complex64
+        [R, >= n_cols] tensor with contiguous rows.  Any number of rows: 64 go into one call.  Does not wait."""
+        torch = _torch()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
+                (x.shape[1] <= 1 or x.stride(1) == 1) and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
+            raise TypeError("x must be a [rows, n] complex64 CUDA tensor with contiguous rows")
+        n_rows, n_in = x.shape
+        lengths = self._row_lengths(n_rows, n_in, lengths)
+        rec = self._records(n_rows, steps, phase0, freqs)
+        if n_cols is None:
+            longest = int(self.output_lengths(lengths, rec["step"], rec["phase0"]).max()) if n_rows else 0
+            n_cols = -(-longest // self.COLUMN_GRAIN) * self.COLUMN_GRAIN
+        n_cols = int(n_cols)
+        if n_cols < 0:
+            raise Gr4pmError("RowResampler: n_cols must not be negative")
+        h = self._handle()
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        out = _rows_output(out, n_rows, n_cols, x.device, "RowResampler")
+        out_lengths = np.zeros(n_rows, dtype=np.uint64)
+        for lo in range(0, n_rows, self.ROWS_PER_CALL):
+            rows, part, dst = x[lo:lo + self.ROWS_PER_CALL], lengths[lo:lo + self.ROWS_PER_CALL], out[lo:lo + self.ROWS_PER_CALL]
+            stride = rows.stride(0) if rows.shape[0] > 1 else max(n_in, 1)
+            out_stride = dst.stride(0) if dst.shape[0] > 1 else max(dst.shape[1], n_cols)
+            check(lib().gr4pm_row_resampler_process(
+                h, rows.data_ptr(), stride, n_in, _np_ptr(part), _np_ptr(rec[lo:lo + self.ROWS_PER_CALL]), part.size,
+                dst.data_ptr(), out_stride, n_cols, _np_ptr(out_lengths[lo:lo + self.ROWS_PER_CALL])), "RowResampler.process_rows")
+        self._last = x  # the calls do not wait: the input lives until the next call
+        return out[:, :n_cols], out_lengths.astype(np.int64)
+
+    @staticmethod
+    def steps_for(rates, samples_per_symbol=4):
+        """round(2^32 / (samples_per_symbol * rho_r)) per row, in Python integers: the Q32.32 step that puts
+        samples_per_symbol output items on a symbol of a row with rho_r symbols per item"""
+        den = [fractions.Fraction(float(r)) * int(samples_per_symbol) for r in rates]
+        if any(d <= 0 for d in den):
+            raise Gr4pmError("RowResampler: a symbol rate must be positive")
+        return [int(round(fractions.Fraction(1 << 32) / d)) for d in den]
+
+    def to_samples_per_symbol(self, x, lengths, rates, offsets=None, samples_per_symbol=4, n_cols=None):
+        """process_rows with step_r = round(2^32 / (samples_per_symbol rates[r])) and freq_r = round(offsets[r] 2^32):
+        rates in symbols per item and offsets in cycles per item, as LineSpectrum.symbol_rate and .carrier_offset give
+        them.  Returns (rows, out_lengths) with samples_per_symbol items per symbol and the offsets removed."""
+        steps = self.steps_for(rates, samples_per_symbol)
+        freqs = None
+        if offsets is not None:
+            freqs = [int(round(fractions.Fraction(float(d)) * (1 << 32))) for d in offsets]
+        return self.process_rows(x, lengths, steps, None, freqs, n_cols)
+
+    def __del__(self):
+        _destroy(self, "gr4pm_row_resampler_destroy")
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

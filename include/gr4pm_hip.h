@@ -1549,6 +1549,84 @@ gr4pm_status gr4pm_find_line(const double* spectrum, size_t n, const gr4pm_line_
 gr4pm_status gr4pm_simplest_ratio(double value, double rel_tol, uint32_t max_num, uint32_t max_den, uint32_t* num,
                                   uint32_t* den);
 
+/* ====================================================================================
+ * RowResampler -- rows of channel items to any real rate with the residual carrier removed, every row with a
+ * step and a frequency of its own (the project's own block).  It is what acts on a
+ * LineSpectrum's per-row symbol rate and offset where they were measured: on the burst rows of
+ * gr4pm_ddc_extract, without going back to the wideband recording.
+ *
+ * Handle: Q phases, a power of two 2 .. 256; P taps per phase, 1 <= P, Q P <= 4096; a real prototype
+ * h[0 .. Q P - 1] at the virtual rate Q per input item, copied from HOST floats at create, h[Q P] = 0.  Two float
+ * tables are made on the host:
+ *     H[q][s]  = h[s Q + q]
+ *     Dh[q][s] = fl32(h[s Q + q + 1] - h[s Q + q])       the difference in double from the float taps, rounded once
+ * Call: R <= 64 rows x[r stride + i] of DEVICE complex64, row r with n_r = lengths[r] items, and R HOST records
+ * {step, phase0, freq}, which travel to the kernel by value.  step and phase0 are positions in input items with 32
+ * fractional bits, 2^26 <= step <= 2^38 (1/64 .. 64 input items per output item); freq is the SIGNED frequency
+ * word, cycles per input item times 2^32 (the position has fractional bits, so w and w - 2^32 are not the same
+ * frequency here).  Output item m of row r, with b = 32 - log2 Q:
+ *     pos   = phase0 + m step                             exact in 64 bits
+ *     i     = pos >> 32,  mu = pos & 0xffffffff,  q = mu >> b
+ *     alpha = fl32(mu & (2^b - 1)) 2^-b                   the conversion rounds to nearest; alpha may round to 1
+ *     c_s   = fmaf(alpha, Dh[q][s], H[q][s])
+ *     acc   = sum_{s=0}^{P-1} c_s x_r[i - s]              one accumulator from +0, s ascending:
+ *                                                         re = fmaf(c_s, x.re, re), im = fmaf(c_s, x.im, im)
+ *     theta = (freq (pos >> 32) + ((int64(freq) int64(mu)) >> 32)) mod 2^32      the shift is arithmetic:
+ *                                                         theta = floor(freq pos / 2^32) mod 2^32
+ *     y_r[m] = exp(-2 pi j theta / 2^32) acc              the Ddc's rotator: double sincospi of -theta / 2^31, an
+ *                                                         exact argument, rounded to float; four fmaf from zero
+ * A sample with i - s < 0 or i - s >= n_r is the operand +0 and IS NEVER LOADED: a row may end at its buffer's last
+ * byte and may hold anything behind n_r.  The mix comes AFTER the filter and the filter is not re-centred: the
+ * block is for residual offsets well inside the prototype's passband.  A tone at the input appears
+ * (Q P - 1) / (2 Q) input items late.
+ * Output length: M_r is the number of m with pos >> 32 <= n_r + P - 2 (the filter runs out over the row's end):
+ * 0 if n_r = 0 or phase0 is beyond that, and cut at n_cols_out.  out[r out_stride + m] = y_r[m] for m < M_r and +0
+ * up to n_cols_out; out may be uninitialised.  M_r is computed on the host.
+ * A ROW'S RESULT DEPENDS ON THAT ROW ALONE, BIT FOR BIT, not on the rows beside it or on R; and items m0 .. of a call
+ * equal items 0 .. of a call with phase0 + m0 step: nothing depends on the tile an item falls in.
+ * ================================================================================== */
+typedef struct gr4pm_row_resampler gr4pm_row_resampler;
+typedef struct {
+    uint64_t step;              /* input items per output item, Q32.32: 2^26 .. 2^38 */
+    uint64_t phase0;            /* position of output item 0, Q32.32: below 2^63 */
+    int32_t freq;               /* cycles per input item times 2^32, signed */
+} gr4pm_row_record;
+typedef struct {
+    uint32_t phases;            /* Q */
+    uint32_t taps_per_phase;    /* P (0 with NULL taps: 12) */
+    const float* taps;          /* host: Q P floats, copied at create (NULL: gr4pm_row_resampler_taps(Q, P, 1, 0.25, 0.75)) */
+    void* stream;               /* hipStream_t (NULL: the default stream) */
+} gr4pm_row_resampler_params;
+/* The prototype, host only: the Kaiser design of gr4pm_ddc_taps at the virtual rate with DC gain Q.  The band edges
+ * are in units of the lower of the input rate and the output rate at max_step (input items per output item, 1/64 ..
+ * 64): they are divided by max(1, max_step), and the span is P = ceil(taps_per_phase max(1, max_step)) taps per
+ * phase, so a decimating handle keeps the design's span in output items.  out: room for Q P floats.  A Q that is
+ * no power of two in 2 .. 256, taps_per_phase == 0, Q P > 4096, a max_step out of range or not finite, or edges
+ * without 0 <= passband < stopband and passband + stopband <= 1: GR4PM_ERR_INVALID. */
+gr4pm_status gr4pm_row_resampler_taps(size_t phases, size_t taps_per_phase, double max_step, double passband,
+                                      double stopband, float* out);
+/* a bad Q, Q P > 4096 or a non-finite tap: GR4PM_ERR_INVALID, no handle */
+gr4pm_status gr4pm_row_resampler_create(const gr4pm_row_resampler_params* params, gr4pm_row_resampler** out);
+void gr4pm_row_resampler_destroy(gr4pm_row_resampler* h);
+/* Host only, no handle: out_lengths[r] = M_r of a handle with taps_per_phase = P for the rows' lengths (HOST, NULL:
+ * n_cols each) and records, cut at n_cols_out.  Refuses what gr4pm_row_resampler_process refuses of them. */
+gr4pm_status gr4pm_row_resampler_output_lengths(size_t taps_per_phase, size_t n_cols, const uint64_t* lengths,
+                                                const gr4pm_row_record* rows, size_t n_rows, size_t n_cols_out,
+                                                uint64_t* out_lengths);
+/* Host only: the output items of a tile of a call whose largest step is max_step, for P taps per phase; 0 for
+ * arguments a call would refuse.  Nothing depends on it but the time a call takes. */
+uint32_t gr4pm_row_resampler_tile_items(size_t taps_per_phase, uint64_t max_step);
+/* x: DEVICE, R rows of n_cols items, `stride` items apart.  lengths: HOST, R items, copied by the call (NULL: every
+ * row has n_cols items).  rows: HOST, R records, copied by the call.  out: DEVICE, R rows of n_cols_out items,
+ * out_stride apart.  out_lengths: HOST, R items: M_r.  Enqueues on the handle's stream, does not wait and reads
+ * nothing back.  Refused with gr4pm_last_error set and nothing enqueued -- GR4PM_ERR_INVALID: R > 64, a length above
+ * n_cols, R > 1 with stride < n_cols or out_stride < n_cols_out, a step out of range, a NULL rows, out_lengths or
+ * out, a NULL x when any length is not zero; GR4PM_ERR_OVERFLOW: n_r + P - 1 >= 2^32, phase0 >= 2^63,
+ * n_cols_out > 2^31.  R = 0 or n_cols_out = 0: OK, nothing enqueued. */
+gr4pm_status gr4pm_row_resampler_process(gr4pm_row_resampler* h, const gr4pm_c64* x, size_t stride, size_t n_cols,
+                                         const uint64_t* lengths, const gr4pm_row_record* rows, size_t n_rows,
+                                         gr4pm_c64* out, size_t out_stride, size_t n_cols_out, uint64_t* out_lengths);
+
 #ifdef __cplusplus
 }
 #endif

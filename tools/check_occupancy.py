@@ -134,6 +134,9 @@ BUDGETS = [
     # SIMD
     (r"k_line_spectrum_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
     (r"k_line_spectrum_reduceILb", dict(vgpr=64, scratch=0)),
+    # the RowResampler block: one accumulator, a coefficient pair and the double-precision rotator per lane, eight waves
+    # per SIMD; its LDS is dynamic, at most 64 KiB of tables and stage
+    (r"k_row_resample", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
 ]
 
 
