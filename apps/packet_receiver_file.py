@@ -3,7 +3,7 @@
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
                             [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
-                            [--refine] [--decimate auto] [--burst-rows]
+                            [--refine] [--decimate auto] [--burst-rows] [--fft-ddc]
                             [--scan [--scan-items N] [--bursts] [--waterfall FILE.npy [--waterfall-average R]]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
@@ -261,9 +261,9 @@ def tune_value(v):
 
 
 def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
-                 fmt="cf32", scale=None, tune=None, decimate=None):
+                 fmt="cf32", scale=None, tune=None, decimate=None, fft_ddc=False):
     """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures).  decimate: an
-    integer, "N/M" or (N, M)"""
+    integer, "N/M" or (N, M).  fft_ddc: an FftDdc in place of the Ddc (a power-of-two decimation)"""
     pkg = pkg or ge.load_package()
     file_dtype = FILE_DTYPES[fmt]
     shape = (chunk_items,) if fmt == "cf32" else (chunk_items, 2)  # integer IQ: [items, (I, Q)]
@@ -279,7 +279,10 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
     ddc = None
     if tune is not None or decimate is not None:
         dec, interp = (1, 1) if decimate is None else (decimate if isinstance(decimate, tuple) else decimation(decimate))
-        ddc = pkg.Ddc([0.0 if tune is None else tune], dec, interpolation=interp, max_frames=chunk_items)
+        if fft_ddc:
+            ddc = pkg.FftDdc([0.0 if tune is None else tune], dec)
+        else:
+            ddc = pkg.Ddc([0.0 if tune is None else tune], dec, interpolation=interp, max_frames=chunk_items)
     fft = 3072  # smallest batch the receiver takes in this mode (one header window + one FFT block)
     pinned = [torch.empty(shape, dtype=file_dtype).pin_memory() for _ in range(2)]
     staged = [torch.empty(shape, dtype=file_dtype, device=dev) for _ in range(2)]
@@ -386,7 +389,17 @@ def main(argv=None):
                          "samples per symbol and remove its residual offset with a RowResampler, each row by its own "
                          "LineSpectrum reading, and receive the rows; no streaming Ddc runs over the file, which has to fit "
                          "one chunk")
+    ap.add_argument("--fft-ddc", action="store_true",
+                    help="with --tune and a power-of-two --decimate of 4 .. 64: an FftDdc (the fast-convolution form, DESIGN "
+                         "section 25) in place of the Ddc; it delivers whole segments, so up to one hop of samples at the "
+                         "end of the file stays undelivered")
     a = ap.parse_args(argv)
+    if a.fft_ddc:
+        d = a.decimate
+        if (a.tune is None or not isinstance(d, tuple) or d[1] != 1 or d[0] not in (4, 8, 16, 32, 64) or a.burst_rows
+                or a.scan):
+            ap.error("--fft-ddc needs --tune and --decimate 4, 8, 16, 32 or 64 (no ratio, not auto), and goes with neither "
+                     "--burst-rows nor --scan")
     if a.burst_rows and (a.tune is None or a.decimate is None or a.scan or a.zmq or a.zmq_ports):
         ap.error("--burst-rows needs --tune and --decimate (values or auto) and goes with neither --scan nor --zmq")
     if (a.bursts or a.waterfall) and not a.scan:
@@ -446,7 +459,7 @@ def main(argv=None):
                 print(f"--decimate auto: {r['rate']:.6f} symbols per file sample: --decimate {dec}/{interp}")
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
-                     fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate)
+                     fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate, fft_ddc=a.fft_ddc)
     print(f"{r['items']} of {r['file_items']} samples in {r['seconds']:.3f} s = {r['items'] / r['seconds'] / 1e6:.1f} Msps "
           f"(file and PCIe included); headers {r['headers']} ({r['invalid_headers']} invalid), packets "
           f"{len(r['packets'])} ({r['crc_failures']} CRC failures), {sum(len(p) for p in r['packets'])} bytes")

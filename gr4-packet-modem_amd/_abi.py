@@ -254,6 +254,12 @@ class RowResamplerParams(C.Structure):
     _fields_ = [("phases", C.c_uint32), ("taps_per_phase", C.c_uint32), ("taps", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class FftDdcParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("decimation", C.c_size_t), ("frequencies", C.c_void_p), ("taps", C.c_void_p),
+                ("n_taps", C.c_size_t), ("taps_per_phase", C.c_size_t), ("overlap", C.c_int64), ("images", C.c_size_t),
+                ("start_index", C.c_uint64), ("stream", C.c_void_p)]
+
+
 # gr4pm_row_record: 24 bytes, the last four are padding
 ROW_RECORD_DTYPE = np.dtype({"names": ["step", "phase0", "freq"], "formats": ["<u8", "<u8", "<i4"], "offsets": [0, 8, 16],
                              "itemsize": 24})
@@ -350,6 +356,8 @@ EXPORTS = [
     "gr4pm_find_line", "gr4pm_simplest_ratio",
     "gr4pm_row_resampler_taps", "gr4pm_row_resampler_create", "gr4pm_row_resampler_destroy",
     "gr4pm_row_resampler_output_lengths", "gr4pm_row_resampler_tile_items", "gr4pm_row_resampler_process",
+    "gr4pm_fft_ddc_taps", "gr4pm_fft_ddc_create", "gr4pm_fft_ddc_destroy", "gr4pm_fft_ddc_reset", "gr4pm_fft_ddc_frames_for",
+    "gr4pm_fft_ddc_frequencies", "gr4pm_fft_ddc_sizes", "gr4pm_fft_ddc_process", "gr4pm_fft_ddc_process_iq",
 ]
 
 _lib = None
@@ -598,6 +606,16 @@ def lib():
     L.gr4pm_row_resampler_tile_items.argtypes = [sz, C.c_uint64]
     L.gr4pm_row_resampler_tile_items.restype = C.c_uint32
     L.gr4pm_row_resampler_process.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, sz, sz, vp]
+    L.gr4pm_fft_ddc_taps.argtypes = [sz, sz, vp]
+    L.gr4pm_fft_ddc_create.argtypes = [C.POINTER(FftDdcParams), C.POINTER(vp)]
+    L.gr4pm_fft_ddc_destroy.argtypes = [vp]
+    L.gr4pm_fft_ddc_destroy.restype = None
+    L.gr4pm_fft_ddc_reset.argtypes = [vp]
+    L.gr4pm_fft_ddc_frames_for.argtypes = [vp, sz, szp]
+    L.gr4pm_fft_ddc_frequencies.argtypes = [vp, vp]
+    L.gr4pm_fft_ddc_sizes.argtypes = [vp, szp, szp]
+    L.gr4pm_fft_ddc_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
+    L.gr4pm_fft_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

@@ -2094,6 +2094,82 @@ class Ddc:
         _destroy(self, "gr4pm_ddc_destroy")
 
 
+def fft_ddc_taps(decimation, taps_per_phase=12):
+    """gr4pm_fft_ddc_taps: the FftDdc's default prototype, ddc_taps(decimation, taps_per_phase) for a power-of-two
+    decimation in 4 .. 64 (host only: works without a GPU)."""
+    n = int(decimation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_fft_ddc_taps(int(decimation), int(taps_per_phase), _np_ptr(out)), "fft_ddc_taps")
+    return out[:n]
+
+
+class FftDdc:
+    """gr4pm_fft_ddc: the Ddc for many channels and a power-of-two decimation (4 .. 64), as a fast-convolution filter
+    bank: one forward 2048-point transform of the wideband stream per segment, shared by all len(frequencies) <= 64
+    channels; per channel a product over `images` * 2048 / decimation bins around the channel's nearest bin, a fold and
+    an inverse transform of 2048 / decimation points.  Row k is the band centred on frequencies[k]
+    on the Ddc's own frame grid; with images = decimation it is the Ddc's result up to float32 rounding, with fewer
+    images it differs by the prototype's response outside +-images / (2 decimation) cycles per sample (images = 1 cuts
+    inside the default design's transition band).  taps: float32 prototype taps (None: fft_ddc_taps(decimation,
+    taps_per_phase)); overlap: a multiple of decimation with len(taps) - 1 <= overlap <= 1984 (None: the smallest
+    multiple of 256 that is >= len(taps) - 1); .hop = 2048 - overlap.  process_bulk() takes any number of samples and
+    delivers whole segments, hop / decimation frames each; the rest stays on the device, and any cutting of the stream
+    into calls gives the same bits.  Frequencies are fixed.  The handle works on the stream that is current when it is
+    made."""
+
+    def __init__(self, frequencies, decimation, taps=None, taps_per_phase=12, overlap=None, images=2, start_index=0):
+        self.decimation, self.images = int(decimation), int(images)
+        f, self.taps, self.start_index = _xlate_settings("FftDdc", frequencies, self.decimation, taps, taps_per_phase,
+                                                         start_index, fft_ddc_taps)
+        if self.images < 0 or (overlap is not None and not 0 <= int(overlap) < 1 << 62):
+            raise Gr4pmError("FftDdc: images and overlap must not be negative")
+        self.n_channels = self.n_rows = int(f.size)
+        stream = _stream_handle()
+        self._stream = stream.value
+        self._h = C.c_void_p()
+        p = _abi.FftDdcParams(self.n_channels, self.decimation, _np_ptr(f) if f.size else None, _np_ptr(self.taps),
+                              self.taps.size, int(taps_per_phase), -1 if overlap is None else int(overlap), self.images,
+                              self.start_index, stream)
+        check(lib().gr4pm_fft_ddc_create(C.byref(p), C.byref(self._h)), "FftDdc")
+        q = np.zeros(self.n_channels, dtype=np.float64)
+        check(lib().gr4pm_fft_ddc_frequencies(self._h, _np_ptr(q)), "FftDdc.frequencies")
+        self.frequencies = q
+        v, hop = C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_fft_ddc_sizes(self._h, C.byref(v), C.byref(hop)), "FftDdc.sizes")
+        self.overlap, self.hop = v.value, hop.value
+
+    def frames_for(self, n_in):
+        """frames per row the next process_bulk() of n_in samples delivers"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_ddc_frames_for(self._h, int(n_in), C.byref(n)), "FftDdc.frames_for")
+        return n.value
+
+    def reset(self):
+        """back to start_index: zero prehistory, no carried samples"""
+        check(lib().gr4pm_fft_ddc_reset(self._h), "FftDdc.reset")
+
+    def process_bulk(self, x, out=None, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ: an int16 (sc16),
+        int8 (sc8) or uint8 (cu8) CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it
+        (gr4pm_fft_ddc_process_iq: the same result bit for bit; calls of any format mix on one handle).  Returns
+        y[n_channels, frames], the array NativeMultiChannelReceiver.submit() takes; out: an optional CUDA complex64
+        [n_channels, >= frames] tensor with contiguous rows and any row stride to write into."""
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        out = _rows_output(out, self.n_channels, self.frames_for(n_in), x.device, "FftDdc")
+        n = C.c_size_t(0)
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        if fmt is None:
+            check(lib().gr4pm_fft_ddc_process(self._h, x.data_ptr(), n_in, out.data_ptr(), stride, out.shape[1], C.byref(n)),
+                  "FftDdc.process")
+        else:
+            check(lib().gr4pm_fft_ddc_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), stride, out.shape[1],
+                                                 C.byref(n)), "FftDdc.process_iq")
+        return out[:, : n.value]
+
+    def __del__(self):
+        _destroy(self, "gr4pm_fft_ddc_destroy")
+
+
 def duc_taps(interpolation, taps_per_phase=12, passband=0.25, stopband=0.75):
     """gr4pm_duc_taps: the Duc's prototype low-pass, the Kaiser design of ddc_taps with taps_per_phase * interpolation
     float32 taps and DC gain `interpolation`, scaled in double before the one rounding to float32 (host only: works

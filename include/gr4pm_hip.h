@@ -1627,6 +1627,65 @@ gr4pm_status gr4pm_row_resampler_process(gr4pm_row_resampler* h, const gr4pm_c64
                                          const uint64_t* lengths, const gr4pm_row_record* rows, size_t n_rows,
                                          gr4pm_c64* out, size_t out_stride, size_t n_cols_out, uint64_t* out_lengths);
 
+/* ---- FftDdc: K off-grid channels from one shared transform (the project's own block) ----------
+ * The Ddc's drop-in for power-of-two decimations and many channels: a fast-convolution (overlap-save) filter bank.
+ * N = 2048, K channels (1 .. 64), D a power of two in 4 .. 64, B = N / D, a real finite prototype h[0 .. L - 1], an
+ * overlap V with D | V and L - 1 <= V <= N - 64 (overlap < 0: the smallest multiple of 256 that is >= L - 1),
+ * hop = N - V, images = R, a power of two with 1 <= R <= D.  x[i] = 0 before the handle's first sample, whose absolute
+ * index is start_index.
+ *     w_k = llrint(f_k 2^32) mod 2^32,   c_k = floor(w_k N / 2^32 + 1 / 2) mod N   (the nearest bin, in integers)
+ *     segment s: the N items from a_s = s hop - V + D - 1 on (relative to the first sample),  X_s = FFT_N(x_s)
+ *         (forward, unnormalised, no window)
+ *     G_k[u] = (1 / N) sum_t h[t] exp(-2 pi j ((c_k + u) / N - w_k / 2^32) t),   u in [-R B / 2, R B / 2)
+ *         (host, double, each component rounded to float once)
+ *     Z[u] = X_s[(c_k + u) mod N] G_k[u],   Y[v] = sum_{u = v mod B} Z[u]  (R terms, ascending u)
+ *     y'[n'] = sum_v Y[v] exp(+2 pi j v n' / B),   n' = V / D .. B - 1 are kept: hop / D frames a segment
+ *     p = n' D,   i = start_index + a_s + p,   phi = (w_k i - c_k 2^21 p) mod 2^32   (wrapping integers)
+ *     out_k[s hop / D + n' - V / D] = exp(-2 pi j phi / 2^32) y'[n']   (the Ddc's rotator: double sincospi of the
+ *         exact argument rounded to float, then four fmaf from zero)
+ * Frame n of row k lies at i = start_index + n D + D - 1, the Ddc's own frame grid.  With R = D the definition is the
+ * Ddc's y_k[n] in exact arithmetic; with R < D it differs by the prototype's response outside +-R / (2 D) cycles per
+ * sample: |y - y_Ddc| <= ||x_s||_2 ||H_k outside the slice||_2 / sqrt(N).  R = 1 cuts inside the default design's
+ * transition band; it is accepted.  A call delivers whole segments, hop / D frames each; the handle carries V samples
+ * plus the incomplete hop, and any cutting of the stream into calls gives the same bits. */
+typedef struct gr4pm_fft_ddc gr4pm_fft_ddc;
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t decimation;          /* D: a power of two, 4 .. 64 */
+    const double* frequencies;  /* HOST, K items, cycles per input sample, finite */
+    const float* taps;          /* HOST, n_taps items, finite; NULL: gr4pm_fft_ddc_taps(D, taps_per_phase) */
+    size_t n_taps;              /* L */
+    size_t taps_per_phase;      /* of the design when taps is NULL */
+    int64_t overlap;            /* V; negative: the default */
+    size_t images;              /* R */
+    uint64_t start_index;
+    void* stream;               /* hipStream_t */
+} gr4pm_fft_ddc_params;
+/* Host only: the Ddc's design (gr4pm_ddc_taps with the band edges 0.25 and 0.75 of the output rate) of
+ * taps_per_phase * decimation floats for a decimation the FftDdc takes. */
+gr4pm_status gr4pm_fft_ddc_taps(size_t decimation, size_t taps_per_phase, float* out);
+/* Refused with GR4PM_ERR_INVALID and no handle: K out of range, a NULL or non-finite frequency, D or R no power of two
+ * or out of range, a non-finite tap, n_taps out of range, V no multiple of D, below L - 1 or above N - 64. */
+gr4pm_status gr4pm_fft_ddc_create(const gr4pm_fft_ddc_params* params, gr4pm_fft_ddc** out);
+void gr4pm_fft_ddc_destroy(gr4pm_fft_ddc* h);
+/* back to start_index: zero prehistory, nothing carried */
+gr4pm_status gr4pm_fft_ddc_reset(gr4pm_fft_ddc* h);
+/* frames per row the next call of n_in samples delivers */
+gr4pm_status gr4pm_fft_ddc_frames_for(const gr4pm_fft_ddc* h, size_t n_in, size_t* n_frames);
+/* out: HOST, K items: w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_fft_ddc_frequencies(const gr4pm_fft_ddc* h, double* out);
+gr4pm_status gr4pm_fft_ddc_sizes(const gr4pm_fft_ddc* h, size_t* overlap, size_t* hop);
+/* in: DEVICE, n_in samples.  out: DEVICE, K rows out_stride items apart with room for out_cap_frames each.  Enqueues on
+ * the handle's stream and does not wait.  Refused with gr4pm_last_error set, *n_frames = 0 and nothing enqueued: a NULL
+ * in with n_in > 0, a NULL out or out_stride below the frames with K > 1 when the call delivers frames
+ * (GR4PM_ERR_INVALID); n_in > 2^40 or fewer than the frames of room (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
+gr4pm_status gr4pm_fft_ddc_process(gr4pm_fft_ddc* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                                   size_t out_cap_frames, size_t* n_frames);
+/* The same for integer IQ (GR4PM_IQ_SC16 / SC8 / CU8; scale 0: the format's default): gr4pm_fft_ddc_process on
+ * gr4pm_iq_unpack(in) bit for bit; calls of any format mix on one handle. */
+gr4pm_status gr4pm_fft_ddc_process_iq(gr4pm_fft_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                      size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,11 @@ BUDGETS = [
     # the Spectrum block: the correlator's eight exchange buffers and twiddles plus 8 KiB of window, two waves per SIMD
     # 
     (r"k_spectrum_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
+    # the FftDdc block: the Spectrum's wave without window, sums and maxima (184 registers as built, two waves per SIMD by
+    # its LDS) and a one-wave inverse transform per (segment, channel) with two 4 KiB buffers and 2 KiB of twiddles (46
+    # registers as built)
+    (r"k_fft_ddc_forwardILi", dict(vgpr=184, lds=151552, lds_exact=True, scratch=0)),
+    (r"k_fft_ddc_channel", dict(vgpr=48, lds=10240, lds_exact=True, scratch=0)),
     # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
     # section 21)
     (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
