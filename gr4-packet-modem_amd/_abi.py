@@ -260,6 +260,12 @@ class FftDdcParams(C.Structure):
                 ("start_index", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class FftDdcMixedParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("decimations", C.c_void_p), ("frequencies", C.c_void_p), ("taps", C.c_void_p),
+                ("n_taps", C.c_void_p), ("taps_per_phase", C.c_size_t), ("images", C.c_void_p), ("overlap", C.c_int64),
+                ("start_index", C.c_uint64), ("stream", C.c_void_p)]
+
+
 # gr4pm_row_record: 24 bytes, the last four are padding
 ROW_RECORD_DTYPE = np.dtype({"names": ["step", "phase0", "freq"], "formats": ["<u8", "<u8", "<i4"], "offsets": [0, 8, 16],
                              "itemsize": 24})
@@ -358,6 +364,8 @@ EXPORTS = [
     "gr4pm_row_resampler_output_lengths", "gr4pm_row_resampler_tile_items", "gr4pm_row_resampler_process",
     "gr4pm_fft_ddc_taps", "gr4pm_fft_ddc_create", "gr4pm_fft_ddc_destroy", "gr4pm_fft_ddc_reset", "gr4pm_fft_ddc_frames_for",
     "gr4pm_fft_ddc_frequencies", "gr4pm_fft_ddc_sizes", "gr4pm_fft_ddc_process", "gr4pm_fft_ddc_process_iq",
+    "gr4pm_fft_ddc_mixed_create", "gr4pm_fft_ddc_mixed_destroy", "gr4pm_fft_ddc_mixed_reset", "gr4pm_fft_ddc_mixed_frames_for",
+    "gr4pm_fft_ddc_mixed_frequencies", "gr4pm_fft_ddc_mixed_sizes", "gr4pm_fft_ddc_mixed_process", "gr4pm_fft_ddc_mixed_process_iq",
 ]
 
 _lib = None
@@ -616,6 +624,15 @@ def lib():
     L.gr4pm_fft_ddc_sizes.argtypes = [vp, szp, szp]
     L.gr4pm_fft_ddc_process.argtypes = [vp, vp, sz, vp, sz, sz, szp]
     L.gr4pm_fft_ddc_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, szp]
+    L.gr4pm_fft_ddc_mixed_create.argtypes = [C.POINTER(FftDdcMixedParams), C.POINTER(vp)]
+    L.gr4pm_fft_ddc_mixed_destroy.argtypes = [vp]
+    L.gr4pm_fft_ddc_mixed_destroy.restype = None
+    L.gr4pm_fft_ddc_mixed_reset.argtypes = [vp]
+    L.gr4pm_fft_ddc_mixed_frames_for.argtypes = [vp, sz, vp]
+    L.gr4pm_fft_ddc_mixed_frequencies.argtypes = [vp, vp]
+    L.gr4pm_fft_ddc_mixed_sizes.argtypes = [vp, szp, szp]
+    L.gr4pm_fft_ddc_mixed_process.argtypes = [vp, vp, sz, vp, sz, sz, vp]
+    L.gr4pm_fft_ddc_mixed_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, vp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

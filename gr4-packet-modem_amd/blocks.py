@@ -2170,6 +2170,98 @@ class FftDdc:
         _destroy(self, "gr4pm_fft_ddc_destroy")
 
 
+def fft_ddc_decimation(bandwidth):
+    """the decimation the MixedFftDdc gives a carrier of `bandwidth` cycles per wideband sample (find_carriers' field):
+    the largest power of two <= provisional_decimation(bandwidth), at most 64 (host only).  The row then holds the
+    carrier at 4 to 8 samples per symbol or more, which RowResampler brings to 4.  Below 4 (a carrier wider than 0.1 of
+    the band) raises Gr4pmError: that carrier is the Ddc's."""
+    d = provisional_decimation(bandwidth)
+    if d < 4:
+        raise Gr4pmError(f"fft_ddc_decimation: a bandwidth of {float(bandwidth)} gives a decimation of {d}, below 4")
+    return min(64, 1 << (d.bit_length() - 1))
+
+
+class MixedFftDdc:
+    """gr4pm_fft_ddc_mixed: the FftDdc with a decimation per channel: carriers of different symbol rates from one pass
+    over the stream and one forward transform per segment.  decimations[k] is a power of two in
+    4 .. 64; row k is the band centred on frequencies[k] on the Ddc's frame grid at decimations[k], as
+    FftDdc([frequencies[k]], decimations[k]) would give it, and with all decimations equal the block is the FftDdc bit
+    for bit.  taps: a list of one float32 prototype per channel (None: fft_ddc_taps(decimations[k], taps_per_phase)
+    each); images: an int or one per channel; overlap: one for the handle, a multiple of max(decimations) with
+    max(decimations) - decimations[k] + len(taps[k]) - 1 <= overlap <= 1984 for every k (None: the smallest multiple of
+    256 that takes all of them); .hop = 2048 - overlap.  process_bulk() takes any number of samples and delivers whole
+    segments, hop / decimations[k] frames of row k each; the rest stays on the device, and any cutting of the stream
+    into calls gives the same bits.  The handle works on the stream that is current when it is made."""
+
+    def __init__(self, frequencies, decimations, taps=None, taps_per_phase=12, overlap=None, images=2, start_index=0):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
+        if f.ndim != 1:
+            raise Gr4pmError("MixedFftDdc: frequencies must be a list of numbers")
+        K = int(f.size)
+        dec = [int(d) for d in np.atleast_1d(decimations)]
+        img = [int(images)] * K if np.ndim(images) == 0 else [int(r) for r in images]
+        if len(dec) != K or len(img) != K or (taps is not None and len(taps) != K):
+            raise Gr4pmError(f"MixedFftDdc: {K} frequencies need {K} decimations, {K} images (or one) and {K} prototypes (or None)")
+        if min(dec + img + [0]) < 0 or (overlap is not None and not 0 <= int(overlap) < 1 << 62):
+            raise Gr4pmError("MixedFftDdc: decimations, images and overlap must not be negative")
+        self.start_index = int(start_index)
+        if not 0 <= self.start_index < 1 << 64:
+            raise Gr4pmError("MixedFftDdc: start_index must fit 64 unsigned bits")
+        if taps is not None:
+            self.taps = [np.ascontiguousarray(t, dtype=np.float32).reshape(-1) for t in taps]
+        else:
+            self.taps = [fft_ddc_taps(d, taps_per_phase) for d in dec]
+        self.decimations, self.images = np.array(dec, dtype=np.int64), np.array(img, dtype=np.int64)
+        self.n_channels = self.n_rows = K
+        d_arr, r_arr = np.array(dec, dtype=np.uintp), np.array(img, dtype=np.uintp)
+        l_arr = np.array([t.size for t in self.taps], dtype=np.uintp)
+        all_taps = np.ascontiguousarray(np.concatenate(self.taps + [np.zeros(1, dtype=np.float32)]))
+        stream = _stream_handle()
+        self._stream = stream.value
+        self._h = C.c_void_p()
+        p = _abi.FftDdcMixedParams(K, _np_ptr(d_arr), _np_ptr(f) if K else None, _np_ptr(all_taps), _np_ptr(l_arr), int(taps_per_phase),
+                                   _np_ptr(r_arr), -1 if overlap is None else int(overlap), self.start_index, stream)
+        check(lib().gr4pm_fft_ddc_mixed_create(C.byref(p), C.byref(self._h)), "MixedFftDdc")
+        q = np.zeros(K, dtype=np.float64)
+        check(lib().gr4pm_fft_ddc_mixed_frequencies(self._h, _np_ptr(q)), "MixedFftDdc.frequencies")
+        self.frequencies = q
+        v, hop = C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_fft_ddc_mixed_sizes(self._h, C.byref(v), C.byref(hop)), "MixedFftDdc.sizes")
+        self.overlap, self.hop = v.value, hop.value
+
+    def frames_for(self, n_in):
+        """frames of each row the next process_bulk() of n_in samples delivers (numpy, int64, one per channel)"""
+        n = np.zeros(self.n_channels, dtype=np.uintp)
+        check(lib().gr4pm_fft_ddc_mixed_frames_for(self._h, int(n_in), _np_ptr(n)), "MixedFftDdc.frames_for")
+        return n.astype(np.int64)
+
+    def reset(self):
+        """back to start_index: zero prehistory, no carried samples"""
+        check(lib().gr4pm_fft_ddc_mixed_reset(self._h), "MixedFftDdc.reset")
+
+    def process_bulk(self, x, out=None, scale=None):
+        """x: a contiguous CUDA complex64 tensor of any length (all of it is consumed), or integer IQ [n, 2] as
+        FftDdc.process_bulk takes it (the same result bit for bit).  Returns (rows, lengths): rows is CUDA complex64
+        [n_channels, max(lengths)] with rows[k, :lengths[k]] the frames of channel k and +0 behind them, the layout of
+        Ddc.extract and RowResampler; lengths is numpy int64.  out: an optional CUDA complex64 [n_channels, >=
+        max(lengths)] tensor with contiguous rows and any row stride to write into."""
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        longest = int(self.frames_for(n_in).max())
+        out = _rows_output(out, self.n_channels, longest, x.device, "MixedFftDdc")
+        n = np.zeros(self.n_channels, dtype=np.uintp)
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        if fmt is None:
+            check(lib().gr4pm_fft_ddc_mixed_process(self._h, x.data_ptr(), n_in, out.data_ptr(), stride, out.shape[1], _np_ptr(n)),
+                  "MixedFftDdc.process")
+        else:
+            check(lib().gr4pm_fft_ddc_mixed_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), stride, out.shape[1],
+                                                       _np_ptr(n)), "MixedFftDdc.process_iq")
+        return out[:, :longest], n.astype(np.int64)
+
+    def __del__(self):
+        _destroy(self, "gr4pm_fft_ddc_mixed_destroy")
+
+
 def duc_taps(interpolation, taps_per_phase=12, passband=0.25, stopband=0.75):
     """gr4pm_duc_taps: the Duc's prototype low-pass, the Kaiser design of ddc_taps with taps_per_phase * interpolation
     float32 taps and DC gain `interpolation`, scaled in double before the one rounding to float32 (host only: works

@@ -16,6 +16,8 @@
 //   out, twiddles exp(+2 pi j m / 512) from a table made in double; then the kept items n' >= V / D take the rotator
 //   (the Ddc's: double sincospi of the exact phase, rounded to float, four fmaf from zero) and leave as hop / D
 //   consecutive frames of row k.
+// k_fft_ddc_mixed: the same wave (fft_ddc_channel_body(), one body for both kernels) with B, R, the kept items and the row
+//   from a per-channel descriptor, for the MixedFftDdc at the end of this file.
 // A launch pair covers at most kChunk segments, so the spectra of a call of any length stay within one 64 MiB buffer
 // that the next pair reuses in stream order.  No atomics, no scratch; every result is a function of (channel, frame,
 // stream) only, whatever the cuts into calls.
@@ -24,6 +26,7 @@
 #include "spectrum_segment.hpp"
 #include "freq_xlate.hpp"
 #include "hostlogic/fft_ddc_plan.hpp"
+#include "hostlogic/fft_ddc_mixed_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -131,24 +134,25 @@ struct ChanArgs {
     uint32_t hop;
 };
 
-// blockIdx.x: the segment of the launch, blockIdx.y: the channel; 64 threads
-__global__ __launch_bounds__(64) void k_fft_ddc_channel(ChanArgs a)
+// One wave's work for a (segment, channel), the arithmetic of both channel kernels: X the segment's spectrum, G the
+// channel's table (item t is u = t - R B / 2), w its frequency word, B = 2^logB; the items n' = first .. first + frames - 1 of the inverse
+// transform leave as o[0 .. frames - 1]; i0: the absolute index of the segment's item 0 (its low 32 bits).
+__device__ __forceinline__ void fft_ddc_channel_body(const float2* __restrict__ twg, const float2* __restrict__ X,
+                                                     const float2* __restrict__ G, const uint32_t* __restrict__ w, uint32_t logB, uint32_t R, uint32_t first,
+                                                     uint32_t D, uint32_t frames, uint32_t i0, float2* __restrict__ o)
 {
     __shared__ float2 buf[2][kMaxB];
     __shared__ float2 tw[kTwiddles];
     const uint32_t lane = threadIdx.x;
-    const uint32_t seg = blockIdx.x, k = blockIdx.y;
-    const uint32_t B = 1u << a.logB, RB = a.R << a.logB;
-    for (uint32_t m = lane; m < kTwiddles; m += 64) tw[m] = a.tw[m];
+    const uint32_t B = 1u << logB, RB = R << logB;
+    for (uint32_t m = lane; m < kTwiddles; m += 64) tw[m] = twg[m];
 
-    const uint32_t wk = a.w[k], c = fft_ddc_bin(wk);
-    const float2* __restrict__ X = a.spec + static_cast<size_t>(seg) * kN;
-    const float2* __restrict__ G = a.G + static_cast<size_t>(k) * RB;
+    const uint32_t wk = *w, c = fft_ddc_bin(wk);
     const uint32_t bin0 = c + static_cast<uint32_t>(kN) - RB / 2; // bin of the table's item 0, before the wrap
     for (uint32_t v = lane; v < B; v += 64) {
         uint32_t t = (v + RB / 2) & (B - 1); // the table's first item of the folded bin v; the others are B apart
         float2 y = {0.0f, 0.0f};
-        for (uint32_t r = 0; r < a.R; ++r, t += B) {
+        for (uint32_t r = 0; r < R; ++r, t += B) {
             const float2 x = X[(bin0 + t) & (kN - 1)], g = G[t];
             const float2 z = {x.x * g.x - x.y * g.y, x.x * g.y + x.y * g.x};
             if (r == 0)
@@ -163,31 +167,82 @@ __global__ __launch_bounds__(64) void k_fft_ddc_channel(ChanArgs a)
     // stage of sub-transform length Ns: butterfly j takes items j and j + B / 2, position q = j mod Ns of its sub-transform,
     // and writes items (j - q) 2 + q and Ns later.  Natural order in, natural order out
     uint32_t src = 0;
-    for (uint32_t ls = 0; ls < a.logB; ++ls) {
+    for (uint32_t ls = 0; ls < logB; ++ls) {
         const uint32_t Ns = 1u << ls;
         for (uint32_t j = lane; j < B / 2; j += 64) {
             const uint32_t q = j & (Ns - 1);
             const float2 t = tw[q << (8 - ls)]; // exp(+2 pi j q / (2 Ns))
             const float2 p = buf[src][j], b = buf[src][j + B / 2];
             const float2 e = {b.x * t.x - b.y * t.y, b.x * t.y + b.y * t.x};
-            const uint32_t o = ((j - q) << 1) + q;
-            buf[src ^ 1][o] = float2{p.x + e.x, p.y + e.y};
-            buf[src ^ 1][o + Ns] = float2{p.x - e.x, p.y - e.y};
+            const uint32_t o2 = ((j - q) << 1) + q;
+            buf[src ^ 1][o2] = float2{p.x + e.x, p.y + e.y};
+            buf[src ^ 1][o2 + Ns] = float2{p.x - e.x, p.y - e.y};
         }
         src ^= 1;
         __syncthreads();
     }
 
-    const uint32_t frames = B - a.first;
-    const uint32_t i0 = static_cast<uint32_t>(a.index0) + seg * a.hop;
-    float2* __restrict__ o = a.out + static_cast<size_t>(k) * a.out_stride + a.frame0 + static_cast<size_t>(seg) * frames;
     for (uint32_t f = lane; f < frames; f += 64) {
-        const uint32_t p = (a.first + f) * a.D;
+        const uint32_t p = (first + f) * D;
         const uint32_t phi = fft_ddc_phi(wk, c, i0 + p, p);
         float2 y = {0.0f, 0.0f};
-        cmac(y, mixer<-1>(phi, 1u), buf[src][a.first + f]);
+        cmac(y, mixer<-1>(phi, 1u), buf[src][first + f]);
         o[f] = y;
     }
+}
+
+// blockIdx.x: the segment of the launch, blockIdx.y: the channel; 64 threads
+__global__ __launch_bounds__(64) void k_fft_ddc_channel(ChanArgs a)
+{
+    const uint32_t seg = blockIdx.x, k = blockIdx.y;
+    const uint32_t B = 1u << a.logB, RB = a.R << a.logB;
+    const uint32_t frames = B - a.first;
+    fft_ddc_channel_body(a.tw, a.spec + static_cast<size_t>(seg) * kN, a.G + static_cast<size_t>(k) * RB, a.w + k, a.logB, a.R, a.first, a.D,
+                         frames, static_cast<uint32_t>(a.index0) + seg * a.hop,
+                         a.out + static_cast<size_t>(k) * a.out_stride + a.frame0 + static_cast<size_t>(seg) * frames);
+}
+
+// What the MixedFftDdc's kernel takes per channel in the place of launch-wide constants.  The table is ordered by
+// descending B, so the workgroups with the longest inverse transforms are dispatched first.
+struct MixedDesc {
+    uint32_t w;      // the frequency word
+    uint32_t logB;   // log2 B_k
+    uint32_t R;      // images
+    uint32_t first;  // the first n' that is kept
+    uint32_t D;      // D_k
+    uint32_t frames; // hop / D_k
+    uint32_t table;  // the channel's first item of G
+    uint32_t row;    // the output row
+};
+
+struct MixedArgs {
+    const float2* spec;    // [segments of the launch][2048]
+    const float2* G;       // the channels' tables behind one another, R_k B_k items each
+    const float2* tw;      // [256]
+    const MixedDesc* desc; // [K]
+    float2* out;
+    size_t out_stride;
+    size_t seg0;           // the launch's first segment, counted from the call's
+    size_t call_segments;  // segments of the call
+    uint64_t index0;       // absolute index of item 0 of the launch's first segment
+    uint32_t hop;
+    uint32_t max_frames;   // hop / min D_k: frames of a segment on the longest row
+};
+
+// blockIdx.x: the segment of the launch, blockIdx.y: the descriptor; 64 threads.  Row k takes the call's frames_k frames
+// per segment from the front; behind the call's last frame the workgroup of the call's segment s writes the zeros
+// [s (max_frames - frames_k), (s + 1) (max_frames - frames_k)), so all rows end at call_segments max_frames
+__global__ __launch_bounds__(64) void k_fft_ddc_mixed(MixedArgs a)
+{
+    const uint32_t seg = blockIdx.x;
+    const MixedDesc d = a.desc[blockIdx.y];
+    const size_t s = a.seg0 + seg;
+    float2* __restrict__ row = a.out + static_cast<size_t>(d.row) * a.out_stride;
+    fft_ddc_channel_body(a.tw, a.spec + static_cast<size_t>(seg) * kN, a.G + d.table, &a.desc[blockIdx.y].w, d.logB, d.R, d.first, d.D, d.frames,
+                         static_cast<uint32_t>(a.index0) + seg * a.hop, row + s * d.frames);
+    const uint32_t pad = a.max_frames - d.frames;
+    float2* __restrict__ z = row + a.call_segments * d.frames + s * pad;
+    for (uint32_t f = threadIdx.x; f < pad; f += 64) z[f] = float2{0.0f, 0.0f};
 }
 
 // G_k[u] = (1 / N) sum_t h[t] exp(-2 pi j psi t / 2^32), psi = ((c_k + u) 2^21 - w_k) mod 2^32: the phase of every term an
@@ -214,20 +269,93 @@ gr4pm_status check_decimation(size_t D)
     return GR4PM_OK;
 }
 
-} // namespace
-
-struct gr4pm_fft_ddc {
-    size_t K = 0, D = 0, R = 0, V = 0;
+// What both handles hold for the stream and the shared forward transform, and what their calls do alike.
+struct FftDdcCore {
     uint64_t start_index = 0;
     uint64_t taken = 0; // samples since create or reset
     FftDdcShape shape = {};
     hipStream_t stream = nullptr;
     size_t max_waves = 2048; // of one forward launch: eight per compute unit, at most 2048
-    std::vector<uint32_t> words;
     gr4pm::StreamTail tail; // keep = 0, frame = N: the virtual items of the incomplete segment
     gr4pm::DevBuf<float4> d_tT;
     gr4pm::DevBuf<cf> d_cc, d_spec;
-    gr4pm::DevBuf<float2> d_G, d_tw;
+    gr4pm::DevBuf<float2> d_tw;
+
+    // the segment grid of (D, V), the forward transform's tables, the inverse transforms' twiddles, the spectra and the tail
+    gr4pm_status init(size_t D, size_t V, uint64_t start, void* on_stream)
+    {
+        start_index = start;
+        shape = fft_ddc_shape(static_cast<uint32_t>(D), static_cast<uint32_t>(V));
+        stream = static_cast<hipStream_t>(on_stream);
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+            max_waves = std::min(max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
+        std::vector<float4> tT(kW64TwFloat4);
+        std::vector<cf> cc(64);
+        build_w64_tables(
+            [](int k) {
+                const double ang = -2.0 * M_PI * k / kFftN;
+                return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
+            },
+            tT.data(), cc.data());
+        std::vector<float2> tw(kTwiddles);
+        for (int m = 0; m < kTwiddles; ++m) {
+            double cs, sn;
+            unit_phasor(static_cast<uint32_t>(m) << 23, cs, sn); // m / 512 of a turn
+            tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
+        }
+        GR4PM_TRY(d_tT.alloc(tT.size()));
+        GR4PM_TRY(d_cc.alloc(cc.size()));
+        GR4PM_TRY(d_tw.alloc(tw.size()));
+        GR4PM_TRY(d_spec.alloc(kChunk * kN));
+        GR4PM_TRY(d_tT.upload(tT.data(), tT.size(), stream));
+        GR4PM_TRY(d_cc.upload(cc.data(), cc.size(), stream));
+        GR4PM_TRY(d_tw.upload(tw.data(), tw.size(), stream));
+        GR4PM_HIP_TRY(hipStreamSynchronize(stream)); // the uploads read this function's vectors
+        return tail.alloc(0, kN, 1, stream);
+    }
+
+    // A call that was validated: per launch pair the forward kernel, then channels(done, segs), which launches the
+    // handle's channel kernel for the segments [done, done + segs) of the call; then the tail.  format iq::kC64 for
+    // complex64 samples
+    template <class Channels>
+    gr4pm_status run(const FftDdcPlan& p, const void* in, int format, float scale, size_t n_in, Channels&& channels)
+    {
+        // the samples in front of the virtual stream (V = 0 only) belong to no frame
+        const size_t item = format == iq::kC64 ? sizeof(float2) : iq::item_bytes(format);
+        const void* x = static_cast<const char*>(in) + p.drop * item;
+        const StreamTail::Plan t = {tail.d_hist[tail.cur].p, tail.d_hist[1 - tail.cur].p, p.tail, p.n_segments, p.tail_new, p.tail_new};
+        FwdArgs a = {};
+        a.hist = t.hist, a.in = x, a.H = p.tail;
+        a.tT = d_tT.p, a.cc = d_cc.p, a.spec = d_spec.p;
+        a.hop = shape.hop, a.scale = scale;
+        iq::with_format(format, [&](auto f) {
+            for (size_t done = 0; done < p.n_segments;) {
+                const size_t segs = std::min(p.n_segments - done, kChunk);
+                const size_t per_wave = (segs + max_waves - 1) / max_waves;
+                const size_t waves = (segs + per_wave - 1) / per_wave;
+                a.seg0 = done, a.n_seg = static_cast<uint32_t>(segs), a.run = static_cast<uint32_t>(per_wave);
+                hipLaunchKernelGGL(k_fft_ddc_forward<decltype(f)::value>, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)),
+                                   dim3(kW64Threads), 0, stream, a);
+                channels(done, segs);
+                done += segs;
+            }
+            tail.launch_history<decltype(f)::value>(t, x, 0, p.n_used, scale, stream);
+        });
+        GR4PM_HIP_TRY(hipGetLastError());
+        tail.commit(t);
+        taken += n_in;
+        return GR4PM_OK;
+    }
+};
+
+} // namespace
+
+struct gr4pm_fft_ddc : FftDdcCore {
+    size_t K = 0, D = 0, R = 0, V = 0;
+    std::vector<uint32_t> words;
+    gr4pm::DevBuf<float2> d_G;
     gr4pm::DevBuf<uint32_t> d_w;
 };
 
@@ -255,41 +383,18 @@ static gr4pm_status process_any(gr4pm_fft_ddc* h, const void* in, int format, fl
         set_error("fft_ddc: no output array, or a row stride of %zu items for %zu frames", out_stride, p.frames);
         return GR4PM_ERR_INVALID;
     }
-    // the samples in front of the virtual stream (V = 0 only) belong to no frame
-    const size_t item = format == iq::kC64 ? sizeof(float2) : iq::item_bytes(format);
-    const void* x = static_cast<const char*>(in) + p.drop * item;
-    const StreamTail::Plan t = {h->tail.d_hist[h->tail.cur].p, h->tail.d_hist[1 - h->tail.cur].p, p.tail, p.n_segments,
-                                p.tail_new, p.tail_new};
-    FwdArgs a = {};
-    a.hist = t.hist, a.in = x, a.H = p.tail;
-    a.tT = h->d_tT.p, a.cc = h->d_cc.p, a.spec = h->d_spec.p;
-    a.hop = h->shape.hop, a.scale = scale;
     ChanArgs b = {};
     b.spec = reinterpret_cast<const float2*>(h->d_spec.p), b.G = h->d_G.p, b.tw = h->d_tw.p, b.w = h->d_w.p;
     b.out = reinterpret_cast<float2*>(out), b.out_stride = out_stride;
     b.D = static_cast<uint32_t>(h->D), b.R = static_cast<uint32_t>(h->R);
     b.logB = static_cast<uint32_t>(__builtin_ctzll(kN / h->D));
     b.first = h->shape.first, b.hop = h->shape.hop;
-    iq::with_format(format, [&](auto f) {
-        for (size_t done = 0; done < p.n_segments;) {
-            const size_t segs = std::min(p.n_segments - done, kChunk);
-            const size_t run = (segs + h->max_waves - 1) / h->max_waves;
-            const size_t waves = (segs + run - 1) / run;
-            a.seg0 = done, a.n_seg = static_cast<uint32_t>(segs), a.run = static_cast<uint32_t>(run);
-            hipLaunchKernelGGL(k_fft_ddc_forward<decltype(f)::value>, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)),
-                               dim3(kW64Threads), 0, h->stream, a);
-            b.n_seg = a.n_seg;
-            b.frame0 = done * h->shape.frames;
-            b.index0 = fft_ddc_segment_index(h->shape, h->start_index, p.segments_before + done);
-            hipLaunchKernelGGL(k_fft_ddc_channel, dim3(static_cast<unsigned>(segs), static_cast<unsigned>(h->K)), dim3(64), 0,
-                               h->stream, b);
-            done += segs;
-        }
-        h->tail.launch_history<decltype(f)::value>(t, x, 0, p.n_used, scale, h->stream);
-    });
-    GR4PM_HIP_TRY(hipGetLastError());
-    h->tail.commit(t);
-    h->taken += n_in;
+    GR4PM_TRY(h->run(p, in, format, scale, n_in, [&](size_t done, size_t segs) {
+        b.n_seg = static_cast<uint32_t>(segs);
+        b.frame0 = done * h->shape.frames;
+        b.index0 = fft_ddc_segment_index(h->shape, h->start_index, p.segments_before + done);
+        hipLaunchKernelGGL(k_fft_ddc_channel, dim3(static_cast<unsigned>(segs), static_cast<unsigned>(h->K)), dim3(64), 0, h->stream, b);
+    }));
     *n_frames = p.frames;
     return GR4PM_OK;
 }
@@ -352,47 +457,18 @@ try {
     std::unique_ptr<gr4pm_fft_ddc> h(new (std::nothrow) gr4pm_fft_ddc);
     if (!h) return GR4PM_ERR_NOMEM;
     h->K = K, h->D = D, h->R = R, h->V = V;
-    h->start_index = p->start_index;
-    h->shape = fft_ddc_shape(static_cast<uint32_t>(D), static_cast<uint32_t>(V));
-    h->stream = static_cast<hipStream_t>(p->stream);
     h->words = std::move(words);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        h->max_waves = std::min(h->max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
-
-    std::vector<float4> tT(kW64TwFloat4);
-    std::vector<cf> cc(64);
-    build_w64_tables(
-        [](int k) {
-            const double ang = -2.0 * M_PI * k / kFftN;
-            return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
-        },
-        tT.data(), cc.data());
-    std::vector<float2> tw(kTwiddles);
-    for (int m = 0; m < kTwiddles; ++m) {
-        double cs, sn;
-        unit_phasor(static_cast<uint32_t>(m) << 23, cs, sn); // m / 512 of a turn
-        tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
-    }
+    GR4PM_TRY(h->init(D, V, p->start_index, p->stream));
     const size_t B = kN / D, RB = R * B;
     std::vector<float2> G(K * RB);
     for (size_t k = 0; k < K; ++k) {
         const uint32_t w = h->words[k], c = fft_ddc_bin(w);
         for (size_t t = 0; t < RB; ++t) G[k * RB + t] = response(taps, w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
     }
-    GR4PM_TRY(h->d_tT.alloc(tT.size()));
-    GR4PM_TRY(h->d_cc.alloc(cc.size()));
-    GR4PM_TRY(h->d_tw.alloc(tw.size()));
     GR4PM_TRY(h->d_G.alloc(G.size()));
     GR4PM_TRY(h->d_w.alloc(K));
-    GR4PM_TRY(h->d_spec.alloc(kChunk * kN));
-    GR4PM_TRY(h->d_tT.upload(tT.data(), tT.size(), h->stream));
-    GR4PM_TRY(h->d_cc.upload(cc.data(), cc.size(), h->stream));
-    GR4PM_TRY(h->d_tw.upload(tw.data(), tw.size(), h->stream));
     GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
     GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
-    GR4PM_TRY(h->tail.alloc(0, kN, 1, h->stream));
     return finish_create(h, out, "fft_ddc");
 }
 GR4PM_ABI_CATCH
@@ -461,6 +537,253 @@ try {
     }
     return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
                        n_frames);
+}
+GR4PM_ABI_CATCH
+
+} // extern "C"
+
+// ---- MixedFftDdc: a decimation per channel from the same shared transform ------------------------
+// The segment grid is the FftDdc's at Dmax (fft_ddc_shape(Dmax, V), fft_ddc_plan() unchanged), the forward kernel is used
+// as it is, and k_fft_ddc_mixed runs fft_ddc_channel_body() with each channel's own B_k, R_k, first_k and frames_k.
+
+namespace {
+
+using gr4pm::hostlogic::fft_ddc_mixed_channel;
+using gr4pm::hostlogic::fft_ddc_mixed_default_overlap;
+using gr4pm::hostlogic::fft_ddc_mixed_frames;
+using gr4pm::hostlogic::fft_ddc_mixed_max_decimation;
+using gr4pm::hostlogic::fft_ddc_mixed_table_offsets;
+using gr4pm::hostlogic::fft_ddc_mixed_validate;
+using gr4pm::hostlogic::fft_ddc_mixed_validate_channels;
+using gr4pm::hostlogic::FftDdcMixedChannel;
+using gr4pm::hostlogic::FftDdcMixedRefusal;
+using gr4pm::hostlogic::FftDdcMixedVerdict;
+
+} // namespace
+
+struct gr4pm_fft_ddc_mixed : FftDdcCore { // the core's shape is that of (Dmax, V)
+    size_t K = 0, Dmax = 0, V = 0;
+    uint32_t max_frames = 0; // hop / min D_k
+    std::vector<uint32_t> words;
+    std::vector<FftDdcMixedChannel> channels;
+    gr4pm::DevBuf<float2> d_G;
+    gr4pm::DevBuf<MixedDesc> d_desc;
+};
+
+// frames per row of a call: counts[k]
+static void mixed_frames(const gr4pm_fft_ddc_mixed* h, const FftDdcPlan& p, size_t* counts)
+{
+    for (size_t k = 0; k < h->K; ++k) counts[k] = fft_ddc_mixed_frames(p, h->channels[k]);
+}
+
+static gr4pm_status mixed_process_any(gr4pm_fft_ddc_mixed* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                      size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+{
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    std::fill(n_frames, n_frames + h->K, size_t(0));
+    if (n_in > (size_t(1) << 40)) {
+        set_error("fft_ddc_mixed: %zu samples in one call, at most 2^40", n_in);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (n_in == 0) return GR4PM_OK;
+    if (!in) {
+        set_error("fft_ddc_mixed: no input array");
+        return GR4PM_ERR_INVALID;
+    }
+    const FftDdcPlan p = fft_ddc_plan(h->shape, h->taken, n_in);
+    const size_t longest = p.n_segments * h->max_frames;
+    if (longest > out_cap_frames) {
+        set_error("fft_ddc_mixed: %zu frames on the longest row, room for %zu", longest, out_cap_frames);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (longest && (!out || (h->K > 1 && out_stride < longest))) {
+        set_error("fft_ddc_mixed: no output array, or a row stride of %zu items for %zu frames", out_stride, longest);
+        return GR4PM_ERR_INVALID;
+    }
+    MixedArgs b = {};
+    b.spec = reinterpret_cast<const float2*>(h->d_spec.p), b.G = h->d_G.p, b.tw = h->d_tw.p, b.desc = h->d_desc.p;
+    b.out = reinterpret_cast<float2*>(out), b.out_stride = out_stride;
+    b.call_segments = p.n_segments, b.hop = h->shape.hop, b.max_frames = h->max_frames;
+    GR4PM_TRY(h->run(p, in, format, scale, n_in, [&](size_t done, size_t segs) {
+        b.seg0 = done;
+        b.index0 = fft_ddc_segment_index(h->shape, h->start_index, p.segments_before + done);
+        hipLaunchKernelGGL(k_fft_ddc_mixed, dim3(static_cast<unsigned>(segs), static_cast<unsigned>(h->K)), dim3(64), 0, h->stream, b);
+    }));
+    mixed_frames(h, p, n_frames);
+    return GR4PM_OK;
+}
+
+extern "C" {
+
+gr4pm_status gr4pm_fft_ddc_mixed_create(const gr4pm_fft_ddc_mixed_params* p, gr4pm_fft_ddc_mixed** out)
+try {
+    if (!p || !out) return GR4PM_ERR_INVALID;
+    *out = nullptr;
+    const size_t K = p->n_channels;
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("fft_ddc_mixed", p->frequencies, K, kFftDdcMaxK, words));
+    if (!p->decimations) {
+        set_error("fft_ddc_mixed: no decimations");
+        return GR4PM_ERR_INVALID;
+    }
+    if ((p->taps == nullptr) != (p->n_taps == nullptr)) {
+        set_error("fft_ddc_mixed: taps and n_taps come together or not at all");
+        return GR4PM_ERR_INVALID;
+    }
+    const std::vector<size_t> D(p->decimations, p->decimations + K);
+    const std::vector<size_t> R = p->images ? std::vector<size_t>(p->images, p->images + K) : std::vector<size_t>(K, 2);
+    std::vector<size_t> L(K);
+    for (size_t k = 0; k < K; ++k) {
+        if (!fft_ddc_pow2(D[k]) || D[k] < kFftDdcMinD || D[k] > kFftDdcMaxD) {
+            set_error("fft_ddc_mixed: decimations[%zu] must be a power of two in [%u, %u], not %zu", k, kFftDdcMinD, kFftDdcMaxD, D[k]);
+            return GR4PM_ERR_INVALID;
+        }
+        if (p->taps) {
+            GR4PM_TRY(prototype_length("fft_ddc_mixed", p->taps, p->n_taps[k], kN));
+            L[k] = p->n_taps[k];
+        } else {
+            if (p->taps_per_phase < 1 || p->taps_per_phase * D[k] > kN) {
+                set_error("fft_ddc_mixed: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", p->taps_per_phase, D[k], kN);
+                return GR4PM_ERR_INVALID;
+            }
+            L[k] = p->taps_per_phase * D[k];
+        }
+    }
+    const FftDdcMixedVerdict sizes = fft_ddc_mixed_validate_channels(K, D.data(), R.data(), L.data());
+    if (sizes.refusal == FftDdcMixedRefusal::images) {
+        set_error("fft_ddc_mixed: images[%zu] must be a power of two in [1, %zu], not %zu", sizes.channel, D[sizes.channel], R[sizes.channel]);
+        return GR4PM_ERR_INVALID;
+    }
+    if (sizes.refusal != FftDdcMixedRefusal::none) {
+        set_error("fft_ddc_mixed: invalid sizes of channel %zu", sizes.channel);
+        return GR4PM_ERR_INVALID;
+    }
+    std::vector<std::vector<float>> taps(K);
+    for (size_t k = 0, at = 0; k < K; at += L[k], ++k) {
+        if (p->taps) {
+            taps[k].assign(p->taps + at, p->taps + at + L[k]);
+        } else {
+            taps[k].resize(L[k]);
+            GR4PM_TRY(gr4pm_ddc_taps(D[k], p->taps_per_phase, 0.25, 0.75, taps[k].data()));
+        }
+        for (size_t t = 0; t < L[k]; ++t)
+            if (!std::isfinite(taps[k][t])) {
+                set_error("fft_ddc_mixed: taps[%zu] of channel %zu is not finite", t, k);
+                return GR4PM_ERR_INVALID;
+            }
+    }
+    const size_t Dmax = fft_ddc_mixed_max_decimation(K, D.data());
+    const size_t V = p->overlap < 0 ? fft_ddc_mixed_default_overlap(K, D.data(), L.data()) : static_cast<size_t>(p->overlap);
+    const FftDdcMixedVerdict v = fft_ddc_mixed_validate(K, D.data(), R.data(), L.data(), V);
+    switch (v.refusal) {
+    case FftDdcMixedRefusal::none: break;
+    case FftDdcMixedRefusal::overlap_multiple:
+        set_error("fft_ddc_mixed: the overlap %zu is no multiple of the largest decimation %zu", V, Dmax);
+        return GR4PM_ERR_INVALID;
+    case FftDdcMixedRefusal::overlap_low:
+        set_error("fft_ddc_mixed: the overlap %zu is below the reach of channel %zu: %zu taps at a decimation of %zu beside %zu need %zu", V,
+                  v.channel, L[v.channel], D[v.channel], Dmax, Dmax - D[v.channel] + L[v.channel] - 1);
+        return GR4PM_ERR_INVALID;
+    case FftDdcMixedRefusal::overlap_high:
+        set_error("fft_ddc_mixed: the overlap %zu leaves a hop below %u: at most %zu", V, kFftDdcMinHop, kN - kFftDdcMinHop);
+        return GR4PM_ERR_INVALID;
+    default: set_error("fft_ddc_mixed: invalid sizes"); return GR4PM_ERR_INVALID;
+    }
+    GR4PM_TRY(require_device());
+    std::unique_ptr<gr4pm_fft_ddc_mixed> h(new (std::nothrow) gr4pm_fft_ddc_mixed);
+    if (!h) return GR4PM_ERR_NOMEM;
+    h->K = K, h->Dmax = Dmax, h->V = V;
+    h->words = std::move(words);
+    GR4PM_TRY(h->init(Dmax, V, p->start_index, p->stream));
+    std::vector<size_t> offsets(K);
+    std::vector<float2> G(fft_ddc_mixed_table_offsets(K, D.data(), R.data(), offsets.data()));
+    std::vector<MixedDesc> desc(K);
+    h->channels.resize(K);
+    for (size_t k = 0; k < K; ++k) {
+        const uint32_t w = h->words[k], c = fft_ddc_bin(w);
+        const size_t RB = R[k] * (kN / D[k]);
+        for (size_t t = 0; t < RB; ++t)
+            G[offsets[k] + t] = response(taps[k], w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
+        h->channels[k] = fft_ddc_mixed_channel(static_cast<uint32_t>(Dmax), static_cast<uint32_t>(V), static_cast<uint32_t>(D[k]));
+        h->max_frames = std::max(h->max_frames, h->channels[k].frames);
+        desc[k] = MixedDesc{w, static_cast<uint32_t>(__builtin_ctzll(kN / D[k])), static_cast<uint32_t>(R[k]), h->channels[k].first,
+                            static_cast<uint32_t>(D[k]), h->channels[k].frames, static_cast<uint32_t>(offsets[k]), static_cast<uint32_t>(k)};
+    }
+    // the longest inverse transforms first: a workgroup at B = 512 costs many times one at B = 32
+    std::stable_sort(desc.begin(), desc.end(), [](const MixedDesc& x, const MixedDesc& y) { return x.logB > y.logB; });
+    GR4PM_TRY(h->d_G.alloc(G.size()));
+    GR4PM_TRY(h->d_desc.alloc(K));
+    GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
+    GR4PM_TRY(h->d_desc.upload(desc.data(), K, h->stream));
+    return finish_create(h, out, "fft_ddc_mixed");
+}
+GR4PM_ABI_CATCH
+
+void gr4pm_fft_ddc_mixed_destroy(gr4pm_fft_ddc_mixed* h)
+try {
+    if (!h) return;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+GR4PM_ABI_CATCH_VOID
+
+gr4pm_status gr4pm_fft_ddc_mixed_reset(gr4pm_fft_ddc_mixed* h)
+try {
+    if (!h) return GR4PM_ERR_INVALID;
+    GR4PM_TRY(h->tail.reset(h->stream));
+    h->taken = 0;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_ddc_mixed_frames_for(const gr4pm_fft_ddc_mixed* h, size_t n_in, size_t* n_frames)
+try {
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    std::fill(n_frames, n_frames + h->K, size_t(0));
+    if (n_in > (size_t(1) << 40)) {
+        set_error("fft_ddc_mixed: %zu samples in one call, at most 2^40", n_in);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    mixed_frames(h, fft_ddc_plan(h->shape, h->taken, n_in), n_frames);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_ddc_mixed_frequencies(const gr4pm_fft_ddc_mixed* h, double* out)
+try {
+    if (!h || !out) return GR4PM_ERR_INVALID;
+    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_ddc_mixed_sizes(const gr4pm_fft_ddc_mixed* h, size_t* overlap, size_t* hop)
+try {
+    if (!h || !overlap || !hop) return GR4PM_ERR_INVALID;
+    *overlap = h->V;
+    *hop = h->shape.hop;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_ddc_mixed_process(gr4pm_fft_ddc_mixed* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                                         size_t out_cap_frames, size_t* n_frames)
+try {
+    return mixed_process_any(h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_ddc_mixed_process_iq(gr4pm_fft_ddc_mixed* h, const void* in, int format, float scale, size_t n_in,
+                                            gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames)
+try {
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    std::fill(n_frames, n_frames + h->K, size_t(0));
+    if (!iq::valid(format)) {
+        set_error("fft_ddc_mixed: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
+        return GR4PM_ERR_INVALID;
+    }
+    return mixed_process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
+                             n_frames);
 }
 GR4PM_ABI_CATCH
 

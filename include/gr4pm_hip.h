@@ -1686,6 +1686,61 @@ gr4pm_status gr4pm_fft_ddc_process(gr4pm_fft_ddc* h, const gr4pm_c64* in, size_t
 gr4pm_status gr4pm_fft_ddc_process_iq(gr4pm_fft_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
                                       size_t out_stride, size_t out_cap_frames, size_t* n_frames);
 
+/* ---- MixedFftDdc: a decimation per channel from one shared transform (the project's own block) --
+ * The FftDdc with its restriction to one decimation lifted: carriers of different symbol rates in one pass over the
+ * stream.  N = 2048, K channels (1 .. 64); channel k has a frequency f_k, D_k a power of two in 4 .. 64, B_k = N / D_k, a
+ * real finite prototype h_k[0 .. L_k - 1] and R_k images, a power of two with 1 <= R_k <= D_k.  Dmax = max D_k.  One
+ * overlap V for the handle with Dmax | V, V <= N - 64 and V - (Dmax - D_k) >= L_k - 1 for every k (overlap < 0: the
+ * smallest multiple of 256 that is >= max_k (Dmax - D_k + L_k - 1)), hop = N - V.  All channels share one segment
+ * grid, anchored on Dmax:
+ *     segment s: the N items from a_s = s hop - V + Dmax - 1 on (x = 0 before start_index),  X_s = FFT_N(x_s)
+ *     w_k, c_k, G_k[u], Z[u], Y[v], y'[n']: the FftDdc's with h_k, B_k, R_k in the place of h, B, R
+ *     first_k = (V - Dmax) / D_k + 1,   n' = first_k .. first_k + hop / D_k - 1 are kept
+ *     p = n' D_k,   i = start_index + a_s + p,   phi = (w_k i - c_k 2^21 p) mod 2^32
+ *     out_k[s hop / D_k + n' - first_k] = exp(-2 pi j phi / 2^32) y'[n']
+ * Frame n of row k lies at i = start_index + n D_k + D_k - 1, the Ddc's frame grid at D_k, so row k is
+ * Ddc([f_k], D_k, taps = h_k) from frame 0 on, up to the truncation to R_k images (the FftDdc's bound).  With all D_k
+ * equal the block is the FftDdc, bit for bit.  A call delivers whole segments, hop / D_k frames of row k each; the handle
+ * carries V samples plus the incomplete hop, and any cutting of the stream into calls gives the same bits. */
+typedef struct gr4pm_fft_ddc_mixed gr4pm_fft_ddc_mixed;
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    const size_t* decimations;  /* HOST, K items: D_k, powers of two, 4 .. 64 */
+    const double* frequencies;  /* HOST, K items, cycles per input sample, finite */
+    const float* taps;          /* HOST, the K prototypes behind one another, finite; NULL together with n_taps:
+                                   gr4pm_fft_ddc_taps(D_k, taps_per_phase) per channel */
+    const size_t* n_taps;       /* HOST, K items: L_k */
+    size_t taps_per_phase;      /* of the design when taps is NULL */
+    const size_t* images;       /* HOST, K items: R_k; NULL: 2 each */
+    int64_t overlap;            /* V; negative: the default */
+    uint64_t start_index;
+    void* stream;               /* hipStream_t */
+} gr4pm_fft_ddc_mixed_params;
+/* Refused with GR4PM_ERR_INVALID and no handle: K out of range, a NULL or non-finite frequency, no decimations, taps
+ * without n_taps or the reverse, a D_k or R_k no power of two or out of range, a non-finite tap, an L_k out of range, V
+ * no multiple of Dmax, above N - 64, or below Dmax - D_k + L_k - 1 for a channel k. */
+gr4pm_status gr4pm_fft_ddc_mixed_create(const gr4pm_fft_ddc_mixed_params* params, gr4pm_fft_ddc_mixed** out);
+void gr4pm_fft_ddc_mixed_destroy(gr4pm_fft_ddc_mixed* h);
+/* back to start_index: zero prehistory, nothing carried */
+gr4pm_status gr4pm_fft_ddc_mixed_reset(gr4pm_fft_ddc_mixed* h);
+/* n_frames: HOST, K items: the frames of each row the next call of n_in samples delivers */
+gr4pm_status gr4pm_fft_ddc_mixed_frames_for(const gr4pm_fft_ddc_mixed* h, size_t n_in, size_t* n_frames);
+/* out: HOST, K items: w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_fft_ddc_mixed_frequencies(const gr4pm_fft_ddc_mixed* h, double* out);
+gr4pm_status gr4pm_fft_ddc_mixed_sizes(const gr4pm_fft_ddc_mixed* h, size_t* overlap, size_t* hop);
+/* in: DEVICE, n_in samples.  out: DEVICE, K rows out_stride items apart with room for out_cap_frames each.  n_frames:
+ * HOST, K items.  Row k receives n_frames[k] frames and behind them +0 up to max_k n_frames[k], written by the same
+ * kernel: rows go to a receiver zero-padded.  Enqueues on the handle's stream and does not wait.  Refused with
+ * gr4pm_last_error set, every n_frames[k] = 0 and nothing enqueued: a NULL in with n_in > 0, a NULL out or out_stride
+ * below the longest row with K > 1 when the call delivers frames (GR4PM_ERR_INVALID); n_in > 2^40 or less room than the
+ * longest row (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
+gr4pm_status gr4pm_fft_ddc_mixed_process(gr4pm_fft_ddc_mixed* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                                         size_t out_cap_frames, size_t* n_frames);
+/* The same for integer IQ (GR4PM_IQ_SC16 / SC8 / CU8; scale 0: the format's default): gr4pm_fft_ddc_mixed_process on
+ * gr4pm_iq_unpack(in) bit for bit; calls of any format mix on one handle. */
+gr4pm_status gr4pm_fft_ddc_mixed_process_iq(gr4pm_fft_ddc_mixed* h, const void* in, int format, float scale, size_t n_in,
+                                            gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames);
+
 #ifdef __cplusplus
 }
 #endif

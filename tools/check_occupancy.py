@@ -132,6 +132,9 @@ BUDGETS = [
     # registers as built)
     (r"k_fft_ddc_forwardILi", dict(vgpr=184, lds=151552, lds_exact=True, scratch=0)),
     (r"k_fft_ddc_channel", dict(vgpr=48, lds=10240, lds_exact=True, scratch=0)),
+    # the MixedFftDdc block: the same wave with its sizes from a per-channel descriptor (47 registers as built) and the same
+    # LDS image, sized for B = 512 whatever a channel's B
+    (r"k_fft_ddc_mixed", dict(vgpr=48, lds=10240, lds_exact=True, scratch=0)),
     # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
     # section 21)
     (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
