@@ -330,7 +330,8 @@ EXPORTS = [
     "gr4pm_additive_scrambler_process",
     "gr4pm_header_payload_split_create", "gr4pm_header_payload_split_destroy",
     "gr4pm_header_payload_split_reset", "gr4pm_header_payload_split_process", "gr4pm_header_payload_split_process_c64",
-    "gr4pm_header_fec_decoder_create", "gr4pm_header_fec_decoder_destroy", "gr4pm_header_fec_decoder_process",
+    "gr4pm_header_fec_decoder_create", "gr4pm_header_fec_decoder_destroy", "gr4pm_header_fec_decoder_dims",
+    "gr4pm_header_fec_decoder_process",
     "gr4pm_header_parse",
     "gr4pm_binary_slicer_process", "gr4pm_pack_bits_process", "gr4pm_slice_pack_process",
     "gr4pm_crc_check_create", "gr4pm_crc_check_destroy", "gr4pm_crc_check_compute", "gr4pm_crc_check_process",
@@ -495,6 +496,7 @@ def lib():
     L.gr4pm_header_fec_decoder_create.argtypes = [C.POINTER(HeaderFecDecoderParams), C.POINTER(vp)]
     L.gr4pm_header_fec_decoder_destroy.argtypes = [vp]
     L.gr4pm_header_fec_decoder_destroy.restype = None
+    L.gr4pm_header_fec_decoder_dims.argtypes = [vp, szp, szp]
     L.gr4pm_header_fec_decoder_process.argtypes = [vp, vp, sz, vp, vp]
     L.gr4pm_header_parse.argtypes = [vp, vp, sz, vp, vp]
     L.gr4pm_header_parse.restype = None

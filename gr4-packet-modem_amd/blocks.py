@@ -664,7 +664,8 @@ def header_ldpc_alist():
 
 
 class HeaderFecDecoder:
-    """header_fec_decoder.hpp:13-359: 256 LLRs -> 4 header bytes, or invalid"""
+    """header_fec_decoder.hpp:13-359: 256 LLRs -> 4 header bytes, or invalid.  With another `alist` (an (n, m) code the
+    decoder accepts, include/gr4pm_hip.h): llrs_per_codeword = 2 n LLRs -> header_bytes = (n - m) / 8 bytes"""
 
     def __init__(self, alist=None, max_iterations=25, arithmetic=0):
         """arithmetic: 0 float32 messages (default), 1 8-bit messages (include/gr4pm_hip.h)"""
@@ -672,14 +673,18 @@ class HeaderFecDecoder:
         p = _abi.HeaderFecDecoderParams(self._alist, max_iterations, _stream_handle(), arithmetic)
         self._h = C.c_void_p()
         check(lib().gr4pm_header_fec_decoder_create(C.byref(p), C.byref(self._h)), "HeaderFecDecoder.start")
+        n_llrs, n_bytes = C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_header_fec_decoder_dims(self._h, C.byref(n_llrs), C.byref(n_bytes)), "HeaderFecDecoder.start")
+        self.llrs_per_codeword, self.header_bytes = n_llrs.value, n_bytes.value
 
     def process_bulk(self, llrs):
-        """llrs: CUDA float32, 256 per codeword.  Returns (headers [n, 4] uint8, invalid [n] bool)"""
+        """llrs: CUDA float32, llrs_per_codeword (256) per codeword.
+        Returns (headers [n, header_bytes (4)] uint8, invalid [n] bool)"""
         torch = _torch()
         llrs = llrs.contiguous()
         assert llrs.is_cuda and llrs.dtype == torch.float32
-        n = llrs.numel() // 256
-        out = np.empty((max(n, 1), 4), dtype=np.uint8)
+        n = llrs.numel() // self.llrs_per_codeword
+        out = np.empty((max(n, 1), self.header_bytes), dtype=np.uint8)
         inval = np.empty(max(n, 1), dtype=np.uint8)
         check(lib().gr4pm_header_fec_decoder_process(self._h, llrs.data_ptr(), n, _np_ptr(out), _np_ptr(inval)),
               "HeaderFecDecoder.processBulk")

@@ -834,7 +834,17 @@ try {
                 set_error("alist: bad row entry");
                 return GR4PM_ERR_INVALID;
             }
+            // a layer's lanes write P[v] at once: a check that holds v twice has two writers, and the last one wins
+            for (unsigned j = 0; j < row_deg[c]; ++j)
+                if (row_var[c * kMaxDeg + j] == static_cast<uint8_t>(x - 1)) {
+                    set_error("alist: check %u names variable %ld twice", c + 1, x);
+                    return GR4PM_ERR_INVALID;
+                }
             row_var[c * kMaxDeg + row_deg[c]++] = static_cast<uint8_t>(x - 1);
+        }
+        if (row_deg[c] == 0) {
+            set_error("alist: check %u has no variables", c + 1);
+            return GR4PM_ERR_INVALID;
         }
     }
     // layers (see the kernel's comment)
@@ -908,6 +918,15 @@ try {
     delete h;
 }
 GR4PM_ABI_CATCH_VOID
+gr4pm_status gr4pm_header_fec_decoder_dims(const gr4pm_header_fec_decoder* h, size_t* llrs_per_codeword,
+                                           size_t* header_bytes)
+try {
+    if (!h) return GR4PM_ERR_INVALID;
+    if (llrs_per_codeword) *llrs_per_codeword = 2 * static_cast<size_t>(h->n);
+    if (header_bytes) *header_bytes = (h->n - h->m) / 8;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
 gr4pm_status gr4pm_header_fec_decoder_process(gr4pm_header_fec_decoder* h, const float* llrs, size_t n_codewords,
                                               uint8_t* headers, uint8_t* invalid)
 try {

@@ -123,7 +123,16 @@ struct HeaderLoop {
         gr4pm_header_payload_split_params hp{ 256, s }; // :136-137
         GR4PM_TRY(gr4pm_header_payload_split_create(&hp, &split));
         gr4pm_header_fec_decoder_params fp{ alist, 25, s }; // :138
-        return gr4pm_header_fec_decoder_create(&fp, &fec);
+        GR4PM_TRY(gr4pm_header_fec_decoder_create(&fp, &fec));
+        // the split above, acc and bytes below and gr4pm_header_parse are built for the header code's 256 LLRs -> 4 bytes
+        size_t n_llrs = 0, n_bytes = 0;
+        GR4PM_TRY(gr4pm_header_fec_decoder_dims(fec, &n_llrs, &n_bytes));
+        if (n_llrs != 256 || n_bytes != 4) {
+            set_error("header_alist: a code of %zu LLRs -> %zu header bytes per codeword; the receiver takes 256 -> 4",
+                      n_llrs, n_bytes);
+            return GR4PM_ERR_INVALID;
+        }
+        return GR4PM_OK;
     }
     void destroy()
     {

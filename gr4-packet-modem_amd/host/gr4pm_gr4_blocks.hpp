@@ -1581,6 +1581,15 @@ public:
         }
         gr4pm_header_fec_decoder_params p{ text.c_str(), 25, nullptr };
         detail::check(gr4pm_header_fec_decoder_create(&p, &_h), "HeaderFecDecoder::start");
+        // processBulk and the 1 : 64 resampling ratio are the header code's: 256 LLRs -> 4 bytes
+        size_t n_llrs = 0, n_bytes = 0;
+        const gr4pm_status st = gr4pm_header_fec_decoder_dims(_h, &n_llrs, &n_bytes);
+        if (st != GR4PM_OK || n_llrs != 256 || n_bytes != 4) {
+            gr4pm_header_fec_decoder_destroy(_h);
+            _h = nullptr;
+            throw gr::exception("HeaderFecDecoder: `alist` is a code of " + std::to_string(n_llrs) + " LLRs -> " +
+                                std::to_string(n_bytes) + " header bytes per codeword; the block takes 256 -> 4");
+        }
     }
     void stop() // :282-288
     {

@@ -581,6 +581,9 @@ gr4pm_status gr4pm_header_payload_split_process_c64(gr4pm_header_payload_split* 
  * The reference hands the LDPC decoding to its Rust dependency ldpc-toolbox
  * (ldpc_toolbox_decoder_ctor_alist_string(alist, "HLAminstari8", ""), :276, and
  * ldpc_toolbox_decoder_decode_f32, :315-321, 25 iterations).  `alist` is that same string.
+ * The decoder itself takes any (n, m) code with n <= 256, m <= 192, row weight 1 ... 8, no variable twice in a row,
+ * n - m a multiple of 8 up to 64 and a layering of at most 24 steps (create refuses the rest): 2 n LLRs ->
+ * (n - m) / 8 bytes per codeword, gr4pm_header_fec_decoder_dims.
  * ---------------------------------------------------------------------------------- */
 typedef struct gr4pm_header_fec_decoder gr4pm_header_fec_decoder;
 typedef struct {
@@ -597,8 +600,13 @@ typedef struct {
 gr4pm_status gr4pm_header_fec_decoder_create(const gr4pm_header_fec_decoder_params* params,
                                              gr4pm_header_fec_decoder** out);
 void gr4pm_header_fec_decoder_destroy(gr4pm_header_fec_decoder* h);
-/* llrs: device, 256 per codeword.  headers: host, 4 bytes per codeword; invalid: host, one
- * flag per codeword (the "invalid_header" tag of :322-326). */
+/* The sizes of one codeword of the handle's (n, m) code: 2 n LLRs in (the codeword twice, :308-312) and (n - m) / 8
+ * header bytes out -- 256 and 4 for the header code.  Either pointer may be NULL.  A caller whose buffers are built
+ * for one code asks here after create and refuses every other code. */
+gr4pm_status gr4pm_header_fec_decoder_dims(const gr4pm_header_fec_decoder* h, size_t* llrs_per_codeword,
+                                           size_t* header_bytes);
+/* llrs: device, 2 n per codeword.  headers: host, (n - m) / 8 bytes per codeword; invalid: host, one
+ * flag per codeword (the "invalid_header" tag of :322-326).  See gr4pm_header_fec_decoder_dims. */
 gr4pm_status gr4pm_header_fec_decoder_process(gr4pm_header_fec_decoder* h, const float* llrs,
                                               size_t n_codewords, uint8_t* headers, uint8_t* invalid);
 

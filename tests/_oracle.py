@@ -517,9 +517,12 @@ class HeaderFecDecoder:
     def __init__(self, alist):
         self._h = lib().orc_ldpc_create(alist.encode())
         assert self._h
+        self.n, self.m = (int(t) for t in alist.split()[:2])
 
     def process(self, llrs, arithmetic=0):
-        """arithmetic 1: the product's 8-bit message form (gr4pm_header_fec_decoder_params::arithmetic)"""
+        """the block as the reference has it, 256 LLRs -> 4 bytes (the (128, 32) code only).
+        arithmetic 1: the product's 8-bit message form (gr4pm_header_fec_decoder_params::arithmetic)"""
+        assert (self.n, self.m) == (128, 96), "orc_header_fec_decode is written for 256 LLRs -> 4 bytes: use decode()"
         x = _f32(llrs)
         n = x.size // 256
         out = np.empty((n, 4), dtype=np.uint8)
@@ -527,10 +530,12 @@ class HeaderFecDecoder:
         (lib().orc_header_fec_decode_q8 if arithmetic else lib().orc_header_fec_decode)(self._h, _p(x), n, _p(out), _p(inval))
         return out, inval.astype(bool)
 
-    def decode(self, llrs, max_iterations=25):
+    def decode(self, llrs, max_iterations=25, arithmetic=0):
+        """one codeword of any code: n LLRs -> (the k = n - m information bits, iterations used or -1: no codeword)"""
         x = _f32(llrs)
-        bits = np.empty(32, dtype=np.uint8)
-        it = lib().orc_ldpc_decode(self._h, _p(x), _p(bits), max_iterations)
+        assert x.size == self.n
+        bits = np.empty(self.n - self.m, dtype=np.uint8)
+        it = (lib().orc_ldpc_decode_q8 if arithmetic else lib().orc_ldpc_decode)(self._h, _p(x), _p(bits), max_iterations)
         return bits, it
 
     def __del__(self):

@@ -463,6 +463,24 @@ static int zmq_mode(int argc, char** argv)
     return 0;
 }
 
+// HeaderFecDecoder::start() with the alist text of a file: the block is built for the header code's 256 LLRs -> 4 bytes
+// and refuses (gr::exception, exit status 1 through main) every other code the decoder itself accepts
+static int fec_alist(int argc, char** argv)
+{
+    if (argc < 3) return 2;
+    std::ifstream f(argv[2]);
+    if (!f) return 2;
+    std::stringstream ss;
+    ss << f.rdbuf();
+    gr::stub::Graph fg;
+    auto& dec = fg.emplaceBlock<HeaderFecDecoder>();
+    dec.alist = ss.str();
+    dec.start();
+    dec.stop();
+    std::printf("started\n");
+    return 0;
+}
+
 // A double-mapped ring between two wrapped blocks with host_output = false (gnuradio4's CircularBuffer maps its storage
 // twice, back to back): the producer's spans run past the end of the first mapping, the consumer -- reading in smaller
 // chunks -- sees the items behind the wrap at addresses one ring size lower.  The host memory of the ring is never
@@ -636,7 +654,8 @@ int main(int argc, char** argv)
         if (argc >= 2 && std::strcmp(argv[1], "zmq") == 0) return zmq_mode(argc, argv);
         if (argc >= 2 && std::strcmp(argv[1], "mirror") == 0) return mirror(argc, argv);
         if (argc >= 2 && std::strcmp(argv[1], "threads") == 0) return threads(argc, argv);
-        std::fprintf(stderr, "usage: %s chain|receiver|blocks|mirror|threads ...\n", argv[0]);
+        if (argc >= 2 && std::strcmp(argv[1], "fec_alist") == 0) return fec_alist(argc, argv);
+        std::fprintf(stderr, "usage: %s chain|receiver|blocks|mirror|threads|fec_alist ...\n", argv[0]);
         return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "gr4_blocks_driver: %s\n", e.what());
