@@ -3,6 +3,7 @@
 
     packet_transmitter_file.py output_file (--in packets.bin | --random COUNT SIZE) [--stream-mode] [--gap N]
                                [--format {cf32,sc16,sc8,cu8}] [--gain G] [--tune CYCLES_PER_SAMPLE --interpolate N[/M]]
+                               [--fft-duc]
 
 makes the IQ of PacketTransmitterPdu (packet_transmitter_pdu.hpp:40-355) on the GPU (gr4pm_packet_transmitter) at
 4 samples/symbol and writes it to `output_file` as raw little-endian complex64 (what packet_receiver_file.py reads).
@@ -23,7 +24,11 @@ transmitter, and packet_receiver_file.py --tune F --decimate I receives the file
 prototype's P - 1 items of tail are flushed, so the last burst's ramp-down is whole.  `--interpolate N/M` (N >= M, for
 instance 25/4 for a 25 Msps file of a 1 Msym/s carrier): N / M file samples per transmitter sample, the same Duc
 resampling by N / M in the same pass (DESIGN section 19), so a file can be written at any rate above the modem's;
-packet_receiver_file.py --tune F --decimate N/M receives it."""
+packet_receiver_file.py --tune F --decimate N/M receives it.
+
+`--fft-duc` (with `--tune F --interpolate I`, I a power of two in 4 .. 64): the `FftDuc` (gr4pm_fft_duc: the same filter as
+fast convolution) in the Duc's place, its flush() for the tail.  packet_receiver_file.py --tune F
+--decimate I receives the file, and so does its --fft-ddc."""
 import argparse
 import os
 import sys
@@ -61,10 +66,11 @@ def interpolation(v):
 
 
 def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, fmt="cf32", gain=None, stats=None,
-             tune=None, interpolate=None):
+             tune=None, interpolate=None, fft_duc=False):
     """writes the IQ of `packets` to out_path; returns the number of samples written.  stats: an optional dict that
     receives "clipped", the number of components an integer format clipped.  tune / interpolate: a Duc behind the
-    transmitter; interpolate: an integer, "N/M" or (N, M)"""
+    transmitter; interpolate: an integer, "N/M" or (N, M).  fft_duc: the FftDuc in its place (tune and an integer
+    interpolate that the block takes)"""
     pkg = pkg or ge.load_package()
     clipped = None if fmt == "cf32" else torch.zeros(1, dtype=torch.int64, device="cuda")
     empty = [k for k, p in enumerate(packets) if len(p) == 0]
@@ -73,14 +79,21 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
     batch_bytes = max([sum(len(p) for p in packets[i:i + batch]) for i in range(0, len(packets), batch)] + [1])
     tx = pkg.PacketTransmitter(stream_mode=stream_mode, samples_per_symbol=4, max_packets=batch,
                                max_payload_bytes=batch_bytes)
-    duc = None
-    if tune is not None or interpolate is not None:
+    duc = fast = None
+    if tune is not None or interpolate is not None or fft_duc:
         up, down = (1, 1) if interpolate is None else (interpolate if isinstance(interpolate, tuple) else interpolation(interpolate))
-        duc = pkg.Duc([0.0 if tune is None else tune], up, decimation=down)
+        if fft_duc:
+            if tune is None or interpolate is None or down != 1:
+                raise ValueError("the FftDuc needs a carrier offset and an integer interpolation (--tune F --interpolate I)")
+            fast = pkg.FftDuc([tune], up)
+        else:
+            duc = pkg.Duc([0.0 if tune is None else tune], up, decimation=down)
     written = 0
 
     def emit(f, x):
-        if duc is not None:
+        if fast is not None:
+            emit_wide(f, fast.process_bulk(x))
+        elif duc is not None:
             for lo in range(0, x.numel(), duc.max_items):
                 emit_wide(f, duc.process_bulk(x[lo:lo + duc.max_items]))
         else:
@@ -99,6 +112,8 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
             gaps = None if stream_mode else [gap] * len(chunk)
             x, _, _ = tx.process_bulk(chunk, gaps=gaps)
             emit(f, x)
+        if fast is not None:  # whole segments: what the items so far still owe, the filter's tail included
+            emit_wide(f, fast.flush())
         if duc is not None:  # the filter's tail
             emit(f, torch.zeros(len(duc.taps) // duc.interpolation + 1, dtype=torch.complex64, device="cuda"))
     if stats is not None and clipped is not None:
@@ -120,6 +135,8 @@ def main():
     ap.add_argument("--tune", type=float, metavar="CYCLES_PER_SAMPLE", help="the carrier's offset in the file (a Duc behind)")
     ap.add_argument("--interpolate", metavar="N[/M]", help="file samples per transmitter sample, an integer or a ratio N/M "
                     "such as 25/4 (a Duc behind)")
+    ap.add_argument("--fft-duc", action="store_true", help="the FftDuc in the Duc's place: with --tune F --interpolate I, I a "
+                    "power of two in 4 .. 64")
     a = ap.parse_args()
     if a.stream_mode and a.gap:
         ap.error("--gap is a burst mode option")
@@ -128,6 +145,13 @@ def main():
             a.interpolate = interpolation(a.interpolate)
         except ValueError as e:
             ap.error(str(e))
+    if a.fft_duc:
+        if a.tune is None or a.interpolate is None:
+            ap.error("--fft-duc needs --tune F --interpolate I")
+        n, m = a.interpolate
+        if m != 1 or n not in (4, 8, 16, 32, 64):
+            ap.error(f"--fft-duc: --interpolate {n}{'/%d' % m if m != 1 else ''}: the FftDuc takes a power of two in 4 .. 64 "
+                     "(and no ratio N/M); the Duc without --fft-duc takes the rest")
     if a.random:
         count, size = a.random
         if not 1 <= size <= 65535:
@@ -140,7 +164,7 @@ def main():
         sys.exit("packet_transmitter_file.py needs a GPU")
     stats = {}
     n = transmit(packets, a.output_file, a.stream_mode, a.gap, fmt=a.format, gain=a.gain, stats=stats,
-                 tune=a.tune, interpolate=a.interpolate)
+                 tune=a.tune, interpolate=a.interpolate, fft_duc=a.fft_duc)
     print(f"{len(packets)} packets, {n} samples -> {a.output_file}" +
           (f" ({a.format}, {stats['clipped']} clipped components)" if "clipped" in stats else ""))
 

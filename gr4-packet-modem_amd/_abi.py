@@ -266,6 +266,12 @@ class FftDdcMixedParams(C.Structure):
                 ("start_index", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class FftDucParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("interpolation", C.c_size_t), ("frequencies", C.c_void_p), ("gains", C.c_void_p),
+                ("taps", C.c_void_p), ("n_taps", C.c_size_t), ("taps_per_phase", C.c_size_t), ("overlap", C.c_int64),
+                ("images", C.c_size_t), ("start_index", C.c_uint64), ("stream", C.c_void_p)]
+
+
 # gr4pm_row_record: 24 bytes, the last four are padding
 ROW_RECORD_DTYPE = np.dtype({"names": ["step", "phase0", "freq"], "formats": ["<u8", "<u8", "<i4"], "offsets": [0, 8, 16],
                              "itemsize": 24})
@@ -367,6 +373,8 @@ EXPORTS = [
     "gr4pm_fft_ddc_frequencies", "gr4pm_fft_ddc_sizes", "gr4pm_fft_ddc_process", "gr4pm_fft_ddc_process_iq",
     "gr4pm_fft_ddc_mixed_create", "gr4pm_fft_ddc_mixed_destroy", "gr4pm_fft_ddc_mixed_reset", "gr4pm_fft_ddc_mixed_frames_for",
     "gr4pm_fft_ddc_mixed_frequencies", "gr4pm_fft_ddc_mixed_sizes", "gr4pm_fft_ddc_mixed_process", "gr4pm_fft_ddc_mixed_process_iq",
+    "gr4pm_fft_duc_taps", "gr4pm_fft_duc_create", "gr4pm_fft_duc_destroy", "gr4pm_fft_duc_reset", "gr4pm_fft_duc_output_items",
+    "gr4pm_fft_duc_frequencies", "gr4pm_fft_duc_sizes", "gr4pm_fft_duc_pending", "gr4pm_fft_duc_process",
 ]
 
 _lib = None
@@ -635,6 +643,16 @@ def lib():
     L.gr4pm_fft_ddc_mixed_sizes.argtypes = [vp, szp, szp]
     L.gr4pm_fft_ddc_mixed_process.argtypes = [vp, vp, sz, vp, sz, sz, vp]
     L.gr4pm_fft_ddc_mixed_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, sz, vp]
+    L.gr4pm_fft_duc_taps.argtypes = [sz, sz, vp]
+    L.gr4pm_fft_duc_create.argtypes = [C.POINTER(FftDucParams), C.POINTER(vp)]
+    L.gr4pm_fft_duc_destroy.argtypes = [vp]
+    L.gr4pm_fft_duc_destroy.restype = None
+    L.gr4pm_fft_duc_reset.argtypes = [vp]
+    L.gr4pm_fft_duc_output_items.argtypes = [vp, sz, szp]
+    L.gr4pm_fft_duc_frequencies.argtypes = [vp, vp]
+    L.gr4pm_fft_duc_sizes.argtypes = [vp, szp, szp]
+    L.gr4pm_fft_duc_pending.argtypes = [vp, szp]
+    L.gr4pm_fft_duc_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

@@ -2393,6 +2393,130 @@ class Duc:
         _destroy(self, "gr4pm_duc_destroy")
 
 
+def fft_duc_taps(interpolation, taps_per_phase=12):
+    """gr4pm_fft_duc_taps: the FftDuc's default prototype, duc_taps(interpolation, taps_per_phase) for a power-of-two
+    interpolation in 4 .. 64 (host only: works without a GPU)."""
+    n = int(interpolation) * int(taps_per_phase)
+    out = np.zeros(max(n, 1), dtype=np.float32)
+    check(lib().gr4pm_fft_duc_taps(int(interpolation), int(taps_per_phase), _np_ptr(out)), "fft_duc_taps")
+    return out[:n]
+
+
+class FftDuc:
+    """gr4pm_fft_duc: the Duc for many channels and a power-of-two interpolation (4 .. 64), as a fast-convolution
+    synthesis bank, the mirror of FftDdc: per channel the Duc's rotator and a forward transform of 2048 / interpolation
+    points, a product over `images` * 2048 / interpolation bins around the channel's nearest bin summed into one
+    2048-bin spectrum, and one inverse 2048-point transform per segment shared by all len(frequencies) <= 64 channels
+    (DESIGN section 27).  Row k is interpolated through the prototype, scaled by gains[k] (None: 1) and centred on
+    frequencies[k] (cycles per output sample; .frequencies holds the values in use); with images = interpolation the
+    result is the Duc's up to float32 rounding, with fewer images it differs by the prototype's response outside
+    +-images / (2 interpolation) cycles per sample.  taps: float32 prototype taps (None: fft_duc_taps(interpolation,
+    taps_per_phase)); overlap: a multiple of interpolation with len(taps) - 1 <= overlap <= 1984 (None: the smallest
+    multiple of 256 that is >= len(taps) - 1); .hop = 2048 - overlap.  process_bulk() takes any number of items per row
+    and delivers whole segments, hop samples for every hop / interpolation items; the rest stays on the device
+    (.pending items per row), and any cutting of the rows into calls gives the same bits.  flush() brings out what the
+    items so far still owe.  Frequencies and gains are fixed.  The handle works on the stream that is current when it
+    is made."""
+
+    def __init__(self, frequencies, interpolation, gains=None, taps=None, taps_per_phase=12, overlap=None, images=2,
+                 start_index=0):
+        self.interpolation, self.images = int(interpolation), int(images)
+        f, self.taps, self.start_index = _xlate_settings("FftDuc", frequencies, self.interpolation, taps, taps_per_phase,
+                                                         start_index, fft_duc_taps)
+        if self.images < 0 or (overlap is not None and not 0 <= int(overlap) < 1 << 62):
+            raise Gr4pmError("FftDuc: images and overlap must not be negative")
+        self.n_channels = int(f.size)
+        a = None
+        if gains is not None:
+            a = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, dtype=np.float64)))
+            if a.shape != f.shape:
+                raise Gr4pmError("FftDuc: one gain per frequency")
+        self.gains = np.ones(f.size) if a is None else a
+        stream = _stream_handle()
+        self._stream = stream.value
+        self._h = C.c_void_p()
+        p = _abi.FftDucParams(self.n_channels, self.interpolation, _np_ptr(f) if f.size else None,
+                              _np_ptr(a) if a is not None and a.size else None, _np_ptr(self.taps), self.taps.size,
+                              int(taps_per_phase), -1 if overlap is None else int(overlap), self.images, self.start_index,
+                              stream)
+        check(lib().gr4pm_fft_duc_create(C.byref(p), C.byref(self._h)), "FftDuc")
+        q = np.zeros(self.n_channels, dtype=np.float64)
+        check(lib().gr4pm_fft_duc_frequencies(self._h, _np_ptr(q)), "FftDuc.frequencies")
+        self.frequencies = q
+        v, hop = C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_sizes(self._h, C.byref(v), C.byref(hop)), "FftDuc.sizes")
+        self.overlap, self.hop = v.value, hop.value
+        self._taken = 0  # items per row since create or reset
+
+    @property
+    def pending(self):
+        """items per row taken but not yet in a delivered segment"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_pending(self._h, C.byref(n)), "FftDuc.pending")
+        return n.value
+
+    def output_items(self, n_in):
+        """samples the next process_bulk() of n_in items per row delivers: whole segments of .hop samples, so the count
+        depends on where the handle stands in its stream (the state is unchanged by asking)"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_output_items(self._h, int(n_in), C.byref(n)), "FftDuc.output_items")
+        return n.value
+
+    def reset(self):
+        """back to start_index: zero prehistory, no carried items"""
+        check(lib().gr4pm_fft_duc_reset(self._h), "FftDuc.reset")
+        self._taken = 0
+
+    def process_bulk(self, v, out=None):
+        """v: a CUDA complex64 tensor [n_channels, n] with contiguous rows and any row stride (a window of a wider
+        tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[output_items(n)]; out: an optional
+        contiguous CUDA complex64 tensor of at least that many samples to write into."""
+        torch = _torch()
+        if isinstance(v, torch.Tensor) and self.n_channels == 1 and (v.dim() == 1 or (v.dim() == 2 and v.shape[0] == 1)):
+            v = _dev_c64(v.reshape(-1) if v.dim() == 2 else v, "v")  # one row: its stride means nothing
+            n_in, stride = v.numel(), v.numel()
+        else:
+            v = _dev_c64_rows(v, "v")
+            if v.shape[0] != self.n_channels:
+                raise Gr4pmError(f"FftDuc: v is {tuple(v.shape)}, the handle has {self.n_channels} rows")
+            n_in, stride = v.shape[1], (v.stride(0) if self.n_channels > 1 else v.shape[1])
+        if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
+            _inputs_ready(v)  # made on another stream than the handle's
+        samples = self.output_items(n_in)
+        if out is None:
+            out = torch.empty(samples, dtype=torch.complex64, device=v.device)
+        else:
+            out = _dev_c64(out, "out")
+            if out.dim() != 1 or out.numel() < samples:
+                raise Gr4pmError(f"FftDuc: out is {tuple(out.shape)}, the call makes [{samples}]")
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_process(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), out.numel(), C.byref(n)),
+              "FftDuc.process")
+        self._taken += n_in
+        return out[: n.value]
+
+    def flush_items(self):
+        """zero items per row that flush() feeds: the fewest after which every sample the items so far influence is out.
+        The last of T items reaches the samples up to (T - 1) interpolation + len(taps) - 1, and T' items deliver
+        floor(T' interpolation / hop) hop samples."""
+        if self._taken == 0:
+            return 0
+        need = (self._taken - 1) * self.interpolation + self.taps.size
+        segments = -(-need // self.hop)
+        return max(segments * (self.hop // self.interpolation) - self._taken, 0)
+
+    def flush(self):
+        """feeds flush_items() zero items per row and returns the samples that come out: with them every sample
+        influenced by the items so far is delivered, the prototype's len(taps) - 1 samples of tail included.  The result
+        is bit-equal to process_bulk() of that many zeros, and the stream goes on behind it."""
+        torch = _torch()
+        n = self.flush_items()
+        return self.process_bulk(torch.zeros((self.n_channels, n), dtype=torch.complex64, device="cuda"))
+
+    def __del__(self):
+        _destroy(self, "gr4pm_fft_duc_destroy")
+
+
 def spectrum_window(n):
     """gr4pm_spectrum_window: the periodic Hann window 0.5 - 0.5 cos(2 pi i / n) of the Spectrum block, computed in double
     and rounded to float32 once (host only: works without a GPU)."""

@@ -1749,6 +1749,67 @@ gr4pm_status gr4pm_fft_ddc_mixed_process(gr4pm_fft_ddc_mixed* h, const gr4pm_c64
 gr4pm_status gr4pm_fft_ddc_mixed_process_iq(gr4pm_fft_ddc_mixed* h, const void* in, int format, float scale, size_t n_in,
                                             gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames);
 
+/* ---- FftDuc: K carriers onto one stream from one shared transform (the project's own block) ----
+ * The Duc's drop-in for power-of-two interpolations and many channels, the mirror of the FftDdc: a fast-convolution
+ * (overlap-save) synthesis bank.  N = 2048, K channels (1 .. 64), I a power of two in 4 .. 64, B = N / I, a real finite
+ * prototype h[0 .. L - 1] (NULL: gr4pm_duc_taps(I, taps_per_phase, 0.25, 0.75), DC gain I), real finite gains a_k
+ * (NULL: all 1), an overlap V with I | V and L - 1 <= V <= N - 64 (overlap < 0: the smallest multiple of 256 that is
+ * >= L - 1), hop = N - V, hopI = hop / I, images = R, a power of two with 1 <= R <= I.  start_index: the absolute index
+ * of the first output sample.  v_k[m] = 0 for m < 0.
+ *     w_k = llrint(f_k 2^32) mod 2^32,   c_k = floor(w_k N / 2^32 + 1 / 2) mod N   (the nearest bin, in integers)
+ *     z_k[m] = q_k[m] v_k[m],   q_k[m] = exp(+2 pi j ((w_k (start_index + m I)) mod 2^32) / 2^32)
+ *         (the Duc's rotator: double sincospi of the exact argument rounded to float, then four fmaf from zero)
+ *     segment s: the output samples j = a_s .. a_s + N - 1, a_s = s hop - V; the input items m = a_s / I + n', n' < B
+ *     Z_k[v] = sum_n' z_k[a_s / I + n'] exp(-2 pi j v n' / B),   v in [0, B)   (forward, unnormalised)
+ *     G_k[u] = (a_k / N) sum_t h[t] exp(-2 pi j ((c_k + u) / N - w_k / 2^32) t),   u in [-R B / 2, R B / 2)
+ *         (host, double, each component rounded to float once)
+ *     S_s[b] = sum_k G_k[u] Z_k[b mod B] over the channels whose slice holds b = (c_k + u) mod N
+ *         (one accumulator per bin, from zero, k ascending)
+ *     x_s[p] = sum_b S_s[b] exp(+2 pi j b p / N);   p = V .. N - 1 are kept:   out[s hop + p - V] = x_s[p]
+ * With R = I the definition is the Duc's x[start_index + j] in exact arithmetic; with R < I it differs by the
+ * prototype's response outside +-R / (2 I) cycles per sample: |out - x_Duc| <= sum_k ||v_k over the segment||_2
+ * ||H_k outside the slice||_2 / sqrt(N), H_k = N G_k.  Segment s is complete after (s + 1) hopI items per row; a call of
+ * n_in items per row delivers whole segments, (floor((taken + n_in) / hopI) - floor(taken / hopI)) hop samples; the
+ * handle carries V / I + (taken mod hopI) < B items per row, and any cutting of the rows into calls gives the same
+ * bits. */
+typedef struct gr4pm_fft_duc gr4pm_fft_duc;
+typedef struct {
+    size_t n_channels;          /* K: 1 .. 64 */
+    size_t interpolation;       /* I: a power of two, 4 .. 64 */
+    const double* frequencies;  /* HOST, K items, cycles per output sample, finite */
+    const double* gains;        /* HOST, K items, finite; NULL: all 1 */
+    const float* taps;          /* HOST, n_taps items, finite; NULL: gr4pm_fft_duc_taps(I, taps_per_phase) */
+    size_t n_taps;              /* L */
+    size_t taps_per_phase;      /* of the design when taps is NULL */
+    int64_t overlap;            /* V; negative: the default */
+    size_t images;              /* R */
+    uint64_t start_index;
+    void* stream;               /* hipStream_t */
+} gr4pm_fft_duc_params;
+/* Host only: the Duc's design (gr4pm_duc_taps with the band edges 0.25 and 0.75 of the input rate) of
+ * taps_per_phase * interpolation floats for an interpolation the FftDuc takes. */
+gr4pm_status gr4pm_fft_duc_taps(size_t interpolation, size_t taps_per_phase, float* out);
+/* Refused with GR4PM_ERR_INVALID and no handle: K out of range, a NULL or non-finite frequency, a non-finite gain, I or
+ * R no power of two or out of range, a non-finite tap, n_taps out of range, V no multiple of I, below L - 1 or above
+ * N - 64. */
+gr4pm_status gr4pm_fft_duc_create(const gr4pm_fft_duc_params* params, gr4pm_fft_duc** out);
+void gr4pm_fft_duc_destroy(gr4pm_fft_duc* h);
+/* back to start_index: zero prehistory, nothing carried */
+gr4pm_status gr4pm_fft_duc_reset(gr4pm_fft_duc* h);
+/* samples the next call of n_in items per row delivers */
+gr4pm_status gr4pm_fft_duc_output_items(const gr4pm_fft_duc* h, size_t n_in, size_t* n_out);
+/* out: HOST, K items: w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_fft_duc_frequencies(const gr4pm_fft_duc* h, double* out);
+gr4pm_status gr4pm_fft_duc_sizes(const gr4pm_fft_duc* h, size_t* overlap, size_t* hop);
+/* items per row taken but not yet in a delivered segment: taken mod hopI */
+gr4pm_status gr4pm_fft_duc_pending(const gr4pm_fft_duc* h, size_t* items);
+/* in: DEVICE, K rows in_stride items apart, n_in items each.  out: DEVICE, room for out_cap samples.  Enqueues on the
+ * handle's stream, reads nothing back and does not wait.  Refused with gr4pm_last_error set, *n_out = 0 and nothing
+ * enqueued: a NULL in with n_in > 0, a NULL out when the call delivers samples, in_stride < n_in with K > 1
+ * (GR4PM_ERR_INVALID); n_in > 2^40 or fewer than the samples of room (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
+gr4pm_status gr4pm_fft_duc_process(gr4pm_fft_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
+                                   size_t out_cap, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,12 @@ BUDGETS = [
     # the MixedFftDdc block: the same wave with its sizes from a per-channel descriptor (47 registers as built) and the same
     # LDS image, sized for B = 512 whatever a channel's B
     (r"k_fft_ddc_mixed", dict(vgpr=48, lds=10240, lds_exact=True, scratch=0)),
+    # the FftDuc block: four waves per segment, each with the double-precision rotator and a radix-2 transform in its own
+    # two LDS buffers, the segment's bins in LDS (74 registers as built, six waves per SIMD; its LDS is dynamic, 2 KiB of
+    # twiddles, 16 KiB of bins and 64 B bytes of buffers, at most 50 KiB), and the FftDdc's forward wave run as the inverse,
+    # which stores part of its result (187 registers as built, two waves per SIMD by its LDS)
+    (r"k_fft_duc_assemble", dict(vgpr=80, lds=0, lds_exact=True, scratch=0)),
+    (r"k_fft_duc_inverse", dict(vgpr=192, lds=151552, lds_exact=True, scratch=0)),
     # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
     # section 21)
     (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
