@@ -272,6 +272,12 @@ class FftDucParams(C.Structure):
                 ("images", C.c_size_t), ("start_index", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class FftDucMixedParams(C.Structure):
+    _fields_ = [("n_channels", C.c_size_t), ("interpolations", C.c_void_p), ("frequencies", C.c_void_p), ("gains", C.c_void_p),
+                ("taps", C.c_void_p), ("n_taps", C.c_void_p), ("taps_per_phase", C.c_size_t), ("images", C.c_void_p),
+                ("overlap", C.c_int64), ("start_index", C.c_uint64), ("stream", C.c_void_p)]
+
+
 # gr4pm_row_record: 24 bytes, the last four are padding
 ROW_RECORD_DTYPE = np.dtype({"names": ["step", "phase0", "freq"], "formats": ["<u8", "<u8", "<i4"], "offsets": [0, 8, 16],
                              "itemsize": 24})
@@ -375,6 +381,9 @@ EXPORTS = [
     "gr4pm_fft_ddc_mixed_frequencies", "gr4pm_fft_ddc_mixed_sizes", "gr4pm_fft_ddc_mixed_process", "gr4pm_fft_ddc_mixed_process_iq",
     "gr4pm_fft_duc_taps", "gr4pm_fft_duc_create", "gr4pm_fft_duc_destroy", "gr4pm_fft_duc_reset", "gr4pm_fft_duc_output_items",
     "gr4pm_fft_duc_frequencies", "gr4pm_fft_duc_sizes", "gr4pm_fft_duc_pending", "gr4pm_fft_duc_process",
+    "gr4pm_fft_duc_mixed_create", "gr4pm_fft_duc_mixed_destroy", "gr4pm_fft_duc_mixed_reset", "gr4pm_fft_duc_mixed_items_for",
+    "gr4pm_fft_duc_mixed_output_items", "gr4pm_fft_duc_mixed_frequencies", "gr4pm_fft_duc_mixed_sizes", "gr4pm_fft_duc_mixed_pending",
+    "gr4pm_fft_duc_mixed_process",
 ]
 
 _lib = None
@@ -653,6 +662,16 @@ def lib():
     L.gr4pm_fft_duc_sizes.argtypes = [vp, szp, szp]
     L.gr4pm_fft_duc_pending.argtypes = [vp, szp]
     L.gr4pm_fft_duc_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
+    L.gr4pm_fft_duc_mixed_create.argtypes = [C.POINTER(FftDucMixedParams), C.POINTER(vp)]
+    L.gr4pm_fft_duc_mixed_destroy.argtypes = [vp]
+    L.gr4pm_fft_duc_mixed_destroy.restype = None
+    L.gr4pm_fft_duc_mixed_reset.argtypes = [vp]
+    L.gr4pm_fft_duc_mixed_items_for.argtypes = [vp, sz, vp]
+    L.gr4pm_fft_duc_mixed_output_items.argtypes = [vp, sz, szp]
+    L.gr4pm_fft_duc_mixed_frequencies.argtypes = [vp, vp]
+    L.gr4pm_fft_duc_mixed_sizes.argtypes = [vp, szp, szp]
+    L.gr4pm_fft_duc_mixed_pending.argtypes = [vp, szp]
+    L.gr4pm_fft_duc_mixed_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

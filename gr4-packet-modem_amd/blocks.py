@@ -2517,6 +2517,163 @@ class FftDuc:
         _destroy(self, "gr4pm_fft_duc_destroy")
 
 
+class MixedFftDuc:
+    """gr4pm_fft_duc_mixed: the FftDuc with an interpolation per row: carriers of different symbol rates onto one stream
+    from one assembling pass and one inverse transform per segment.  interpolations[k] is a power of
+    two in 4 .. 64; row k's item m sits at output sample m * interpolations[k], all rows start at output sample 0, and the
+    result is the sum of what FftDuc([frequencies[k]], interpolations[k], gains=[gains[k]]) makes of each row; with all
+    interpolations equal the block is the FftDuc bit for bit.  taps: a list of one float32 prototype per row (None:
+    fft_duc_taps(interpolations[k], taps_per_phase) each); images: an int or one per row; overlap: one for the handle, a
+    multiple of max(interpolations) with len(taps[k]) - 1 <= overlap <= 1984 for every k (None: the smallest multiple of
+    256 that takes all of them); .hop = 2048 - overlap.  The handle counts in slots of .slot = max(interpolations) output
+    samples: a call of u slots takes u * slot / interpolations[k] items of row k (items_for) and delivers the whole
+    segments they complete; the rest stays on the device (.pending slots), and any cutting into calls gives the same
+    bits.  flush() brings out what the items so far still owe.  The handle works on the stream that is current when it is
+    made."""
+
+    def __init__(self, frequencies, interpolations, gains=None, taps=None, taps_per_phase=12, overlap=None, images=2,
+                 start_index=0):
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(frequencies, dtype=np.float64)))
+        if f.ndim != 1:
+            raise Gr4pmError("MixedFftDuc: frequencies must be a list of numbers")
+        K = int(f.size)
+        itp = [int(i) for i in np.atleast_1d(interpolations)]
+        img = [int(images)] * K if np.ndim(images) == 0 else [int(r) for r in images]
+        if len(itp) != K or len(img) != K or (taps is not None and len(taps) != K):
+            raise Gr4pmError(f"MixedFftDuc: {K} frequencies need {K} interpolations, {K} images (or one) and {K} prototypes (or None)")
+        if min(itp + img + [0]) < 0 or (overlap is not None and not 0 <= int(overlap) < 1 << 62):
+            raise Gr4pmError("MixedFftDuc: interpolations, images and overlap must not be negative")
+        self.start_index = int(start_index)
+        if not 0 <= self.start_index < 1 << 64:
+            raise Gr4pmError("MixedFftDuc: start_index must fit 64 unsigned bits")
+        a = None
+        if gains is not None:
+            a = np.ascontiguousarray(np.atleast_1d(np.asarray(gains, dtype=np.float64)))
+            if a.shape != f.shape:
+                raise Gr4pmError("MixedFftDuc: one gain per frequency")
+        self.gains = np.ones(K) if a is None else a
+        if taps is not None:
+            self.taps = [np.ascontiguousarray(t, dtype=np.float32).reshape(-1) for t in taps]
+        else:
+            self.taps = [fft_duc_taps(i, taps_per_phase) for i in itp]
+        self.interpolations, self.images = np.array(itp, dtype=np.int64), np.array(img, dtype=np.int64)
+        self.n_channels = self.n_rows = K
+        self.slot = max(itp + [0])
+        i_arr, r_arr = np.array(itp, dtype=np.uintp), np.array(img, dtype=np.uintp)
+        l_arr = np.array([t.size for t in self.taps], dtype=np.uintp)
+        all_taps = np.ascontiguousarray(np.concatenate(self.taps + [np.zeros(1, dtype=np.float32)]))
+        stream = _stream_handle()
+        self._stream = stream.value
+        self._h = C.c_void_p()
+        p = _abi.FftDucMixedParams(K, _np_ptr(i_arr), _np_ptr(f) if K else None, _np_ptr(a) if a is not None and a.size else None,
+                                   _np_ptr(all_taps), _np_ptr(l_arr), int(taps_per_phase), _np_ptr(r_arr),
+                                   -1 if overlap is None else int(overlap), self.start_index, stream)
+        check(lib().gr4pm_fft_duc_mixed_create(C.byref(p), C.byref(self._h)), "MixedFftDuc")
+        q = np.zeros(K, dtype=np.float64)
+        check(lib().gr4pm_fft_duc_mixed_frequencies(self._h, _np_ptr(q)), "MixedFftDuc.frequencies")
+        self.frequencies = q
+        v, hop = C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_mixed_sizes(self._h, C.byref(v), C.byref(hop)), "MixedFftDuc.sizes")
+        self.overlap, self.hop = v.value, hop.value
+        self._taken = 0  # slots since create or reset
+
+    @property
+    def pending(self):
+        """slots taken but not yet in a delivered segment"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_mixed_pending(self._h, C.byref(n)), "MixedFftDuc.pending")
+        return n.value
+
+    def items_for(self, slots):
+        """items of each row a process_bulk() of `slots` slots takes (numpy, int64, one per row)"""
+        n = np.zeros(self.n_channels, dtype=np.uintp)
+        check(lib().gr4pm_fft_duc_mixed_items_for(self._h, int(slots), _np_ptr(n)), "MixedFftDuc.items_for")
+        return n.astype(np.int64)
+
+    def output_items(self, slots):
+        """samples the next process_bulk() of `slots` slots delivers: whole segments of .hop samples, so the count depends
+        on where the handle stands in its stream (the state is unchanged by asking)"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_mixed_output_items(self._h, int(slots), C.byref(n)), "MixedFftDuc.output_items")
+        return n.value
+
+    def reset(self):
+        """back to start_index: zero prehistory, nothing carried"""
+        check(lib().gr4pm_fft_duc_mixed_reset(self._h), "MixedFftDuc.reset")
+        self._taken = 0
+
+    def process_bulk(self, v, slots=None, out=None):
+        """v: a CUDA complex64 tensor [n_channels, n_cols] with contiguous rows and any row stride; row k's first
+        items_for(slots)[k] items are used.  slots: None for the most that n_cols covers for every row, n_cols *
+        min(interpolations) // slot.  Returns x[output_items(slots)]; out: an optional contiguous CUDA complex64 tensor of
+        at least that many samples to write into."""
+        torch = _torch()
+        if isinstance(v, torch.Tensor) and self.n_channels == 1 and v.dim() == 1:
+            v = v.reshape(1, -1)
+        v = _dev_c64_rows(v, "v")
+        if v.shape[0] != self.n_channels:
+            raise Gr4pmError(f"MixedFftDuc: v is {tuple(v.shape)}, the handle has {self.n_channels} rows")
+        most = v.shape[1] * int(self.interpolations.min()) // self.slot
+        slots = most if slots is None else int(slots)
+        if not 0 <= slots <= most:
+            raise Gr4pmError(f"MixedFftDuc: {slots} slots, the {v.shape[1]} columns of v cover {most}")
+        stride = v.stride(0) if self.n_channels > 1 else v.shape[1]
+        if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
+            _inputs_ready(v)  # made on another stream than the handle's
+        samples = self.output_items(slots)
+        if out is None:
+            out = torch.empty(samples, dtype=torch.complex64, device=v.device)
+        else:
+            out = _dev_c64(out, "out")
+            if out.dim() != 1 or out.numel() < samples:
+                raise Gr4pmError(f"MixedFftDuc: out is {tuple(out.shape)}, the call makes [{samples}]")
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_duc_mixed_process(self._h, v.data_ptr(), stride, slots, out.data_ptr(), out.numel(), C.byref(n)),
+              "MixedFftDuc.process")
+        self._taken += slots
+        return out[: n.value]
+
+    def flush_items(self):
+        """zero slots that flush() feeds: the fewest after which every sample the items so far influence is out.  The last
+        of row k's T_k = taken * slot / interpolations[k] items reaches the samples up to (T_k - 1) interpolations[k] +
+        len(taps[k]) - 1, and T slots deliver floor(T slot / hop) hop samples."""
+        if self._taken == 0:
+            return 0
+        need = max((self._taken * self.slot // int(i) - 1) * int(i) + t.size for i, t in zip(self.interpolations, self.taps))
+        segments = -(-need // self.hop)
+        return max(segments * (self.hop // self.slot) - self._taken, 0)
+
+    def flush(self):
+        """feeds flush_items() zero slots and returns the samples that come out: with them every sample influenced by the
+        items so far is delivered, the prototypes' tails included.  The result is bit-equal to process_bulk() of that
+        many slots of zeros, and the stream goes on behind it."""
+        torch = _torch()
+        n = self.flush_items()
+        cols = n * self.slot // int(self.interpolations.min()) if self.n_channels else 0
+        return self.process_bulk(torch.zeros((self.n_channels, cols), dtype=torch.complex64, device="cuda"), slots=n)
+
+    def pack(self, rows):
+        """rows: a list of n_channels one-dimensional CUDA complex64 tensors, bursts of different lengths at the rows' own
+        rates.  Returns (v, slots): v is [n_channels, n_cols] with row k the burst and zeros behind it, and `slots` the
+        fewest slots that take all of every burst (row k is padded to a whole number of slots); process_bulk(v, slots)
+        takes it."""
+        torch = _torch()
+        if len(rows) != self.n_channels:
+            raise Gr4pmError(f"MixedFftDuc: {len(rows)} rows, the handle has {self.n_channels}")
+        rows = [_dev_c64(r, "rows") for r in rows]
+        if any(r.dim() != 1 for r in rows):
+            raise Gr4pmError("MixedFftDuc: pack() takes one-dimensional rows")
+        per_slot = [self.slot // int(i) for i in self.interpolations]
+        slots = max(-(-r.numel() // p) for r, p in zip(rows, per_slot))
+        v = torch.zeros((self.n_channels, slots * max(per_slot)), dtype=torch.complex64, device=rows[0].device)
+        for k, r in enumerate(rows):
+            v[k, :r.numel()] = r
+        return v, slots
+
+    def __del__(self):
+        _destroy(self, "gr4pm_fft_duc_mixed_destroy")
+
+
 def spectrum_window(n):
     """gr4pm_spectrum_window: the periodic Hann window 0.5 - 0.5 cos(2 pi i / n) of the Spectrum block, computed in double
     and rounded to float32 once (host only: works without a GPU)."""

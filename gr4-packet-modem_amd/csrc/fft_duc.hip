@@ -26,11 +26,16 @@
 // A launch pair covers at most kChunk segments, so the spectra of a call of any length stay within one 64 MiB buffer
 // that the next pair reuses in stream order.  No atomics, no scratch; a segment's samples are a function of its B items
 // per row, the tables and its index only, whatever the cuts into calls.
+// The MixedFftDuc (hostlogic/fft_duc_mixed_plan.hpp) gives every row its own I_k, B_k = N / I_k, taps and
+// image count on the same segment grid, a_s being a multiple of every I_k: k_fft_duc_mixed_assemble is the assembling kernel
+// with a row's sizes from a descriptor table, both instantiate the same two device bodies (fft_duc_row_body,
+// fft_duc_add_body), and k_fft_duc_inverse serves both.  Its rows carry different numbers of items between calls, which
+// k_fft_duc_mixed_history moves between two buffers as stream_tail.hpp's kernel does for rows of one length.
 // Built with FFT_FLAGS: the transforms and the products may contract to FMA.  The rotator is written in explicit fmaf
 // (freq_xlate.hpp's cmac), so it is the Duc's under either set of flags.
 #include "spectrum_segment.hpp"
 #include "freq_xlate.hpp"
-#include "hostlogic/fft_duc_plan.hpp"
+#include "hostlogic/fft_duc_mixed_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -39,6 +44,18 @@ namespace {
 
 namespace iq = gr4pm::iq;
 using namespace gr4pm;
+using gr4pm::hostlogic::fft_duc_mixed_carried_offsets;
+using gr4pm::hostlogic::fft_duc_mixed_default_overlap;
+using gr4pm::hostlogic::fft_duc_mixed_items;
+using gr4pm::hostlogic::fft_duc_mixed_max_interpolation;
+using gr4pm::hostlogic::fft_duc_mixed_row;
+using gr4pm::hostlogic::fft_duc_mixed_slots_fit;
+using gr4pm::hostlogic::fft_duc_mixed_table_offsets;
+using gr4pm::hostlogic::fft_duc_mixed_validate;
+using gr4pm::hostlogic::fft_duc_mixed_validate_channels;
+using gr4pm::hostlogic::FftDucMixedRefusal;
+using gr4pm::hostlogic::FftDucMixedRow;
+using gr4pm::hostlogic::FftDucMixedVerdict;
 using gr4pm::hostlogic::fft_ddc_bin;
 using gr4pm::hostlogic::fft_ddc_pow2;
 using gr4pm::hostlogic::fft_ddc_table_word;
@@ -84,6 +101,57 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// One (segment, row) of an assembling kernel, by one wave in two LDS buffers of B items of its own (`mine`): the row's B
+// items from item v0 of hist[0 .. H) ++ in on, rotated on the way in, then log2 B Stockham stages.  The result is in
+// mine + (logB & 1) B.  Both assembling kernels instantiate this under the unit's one set of flags, so a row goes through
+// the same instructions whichever kernel it is in.  Wave-level synchronisation only
+__device__ __forceinline__ void fft_duc_row_body(float2* mine, const float2* tw, const float2* hist, size_t H, const float2* in,
+                                                 size_t v0, uint32_t wk, uint32_t i0, uint32_t I, uint32_t logB, uint32_t lane)
+{
+    const uint32_t B = 1u << logB;
+    for (uint32_t n = lane; n < B; n += 64) {
+        const size_t v = v0 + n;
+        const float2 x = v < H ? hist[v] : in[v - H];
+        float2 z = {0.0f, 0.0f};
+        cmac(z, mixer<1>(wk, i0 + n * I), x);
+        mine[n] = z;
+    }
+    wave_sync();
+    // stage of sub-transform length Ns: butterfly j takes items j and j + B / 2, position q = j mod Ns of its
+    // sub-transform, and writes items (j - q) 2 + q and Ns later.  Natural order in, natural order out
+    for (uint32_t ls = 0; ls < logB; ++ls) {
+        const uint32_t Ns = 1u << ls;
+        const float2* from = mine + (ls & 1) * B;
+        float2* to = mine + ((ls & 1) ^ 1) * B;
+        for (uint32_t j = lane; j < B / 2; j += 64) {
+            const uint32_t q = j & (Ns - 1);
+            const float2 t = tw[q << (8 - ls)]; // exp(-2 pi j q / (2 Ns))
+            const float2 p = from[j], b = from[j + B / 2];
+            const float2 e = {b.x * t.x - b.y * t.y, b.x * t.y + b.y * t.x};
+            const uint32_t o2 = ((j - q) << 1) + q;
+            to[o2] = float2{p.x + e.x, p.y + e.y};
+            to[o2 + Ns] = float2{p.x - e.x, p.y - e.y};
+        }
+        wave_sync();
+    }
+}
+
+// One row into the segment's bins, by all kAsmThreads threads: thread t takes the table's items t, t + 256, ..., which are
+// different bins (R B <= N).  Z: the row's B-point transform, c: its nearest bin
+__device__ __forceinline__ void fft_duc_add_body(float2* S, const float2* Z, const float2* __restrict__ Gk, uint32_t c, uint32_t B,
+                                                 uint32_t RB, uint32_t tid)
+{
+    const uint32_t bin0 = c + static_cast<uint32_t>(kN) - RB / 2; // bin of the table's item 0, before the wrap
+    for (uint32_t t = tid; t < RB; t += kAsmThreads) {
+        const uint32_t b = (bin0 + t) & (kN - 1);
+        const float2 g = Gk[t], z = Z[b & (B - 1)];
+        float2 s = S[b];
+        s.x += g.x * z.x - g.y * z.y;
+        s.y += g.x * z.y + g.y * z.x;
+        S[b] = s;
+    }
+}
+
 // blockIdx.x: the segment of the launch; kAsmThreads threads; dynamic LDS: tw[256] | S[2048] | per wave two buffers of B
 // items
 __global__ __launch_bounds__(kAsmThreads) void k_fft_duc_assemble(AsmArgs a)
@@ -107,60 +175,108 @@ __global__ __launch_bounds__(kAsmThreads) void k_fft_duc_assemble(AsmArgs a)
 
     for (uint32_t k0 = 0; k0 < a.K; k0 += kAsmWaves) {
         const uint32_t k = k0 + wave;
-        if (k < a.K) { // uniform over the wave, which works in its own two buffers up to the barrier below
-            const uint32_t wk = a.w[k];
-            const float2* hist = a.hist + static_cast<size_t>(k) * a.H;
-            const float2* in = a.in + static_cast<size_t>(k) * a.in_stride;
-            for (uint32_t n = lane; n < B; n += 64) {
-                const size_t v = v0 + n;
-                const float2 x = v < a.H ? hist[v] : in[v - a.H];
-                float2 z = {0.0f, 0.0f};
-                cmac(z, mixer<1>(wk, i0 + n * a.I), x);
-                mine[n] = z;
-            }
-            wave_sync();
-            // stage of sub-transform length Ns: butterfly j takes items j and j + B / 2, position q = j mod Ns of its
-            // sub-transform, and writes items (j - q) 2 + q and Ns later.  Natural order in, natural order out
-            for (uint32_t ls = 0; ls < a.logB; ++ls) {
-                const uint32_t Ns = 1u << ls;
-                const float2* from = mine + (ls & 1) * B;
-                float2* to = mine + ((ls & 1) ^ 1) * B;
-                for (uint32_t j = lane; j < B / 2; j += 64) {
-                    const uint32_t q = j & (Ns - 1);
-                    const float2 t = tw[q << (8 - ls)]; // exp(-2 pi j q / (2 Ns))
-                    const float2 p = from[j], b = from[j + B / 2];
-                    const float2 e = {b.x * t.x - b.y * t.y, b.x * t.y + b.y * t.x};
-                    const uint32_t o2 = ((j - q) << 1) + q;
-                    to[o2] = float2{p.x + e.x, p.y + e.y};
-                    to[o2 + Ns] = float2{p.x - e.x, p.y - e.y};
-                }
-                wave_sync();
-            }
-        }
+        if (k < a.K) // uniform over the wave, which works in its own two buffers up to the barrier below
+            fft_duc_row_body(mine, tw, a.hist + static_cast<size_t>(k) * a.H, a.H, a.in + static_cast<size_t>(k) * a.in_stride, v0,
+                             a.w[k], i0, a.I, a.logB, lane);
         __syncthreads();
 
-        // the group's channels into the segment's bins, k ascending: thread t takes the table's items t, t + 256, ..., which
-        // are different bins; the barrier orders a bin's channels
+        // the group's channels into the segment's bins, k ascending; the barrier orders a bin's channels
         const uint32_t gc = a.K - k0 < kAsmWaves ? a.K - k0 : kAsmWaves;
         for (uint32_t kk = 0; kk < gc; ++kk) {
-            const uint32_t c = fft_ddc_bin(a.w[k0 + kk]);
-            const float2* Z = bufs + (kk * 2 + src) * B;
-            const float2* __restrict__ Gk = a.G + static_cast<size_t>(k0 + kk) * RB;
-            const uint32_t bin0 = c + static_cast<uint32_t>(kN) - RB / 2; // bin of the table's item 0, before the wrap
-            for (uint32_t t = tid; t < RB; t += kAsmThreads) {
-                const uint32_t b = (bin0 + t) & (kN - 1);
-                const float2 g = Gk[t], z = Z[b & (B - 1)];
-                float2 s = S[b];
-                s.x += g.x * z.x - g.y * z.y;
-                s.y += g.x * z.y + g.y * z.x;
-                S[b] = s;
-            }
+            fft_duc_add_body(S, bufs + (kk * 2 + src) * B, a.G + static_cast<size_t>(k0 + kk) * RB, fft_ddc_bin(a.w[k0 + kk]), B, RB,
+                             tid);
             __syncthreads(); // behind the last channel: the buffers take the next group
         }
     }
 
     float2* o = a.spec + static_cast<size_t>(seg) * kN;
     for (uint32_t b = tid; b < kN; b += kAsmThreads) o[b] = S[b];
+}
+
+// a row of the MixedFftDuc, fixed at create
+struct MixedRow {
+    uint32_t w;        // frequency word
+    uint32_t logB;     // log2 B_k
+    uint32_t I;        // I_k = N / B_k
+    uint32_t R;        // images
+    uint32_t g_off;    // the row's table in G
+    uint32_t hist_off; // the row's carried items in hist
+};
+
+struct MixedAsmArgs {
+    const float2* hist;   // row k's H_k carried items at hist + rows[k].hist_off
+    const float2* in;     // row k at in + k in_stride
+    size_t in_stride;
+    size_t seg0;          // the launch's first segment, counted from the call's
+    const float2* G;
+    const float2* tw;     // [256]
+    const MixedRow* rows; // [K]
+    float2* spec;         // [segments of the launch][2048]
+    uint32_t index0;      // absolute index of the first output sample of the launch's first segment (its low 32 bits)
+    uint32_t K, Bmax;
+    uint32_t carried;     // V + pending Imax: the output samples the carried items stand for; H_k = carried / I_k
+    uint32_t hop;         // hop / I_k items of row k complete a segment
+};
+
+// The assembling kernel with a descriptor per row.  blockIdx.x: the segment of the launch; kAsmThreads threads; dynamic
+// LDS: tw[256] | S[2048] | per wave two buffers of Bmax items, of which row k uses the first 2 B_k.  The waves of a group run
+// log2 B_k stages each, synchronised per wave; every __syncthreads below is outside the `k < K` branch and inside loops
+// whose bounds (K, gc) are the same for all four waves, so all of them reach each one.  H_k and hop / I_k come from the two
+// launch constants by a shift, so the table is written once, at create.
+__global__ __launch_bounds__(kAsmThreads) void k_fft_duc_mixed_assemble(MixedAsmArgs a)
+{
+    extern __shared__ float2 s_fft_duc[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float2* tw = s_fft_duc;
+    float2* S = s_fft_duc + kTwiddles;
+    float2* bufs = S + kN;
+    float2* mine = bufs + wave * 2 * a.Bmax;
+    for (uint32_t m = tid; m < kTwiddles; m += kAsmThreads) tw[m] = a.tw[m];
+    for (uint32_t b = tid; b < kN; b += kAsmThreads) S[b] = float2{0.0f, 0.0f};
+    __syncthreads();
+
+    const uint32_t seg = blockIdx.x;
+    const uint32_t i0 = a.index0 + seg * a.hop;
+
+    for (uint32_t k0 = 0; k0 < a.K; k0 += kAsmWaves) {
+        const uint32_t k = k0 + wave;
+        if (k < a.K) { // uniform over the wave
+            const MixedRow r = a.rows[k];
+            const uint32_t logI = 11 - r.logB;
+            const size_t H = a.carried >> logI;
+            const size_t v0 = (a.seg0 + seg) * (a.hop >> logI);
+            fft_duc_row_body(mine, tw, a.hist + r.hist_off, H, a.in + static_cast<size_t>(k) * a.in_stride, v0, r.w, i0, r.I, r.logB,
+                             lane);
+        }
+        __syncthreads();
+
+        const uint32_t gc = a.K - k0 < kAsmWaves ? a.K - k0 : kAsmWaves;
+        for (uint32_t kk = 0; kk < gc; ++kk) {
+            const MixedRow r = a.rows[k0 + kk];
+            const uint32_t B = 1u << r.logB;
+            fft_duc_add_body(S, bufs + kk * 2 * a.Bmax + (r.logB & 1) * B, a.G + r.g_off, fft_ddc_bin(r.w), B, r.R << r.logB, tid);
+            __syncthreads(); // behind the last row: the buffers take the next group
+        }
+    }
+
+    float2* o = a.spec + static_cast<size_t>(seg) * kN;
+    for (uint32_t b = tid; b < kN; b += kAsmThreads) o[b] = S[b];
+}
+
+// blockIdx.y: the row.  Its virtual stream is hist[0 .. H_k) ++ in[0 .. n_k) with H_k = carried / I_k, n_k = taken / I_k
+// (taken: the call's slots in output samples); the last H_k' = carried_new / I_k items of it go to hist_new
+__global__ __launch_bounds__(256) void k_fft_duc_mixed_history(const float2* hist, const float2* in, size_t in_stride,
+                                                               const MixedRow* rows, uint32_t carried, size_t taken,
+                                                               uint32_t carried_new, float2* hist_new)
+{
+    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x, k = blockIdx.y;
+    const MixedRow r = rows[k];
+    const uint32_t logI = 11 - r.logB;
+    const size_t H = carried >> logI, n = taken >> logI, H_new = carried_new >> logI;
+    if (i >= H_new) return;
+    const size_t v = H + n - H_new + i;
+    hist_new[r.hist_off + i] = v < H ? hist[r.hist_off + v] : in[k * in_stride + (v - H)];
 }
 
 struct InvArgs {
@@ -263,6 +379,69 @@ gr4pm_status check_items(size_t n_in)
     return GR4PM_OK;
 }
 
+// max_ratio: the items per slot of the MixedFftDuc's longest row
+gr4pm_status check_slots(size_t slots, uint32_t max_ratio)
+{
+    if (!fft_duc_mixed_slots_fit(slots, max_ratio)) {
+        set_error("fft_duc_mixed: %zu slots of %u items in the longest row in one call, at most 2^40 items", slots, max_ratio);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    return GR4PM_OK;
+}
+
+// what a handle of either kind needs for its transforms, whatever its rows: the inverse kernel's tables and wave count,
+// the assembling kernel's twiddles and the buffer of spectra.  The host vectors live until the create's wait
+struct TransformTables {
+    std::vector<float4> tT;
+    std::vector<cf> cc;
+    std::vector<float2> tw;
+};
+
+template <typename Handle>
+gr4pm_status transform_tables(Handle& h, TransformTables& t)
+{
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        h.max_waves = std::min(h.max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
+    t.tT.resize(kW64TwFloat4);
+    t.cc.resize(64);
+    build_w64_tables(
+        [](int k) {
+            const double ang = -2.0 * M_PI * k / kFftN;
+            return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
+        },
+        t.tT.data(), t.cc.data());
+    t.tw.resize(kTwiddles);
+    for (int m = 0; m < kTwiddles; ++m) {
+        double cs, sn;
+        unit_phasor(0u - (static_cast<uint32_t>(m) << 23), cs, sn); // -m / 512 of a turn
+        t.tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
+    }
+    GR4PM_TRY(h.d_tT.alloc(t.tT.size()));
+    GR4PM_TRY(h.d_cc.alloc(t.cc.size()));
+    GR4PM_TRY(h.d_tw.alloc(t.tw.size()));
+    GR4PM_TRY(h.d_spec.alloc(kChunk * kN));
+    GR4PM_TRY(h.d_tT.upload(t.tT.data(), t.tT.size(), h.stream));
+    GR4PM_TRY(h.d_cc.upload(t.cc.data(), t.cc.size(), h.stream));
+    GR4PM_TRY(h.d_tw.upload(t.tw.data(), t.tw.size(), h.stream));
+    return GR4PM_OK;
+}
+
+// the inverse transforms of the `segs` spectra of a launch pair, the call's segments from `done` on
+template <typename Handle>
+void launch_inverse(const Handle& h, InvArgs b, size_t done, size_t segs)
+{
+    const size_t per_wave = (segs + h.max_waves - 1) / h.max_waves;
+    const size_t waves = (segs + per_wave - 1) / per_wave;
+    b.seg0 = done, b.n_seg = static_cast<uint32_t>(segs), b.run = static_cast<uint32_t>(per_wave);
+    hipLaunchKernelGGL(k_fft_duc_inverse, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)), dim3(kW64Threads), 0, h.stream,
+                       b);
+}
+
+// dynamic LDS of k_fft_duc_mixed_assemble
+size_t mixed_assemble_lds(size_t Bmax) { return (kTwiddles + kN + kAsmWaves * 2 * Bmax) * sizeof(float2); }
+
 } // namespace
 
 struct gr4pm_fft_duc {
@@ -278,6 +457,24 @@ struct gr4pm_fft_duc {
     gr4pm::DevBuf<cf> d_cc, d_spec;
     gr4pm::DevBuf<float2> d_tw, d_G;
     gr4pm::DevBuf<uint32_t> d_w;
+};
+
+struct gr4pm_fft_duc_mixed {
+    size_t K = 0, Imax = 0, V = 0, Bmax = 0;
+    uint32_t max_ratio = 1; // Imax / min I_k: items per slot of the longest row
+    uint64_t start_index = 0;
+    uint64_t taken = 0; // slots since create or reset
+    FftDucShape shape = {}; // of Imax: its items are slots
+    hipStream_t stream = nullptr;
+    size_t max_waves = 2048;
+    std::vector<uint32_t> words;
+    std::vector<FftDucMixedRow> rows;
+    int cur = 0; // which buffer holds the carried items
+    gr4pm::DevBuf<float2> d_hist[2];
+    gr4pm::DevBuf<float4> d_tT;
+    gr4pm::DevBuf<cf> d_cc, d_spec;
+    gr4pm::DevBuf<float2> d_tw, d_G;
+    gr4pm::DevBuf<MixedRow> d_rows;
 };
 
 extern "C" {
@@ -343,24 +540,8 @@ try {
     h->shape = fft_duc_shape(static_cast<uint32_t>(I), static_cast<uint32_t>(V));
     h->stream = static_cast<hipStream_t>(p->stream);
     h->words = std::move(words);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        h->max_waves = std::min(h->max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
-    std::vector<float4> tT(kW64TwFloat4);
-    std::vector<cf> cc(64);
-    build_w64_tables(
-        [](int k) {
-            const double ang = -2.0 * M_PI * k / kFftN;
-            return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
-        },
-        tT.data(), cc.data());
-    std::vector<float2> tw(kTwiddles);
-    for (int m = 0; m < kTwiddles; ++m) {
-        double cs, sn;
-        unit_phasor(0u - (static_cast<uint32_t>(m) << 23), cs, sn); // -m / 512 of a turn
-        tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
-    }
+    TransformTables tables;
+    GR4PM_TRY(transform_tables(*h, tables));
     const size_t B = kN / I, RB = R * B;
     std::vector<float2> G(K * RB);
     for (size_t k = 0; k < K; ++k) {
@@ -368,15 +549,8 @@ try {
         const double gain = p->gains ? p->gains[k] : 1.0;
         for (size_t t = 0; t < RB; ++t) G[k * RB + t] = response(taps, gain, w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
     }
-    GR4PM_TRY(h->d_tT.alloc(tT.size()));
-    GR4PM_TRY(h->d_cc.alloc(cc.size()));
-    GR4PM_TRY(h->d_tw.alloc(tw.size()));
-    GR4PM_TRY(h->d_spec.alloc(kChunk * kN));
     GR4PM_TRY(h->d_G.alloc(G.size()));
     GR4PM_TRY(h->d_w.alloc(K));
-    GR4PM_TRY(h->d_tT.upload(tT.data(), tT.size(), h->stream));
-    GR4PM_TRY(h->d_cc.upload(cc.data(), cc.size(), h->stream));
-    GR4PM_TRY(h->d_tw.upload(tw.data(), tw.size(), h->stream));
     GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
     GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
     GR4PM_TRY(h->tail.alloc(h->shape.keep, h->shape.hop_items, K, h->stream));
@@ -470,17 +644,246 @@ try {
         a.seg0 = done;
         a.index0 = static_cast<uint32_t>(fft_duc_item_index(h->shape, h->start_index, p.segments_before + done));
         hipLaunchKernelGGL(k_fft_duc_assemble, dim3(static_cast<unsigned>(segs)), dim3(kAsmThreads), lds, h->stream, a);
-        const size_t per_wave = (segs + h->max_waves - 1) / h->max_waves;
-        const size_t waves = (segs + per_wave - 1) / per_wave;
-        b.seg0 = done, b.n_seg = static_cast<uint32_t>(segs), b.run = static_cast<uint32_t>(per_wave);
-        hipLaunchKernelGGL(k_fft_duc_inverse, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)), dim3(kW64Threads), 0,
-                           h->stream, b);
+        launch_inverse(*h, b, done, segs);
         done += segs;
     }
     h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
     GR4PM_HIP_TRY(hipGetLastError());
     h->tail.commit(t);
     h->taken += n_in;
+    *n_out = p.samples;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+// ---- MixedFftDuc: an interpolation per row ------------------------------------------------------
+
+gr4pm_status gr4pm_fft_duc_mixed_create(const gr4pm_fft_duc_mixed_params* p, gr4pm_fft_duc_mixed** out)
+try {
+    if (!p || !out) return GR4PM_ERR_INVALID;
+    *out = nullptr;
+    const size_t K = p->n_channels;
+    std::vector<uint32_t> words;
+    GR4PM_TRY(frequency_words("fft_duc_mixed", p->frequencies, K, kFftDucMaxK, words));
+    if (!p->interpolations) {
+        set_error("fft_duc_mixed: no interpolations");
+        return GR4PM_ERR_INVALID;
+    }
+    if ((p->taps == nullptr) != (p->n_taps == nullptr)) {
+        set_error("fft_duc_mixed: taps and n_taps come together or not at all");
+        return GR4PM_ERR_INVALID;
+    }
+    GR4PM_TRY(finite_gains("fft_duc_mixed", p->gains, K));
+    const std::vector<size_t> I(p->interpolations, p->interpolations + K);
+    const std::vector<size_t> R = p->images ? std::vector<size_t>(p->images, p->images + K) : std::vector<size_t>(K, 2);
+    std::vector<size_t> L(K);
+    for (size_t k = 0; k < K; ++k) {
+        if (!fft_ddc_pow2(I[k]) || I[k] < kFftDucMinI || I[k] > kFftDucMaxI) {
+            set_error("fft_duc_mixed: interpolations[%zu] must be a power of two in [%u, %u], not %zu", k, kFftDucMinI, kFftDucMaxI, I[k]);
+            return GR4PM_ERR_INVALID;
+        }
+        if (p->taps) {
+            GR4PM_TRY(prototype_length("fft_duc_mixed", p->taps, p->n_taps[k], kN));
+            L[k] = p->n_taps[k];
+        } else {
+            if (p->taps_per_phase < 1 || p->taps_per_phase * I[k] > kN) {
+                set_error("fft_duc_mixed: %zu taps per phase at an interpolation of %zu: the prototype has 1 .. %zu taps", p->taps_per_phase,
+                          I[k], kN);
+                return GR4PM_ERR_INVALID;
+            }
+            L[k] = p->taps_per_phase * I[k];
+        }
+    }
+    const FftDucMixedVerdict sizes = fft_duc_mixed_validate_channels(K, I.data(), R.data(), L.data());
+    if (sizes.refusal == FftDucMixedRefusal::images) {
+        set_error("fft_duc_mixed: images[%zu] must be a power of two in [1, %zu], not %zu", sizes.channel, I[sizes.channel], R[sizes.channel]);
+        return GR4PM_ERR_INVALID;
+    }
+    if (sizes.refusal != FftDucMixedRefusal::none) {
+        set_error("fft_duc_mixed: invalid sizes of row %zu", sizes.channel);
+        return GR4PM_ERR_INVALID;
+    }
+    std::vector<std::vector<float>> taps(K);
+    for (size_t k = 0, at = 0; k < K; at += L[k], ++k) {
+        if (p->taps) {
+            taps[k].assign(p->taps + at, p->taps + at + L[k]);
+        } else {
+            taps[k].resize(L[k]);
+            GR4PM_TRY(gr4pm_duc_taps(I[k], p->taps_per_phase, 0.25, 0.75, taps[k].data()));
+        }
+        for (size_t t = 0; t < L[k]; ++t)
+            if (!std::isfinite(taps[k][t])) {
+                set_error("fft_duc_mixed: taps[%zu] of row %zu is not finite", t, k);
+                return GR4PM_ERR_INVALID;
+            }
+    }
+    const size_t Imax = fft_duc_mixed_max_interpolation(K, I.data());
+    const size_t V = p->overlap < 0 ? fft_duc_mixed_default_overlap(K, L.data()) : static_cast<size_t>(p->overlap);
+    const FftDucMixedVerdict v = fft_duc_mixed_validate(K, I.data(), R.data(), L.data(), V);
+    switch (v.refusal) {
+    case FftDucMixedRefusal::none: break;
+    case FftDucMixedRefusal::overlap_multiple:
+        set_error("fft_duc_mixed: the overlap %zu is no multiple of the largest interpolation %zu", V, Imax);
+        return GR4PM_ERR_INVALID;
+    case FftDucMixedRefusal::overlap_low:
+        set_error("fft_duc_mixed: the overlap %zu is below the reach of row %zu: its %zu taps need %zu", V, v.channel, L[v.channel],
+                  L[v.channel] - 1);
+        return GR4PM_ERR_INVALID;
+    case FftDucMixedRefusal::overlap_high:
+        set_error("fft_duc_mixed: the overlap %zu leaves a hop below %u: at most %zu", V, kFftDucMinHop, kN - kFftDucMinHop);
+        return GR4PM_ERR_INVALID;
+    default: set_error("fft_duc_mixed: invalid sizes"); return GR4PM_ERR_INVALID;
+    }
+    GR4PM_TRY(require_device());
+    std::unique_ptr<gr4pm_fft_duc_mixed> h(new (std::nothrow) gr4pm_fft_duc_mixed);
+    if (!h) return GR4PM_ERR_NOMEM;
+    h->K = K, h->Imax = Imax, h->V = V;
+    h->start_index = p->start_index;
+    h->shape = fft_duc_shape(static_cast<uint32_t>(Imax), static_cast<uint32_t>(V));
+    h->stream = static_cast<hipStream_t>(p->stream);
+    h->words = std::move(words);
+    TransformTables tables;
+    GR4PM_TRY(transform_tables(*h, tables));
+    std::vector<size_t> g_off(K), hist_off(K);
+    std::vector<float2> G(fft_duc_mixed_table_offsets(K, I.data(), R.data(), g_off.data()));
+    const size_t hist_items = fft_duc_mixed_carried_offsets(K, I.data(), hist_off.data());
+    std::vector<MixedRow> rows(K);
+    h->rows.resize(K);
+    for (size_t k = 0; k < K; ++k) {
+        const uint32_t w = h->words[k], c = fft_ddc_bin(w);
+        const double gain = p->gains ? p->gains[k] : 1.0;
+        const size_t B = kN / I[k], RB = R[k] * B;
+        for (size_t t = 0; t < RB; ++t)
+            G[g_off[k] + t] = response(taps[k], gain, w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
+        h->rows[k] = fft_duc_mixed_row(static_cast<uint32_t>(Imax), static_cast<uint32_t>(V), static_cast<uint32_t>(I[k]));
+        h->max_ratio = std::max(h->max_ratio, h->rows[k].ratio);
+        h->Bmax = std::max(h->Bmax, B);
+        rows[k] = MixedRow{w, static_cast<uint32_t>(__builtin_ctzll(B)), static_cast<uint32_t>(I[k]), static_cast<uint32_t>(R[k]),
+                           static_cast<uint32_t>(g_off[k]), static_cast<uint32_t>(hist_off[k])};
+    }
+    GR4PM_TRY(h->d_G.alloc(G.size()));
+    GR4PM_TRY(h->d_rows.alloc(K));
+    GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
+    GR4PM_TRY(h->d_rows.upload(rows.data(), K, h->stream));
+    for (auto& d : h->d_hist) {
+        GR4PM_TRY(d.alloc(hist_items));
+        GR4PM_TRY(d.zero(h->stream));
+    }
+    if (mixed_assemble_lds(h->Bmax) > 48 * 1024) // Bmax = 512
+        GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_fft_duc_mixed_assemble)}, mixed_assemble_lds(h->Bmax), "fft_duc_mixed"));
+    return finish_create(h, out, "fft_duc_mixed"); // waits for the stream: the uploads read this function's vectors
+}
+GR4PM_ABI_CATCH
+
+void gr4pm_fft_duc_mixed_destroy(gr4pm_fft_duc_mixed* h)
+try {
+    if (!h) return;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+GR4PM_ABI_CATCH_VOID
+
+gr4pm_status gr4pm_fft_duc_mixed_reset(gr4pm_fft_duc_mixed* h)
+try {
+    if (!h) return GR4PM_ERR_INVALID;
+    GR4PM_TRY(h->d_hist[h->cur].zero(h->stream));
+    h->taken = 0;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_items_for(const gr4pm_fft_duc_mixed* h, size_t slots, size_t* items)
+try {
+    if (!h || !items) return GR4PM_ERR_INVALID;
+    for (size_t k = 0; k < h->K; ++k) items[k] = 0;
+    GR4PM_TRY(check_slots(slots, h->max_ratio));
+    for (size_t k = 0; k < h->K; ++k) items[k] = fft_duc_mixed_items(h->rows[k], slots);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_output_items(const gr4pm_fft_duc_mixed* h, size_t slots, size_t* n_out)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    GR4PM_TRY(check_slots(slots, h->max_ratio));
+    *n_out = fft_duc_plan(h->shape, h->taken, slots).samples;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_frequencies(const gr4pm_fft_duc_mixed* h, double* out)
+try {
+    if (!h || !out) return GR4PM_ERR_INVALID;
+    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_sizes(const gr4pm_fft_duc_mixed* h, size_t* overlap, size_t* hop)
+try {
+    if (!h || !overlap || !hop) return GR4PM_ERR_INVALID;
+    *overlap = h->V;
+    *hop = h->shape.hop;
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_pending(const gr4pm_fft_duc_mixed* h, size_t* slots)
+try {
+    if (!h || !slots) return GR4PM_ERR_INVALID;
+    *slots = static_cast<size_t>(h->taken % h->shape.hop_items);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_process(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, gr4pm_c64* out,
+                                         size_t out_cap, size_t* n_out)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    GR4PM_TRY(check_slots(slots, h->max_ratio));
+    if (slots == 0) return GR4PM_OK;
+    const FftDucPlan p = fft_duc_plan(h->shape, h->taken, slots); // in slots: a row's items are its ratio times these
+    if (p.samples > out_cap) {
+        set_error("fft_duc_mixed: %zu samples, room for %zu", p.samples, out_cap);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    const size_t longest = slots * h->max_ratio;
+    if (!in || (p.samples && !out) || (h->K > 1 && in_stride < longest)) {
+        set_error("fft_duc_mixed: no input or output array, or a row stride of %zu items for %zu items", in_stride, longest);
+        return GR4PM_ERR_INVALID;
+    }
+    const float2* hist = h->d_hist[h->cur].p;
+    float2* hist_new = h->d_hist[1 - h->cur].p;
+    const uint32_t Imax = static_cast<uint32_t>(h->Imax);
+    MixedAsmArgs a = {};
+    a.hist = hist, a.in = reinterpret_cast<const float2*>(in), a.in_stride = in_stride;
+    a.G = h->d_G.p, a.tw = h->d_tw.p, a.rows = h->d_rows.p, a.spec = reinterpret_cast<float2*>(h->d_spec.p);
+    a.K = static_cast<uint32_t>(h->K), a.Bmax = static_cast<uint32_t>(h->Bmax);
+    a.carried = static_cast<uint32_t>(p.carried) * Imax, a.hop = h->shape.hop;
+    InvArgs b = {};
+    b.spec = h->d_spec.p, b.tT = h->d_tT.p, b.cc = h->d_cc.p, b.out = reinterpret_cast<cf*>(out);
+    b.hop = h->shape.hop, b.V = static_cast<uint32_t>(h->V);
+    const size_t lds = mixed_assemble_lds(h->Bmax);
+    for (size_t done = 0; done < p.n_segments;) {
+        const size_t segs = std::min(p.n_segments - done, kChunk);
+        a.seg0 = done;
+        a.index0 = static_cast<uint32_t>(fft_duc_item_index(h->shape, h->start_index, p.segments_before + done));
+        hipLaunchKernelGGL(k_fft_duc_mixed_assemble, dim3(static_cast<unsigned>(segs)), dim3(kAsmThreads), lds, h->stream, a);
+        launch_inverse(*h, b, done, segs);
+        done += segs;
+    }
+    // the rows' new carried items into the other buffer, p.left slots' worth each (nothing left: no launch, no swap)
+    const uint32_t carried_new = static_cast<uint32_t>(p.left) * Imax;
+    if (carried_new) {
+        const size_t most = static_cast<size_t>(carried_new) * h->max_ratio / Imax; // the longest row's
+        hipLaunchKernelGGL(k_fft_duc_mixed_history, dim3(static_cast<unsigned>((most + 255) / 256), static_cast<unsigned>(h->K)), dim3(256),
+                           0, h->stream, hist, a.in, in_stride, h->d_rows.p, a.carried, slots * h->Imax, carried_new, hist_new);
+    }
+    GR4PM_HIP_TRY(hipGetLastError());
+    if (carried_new) h->cur = 1 - h->cur;
+    h->taken += slots;
     *n_out = p.samples;
     return GR4PM_OK;
 }

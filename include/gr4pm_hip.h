@@ -1810,6 +1810,62 @@ gr4pm_status gr4pm_fft_duc_pending(const gr4pm_fft_duc* h, size_t* items);
 gr4pm_status gr4pm_fft_duc_process(gr4pm_fft_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
                                    size_t out_cap, size_t* n_out);
 
+/* ---- MixedFftDuc: an interpolation per row into one shared transform (the project's own block) --
+ * The FftDuc with its restriction to one interpolation lifted: carriers of different symbol rates onto one stream in one
+ * pass.  N = 2048, K rows (1 .. 64); row k has a frequency f_k, I_k a power of two in 4 .. 64, B_k = N / I_k, a real finite
+ * gain a_k, a real finite prototype h_k[0 .. L_k - 1] and R_k images, a power of two with 1 <= R_k <= I_k.  Imax = max
+ * I_k.  One overlap V for the handle with Imax | V, V <= N - 64 and V >= L_k - 1 for every k (overlap < 0: the smallest
+ * multiple of 256 that is >= max_k (L_k - 1)), hop = N - V.  Row k's item m sits at output sample m I_k; all rows start
+ * at output sample 0, and v_k[m] = 0 for m < 0.
+ *     w_k, c_k, G_k[u]: the FftDuc's with h_k, a_k, B_k, R_k in the place of h, a_k, B, R
+ *     z_k[m] = exp(+2 pi j ((w_k (start_index + m I_k)) mod 2^32) / 2^32) v_k[m]
+ *     segment s: the output samples a_s .. a_s + N - 1, a_s = s hop - V; row k's items m = a_s / I_k + n', n' < B_k
+ *     Z_k[v] = the B_k-point forward transform of those items
+ *     S_s[b] = sum_k G_k[u] Z_k[b mod B_k],  b = (c_k + u) mod N   (one accumulator per bin, from zero, k ascending)
+ *     x_s = the inverse N-point transform of S_s;  p = V .. N - 1 are kept:  out[s hop + p - V] = x_s[p]
+ * With R_k = I_k the output is sum_k Duc([f_k], I_k, taps = h_k, gains = [a_k])(v_k) in exact arithmetic; with all I_k
+ * equal the block is the FftDuc, bit for bit.  The handle counts in slots of Imax output samples: a call of u slots takes
+ * u Imax / I_k items of row k and delivers the whole segments they complete; it carries (V + pending Imax) / I_k < B_k
+ * items of row k, and any cutting into calls gives the same bits. */
+typedef struct gr4pm_fft_duc_mixed gr4pm_fft_duc_mixed;
+typedef struct {
+    size_t n_channels;            /* K: 1 .. 64 */
+    const size_t* interpolations; /* HOST, K items: I_k, powers of two, 4 .. 64 */
+    const double* frequencies;    /* HOST, K items, cycles per output sample, finite */
+    const double* gains;          /* HOST, K items, finite; NULL: all 1 */
+    const float* taps;            /* HOST, the K prototypes behind one another, finite; NULL together with n_taps:
+                                     gr4pm_fft_duc_taps(I_k, taps_per_phase) per row */
+    const size_t* n_taps;         /* HOST, K items: L_k */
+    size_t taps_per_phase;        /* of the design when taps is NULL */
+    const size_t* images;         /* HOST, K items: R_k; NULL: 2 each */
+    int64_t overlap;              /* V; negative: the default */
+    uint64_t start_index;
+    void* stream;                 /* hipStream_t */
+} gr4pm_fft_duc_mixed_params;
+/* Refused with GR4PM_ERR_INVALID and no handle: K out of range, a NULL or non-finite frequency, no interpolations, a
+ * non-finite gain, taps without n_taps or the reverse, an I_k or R_k no power of two or out of range, a non-finite tap, an
+ * L_k out of range, V no multiple of Imax, above N - 64, or below L_k - 1 for a row k. */
+gr4pm_status gr4pm_fft_duc_mixed_create(const gr4pm_fft_duc_mixed_params* params, gr4pm_fft_duc_mixed** out);
+void gr4pm_fft_duc_mixed_destroy(gr4pm_fft_duc_mixed* h);
+/* back to start_index: zero prehistory, nothing carried */
+gr4pm_status gr4pm_fft_duc_mixed_reset(gr4pm_fft_duc_mixed* h);
+/* items: HOST, K items: the items of each row a call of `slots` slots takes, slots Imax / I_k */
+gr4pm_status gr4pm_fft_duc_mixed_items_for(const gr4pm_fft_duc_mixed* h, size_t slots, size_t* items);
+/* samples the next call of `slots` slots delivers */
+gr4pm_status gr4pm_fft_duc_mixed_output_items(const gr4pm_fft_duc_mixed* h, size_t slots, size_t* n_out);
+/* out: HOST, K items: w_k / 2^32 folded to [-0.5, 0.5) */
+gr4pm_status gr4pm_fft_duc_mixed_frequencies(const gr4pm_fft_duc_mixed* h, double* out);
+gr4pm_status gr4pm_fft_duc_mixed_sizes(const gr4pm_fft_duc_mixed* h, size_t* overlap, size_t* hop);
+/* slots taken but not yet in a delivered segment: taken mod (hop / Imax) */
+gr4pm_status gr4pm_fft_duc_mixed_pending(const gr4pm_fft_duc_mixed* h, size_t* slots);
+/* in: DEVICE, K rows in_stride items apart, slots Imax / I_k items in row k.  out: DEVICE, room for out_cap samples.
+ * Enqueues on the handle's stream, reads nothing back and does not wait.  Refused with gr4pm_last_error set, *n_out = 0
+ * and nothing enqueued: a NULL in with slots > 0, a NULL out when the call delivers samples, in_stride below the longest
+ * row's items with K > 1 (GR4PM_ERR_INVALID); more than 2^40 items in the longest row or fewer than the samples of room
+ * (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
+gr4pm_status gr4pm_fft_duc_mixed_process(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, gr4pm_c64* out,
+                                         size_t out_cap, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,10 @@ BUDGETS = [
     # which stores part of its result (187 registers as built, two waves per SIMD by its LDS)
     (r"k_fft_duc_assemble", dict(vgpr=80, lds=0, lds_exact=True, scratch=0)),
     (r"k_fft_duc_inverse", dict(vgpr=192, lds=151552, lds_exact=True, scratch=0)),
+    # the MixedFftDuc block: the same wave bodies with a row's sizes from a descriptor (77 registers and 65 SGPRs as built,
+    # six waves per SIMD like the uniform kernel; dynamic LDS sized by the largest B of the handle, at most 50 KiB) (DESIGN
+    # section 28)
+    (r"k_fft_duc_mixed_assemble", dict(vgpr=80, lds=0, lds_exact=True, scratch=0)),
     # the Spectrogram block: the same LDS image, 32 accumulators where the Spectrum has 64, two waves per SIMD (DESIGN
     # section 21)
     (r"k_spectrogram_w64ILi", dict(vgpr=256, lds=159744, lds_exact=True, scratch=0)),
