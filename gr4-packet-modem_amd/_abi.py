@@ -254,6 +254,11 @@ class RowResamplerParams(C.Structure):
     _fields_ = [("phases", C.c_uint32), ("taps_per_phase", C.c_uint32), ("taps", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class RowStreamParams(C.Structure):
+    _fields_ = [("phases", C.c_uint32), ("taps_per_phase", C.c_uint32), ("taps", C.c_void_p), ("n_rows", C.c_size_t),
+                ("rows", C.c_void_p), ("start_index", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class FftDdcParams(C.Structure):
     _fields_ = [("n_channels", C.c_size_t), ("decimation", C.c_size_t), ("frequencies", C.c_void_p), ("taps", C.c_void_p),
                 ("n_taps", C.c_size_t), ("taps_per_phase", C.c_size_t), ("overlap", C.c_int64), ("images", C.c_size_t),
@@ -375,6 +380,8 @@ EXPORTS = [
     "gr4pm_find_line", "gr4pm_simplest_ratio",
     "gr4pm_row_resampler_taps", "gr4pm_row_resampler_create", "gr4pm_row_resampler_destroy",
     "gr4pm_row_resampler_output_lengths", "gr4pm_row_resampler_tile_items", "gr4pm_row_resampler_process",
+    "gr4pm_row_stream_create", "gr4pm_row_stream_destroy", "gr4pm_row_stream_reset", "gr4pm_row_stream_items_for",
+    "gr4pm_row_stream_process", "gr4pm_row_stream_flush", "gr4pm_row_stream_set_row", "gr4pm_row_stream_state",
     "gr4pm_fft_ddc_taps", "gr4pm_fft_ddc_create", "gr4pm_fft_ddc_destroy", "gr4pm_fft_ddc_reset", "gr4pm_fft_ddc_frames_for",
     "gr4pm_fft_ddc_frequencies", "gr4pm_fft_ddc_sizes", "gr4pm_fft_ddc_process", "gr4pm_fft_ddc_process_iq",
     "gr4pm_fft_ddc_mixed_create", "gr4pm_fft_ddc_mixed_destroy", "gr4pm_fft_ddc_mixed_reset", "gr4pm_fft_ddc_mixed_frames_for",
@@ -633,6 +640,15 @@ def lib():
     L.gr4pm_row_resampler_tile_items.argtypes = [sz, C.c_uint64]
     L.gr4pm_row_resampler_tile_items.restype = C.c_uint32
     L.gr4pm_row_resampler_process.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp, sz, sz, vp]
+    L.gr4pm_row_stream_create.argtypes = [C.POINTER(RowStreamParams), C.POINTER(vp)]
+    L.gr4pm_row_stream_destroy.argtypes = [vp]
+    L.gr4pm_row_stream_destroy.restype = None
+    L.gr4pm_row_stream_reset.argtypes = [vp]
+    L.gr4pm_row_stream_items_for.argtypes = [vp, vp, vp]
+    L.gr4pm_row_stream_process.argtypes = [vp, vp, sz, sz, vp, vp, sz, sz, vp]
+    L.gr4pm_row_stream_flush.argtypes = [vp, vp, sz, sz, vp]
+    L.gr4pm_row_stream_set_row.argtypes = [vp, sz, C.c_uint64, C.c_int32]
+    L.gr4pm_row_stream_state.argtypes = [vp, sz, vp, vp]
     L.gr4pm_fft_ddc_taps.argtypes = [sz, sz, vp]
     L.gr4pm_fft_ddc_create.argtypes = [C.POINTER(FftDdcParams), C.POINTER(vp)]
     L.gr4pm_fft_ddc_destroy.argtypes = [vp]

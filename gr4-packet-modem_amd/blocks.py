@@ -3240,6 +3240,221 @@ class RowResampler:
         _destroy(self, "gr4pm_row_resampler_destroy")
 
 
+class StreamRowResampler:
+    """gr4pm_row_stream: the RowResampler as a stream block.  Every row's position, history and phase
+    are carried from call to call, so cutting the rows into calls changes no bit of what comes out, and the rows of
+    MixedFftDdc.process_bulk go to exactly 4 samples per symbol call after call.  steps: one Q32.32 step per row (1 .. 64
+    rows); freqs (None: 0): signed frequency words; phase0 (None: 0): the position of output item 0, below 2^63;
+    start_index (None: 0): the absolute index of the first item each row is given (items in front of it are +0, and
+    output begins with the first item at or behind it).  phases, taps_per_phase, taps, max_step: RowResampler's.  The
+    handle is made at construction and is host only until the first process_rows or flush, which run on the stream that
+    was current at construction: items_for, set_row, set_rate, state and reset work without a GPU."""
+
+    COLUMN_GRAIN = 2048
+
+    def __init__(self, steps, freqs=None, phase0=None, start_index=None, phases=32, taps_per_phase=12, taps=None, max_step=1.0):
+        shape = RowResampler(phases, taps_per_phase, taps, max_step)  # the sizes' and the taps' checks, and the design
+        self.phases, self.taps, self.taps_per_phase, self.delay_items = shape.phases, shape.taps, shape.taps_per_phase, shape.delay_items
+        steps = [int(s) for s in (steps.tolist() if isinstance(steps, np.ndarray) else steps)]
+        self.n_rows = len(steps)
+        if not 1 <= self.n_rows <= 64:
+            raise Gr4pmError(f"StreamRowResampler: {self.n_rows} rows, a handle has 1 .. 64")
+        rec = shape._records(self.n_rows, steps, phase0, freqs)
+        if start_index is None:
+            start_index = [0] * self.n_rows
+        start = [int(v) for v in (start_index.tolist() if isinstance(start_index, np.ndarray) else start_index)]
+        if len(start) != self.n_rows or any(not 0 <= v < 1 << 64 for v in start):
+            raise Gr4pmError(f"StreamRowResampler: start_index holds {self.n_rows} values that fit 64 unsigned bits")
+        self.start_index = np.array(start, dtype=np.uint64)
+        self._steps, self._freqs = [int(v) for v in rec["step"]], [int(v) for v in rec["freq"]]
+        try:
+            stream = _stream_handle()
+        except Gr4pmError:  # no GPU: the host-only calls still work, process_rows and flush report the missing device
+            stream = C.c_void_p()
+        self._stream = stream.value
+        p = _abi.RowStreamParams(self.phases, self.taps_per_phase, _np_ptr(self.taps), self.n_rows, _np_ptr(rec),
+                                 _np_ptr(self.start_index), stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_row_stream_create(C.byref(p), C.byref(self._h)), "StreamRowResampler")
+
+    @classmethod
+    def for_rates(cls, rates, offsets=None, samples_per_symbol=4, **kw):
+        """a handle whose row r has rates[r] symbols per item and offsets[r] (None: 0) cycles per item of residual
+        carrier: step_r = round(2^32 / (samples_per_symbol rates[r])), freq_r = round(offsets[r] 2^32)"""
+        steps = RowResampler.steps_for(rates, samples_per_symbol)
+        freqs = None if offsets is None else [cls._freq_word(d) for d in offsets]
+        return cls(steps, freqs, **kw)
+
+    @staticmethod
+    def _freq_word(offset):
+        return int(round(fractions.Fraction(float(offset)) * (1 << 32)))
+
+    def _lengths(self, lengths, n_cols=None):
+        if lengths is None and n_cols is not None:
+            return np.full(self.n_rows, n_cols, dtype=np.uint64)
+        if lengths is None:
+            raise Gr4pmError("StreamRowResampler: no lengths")
+        lengths = RowResampler._row_lengths(self.n_rows, 0, lengths)
+        if lengths.size != self.n_rows:
+            raise Gr4pmError(f"StreamRowResampler: {lengths.size} lengths for {self.n_rows} rows")
+        return lengths
+
+    def items_for(self, lengths):
+        """what the next process_rows with these lengths would report (numpy int64; host only, changes no state)"""
+        lengths = self._lengths(lengths)
+        out = np.zeros(self.n_rows, dtype=np.uint64)
+        check(lib().gr4pm_row_stream_items_for(self._h, _np_ptr(lengths), _np_ptr(out)), "StreamRowResampler.items_for")
+        return out.astype(np.int64)
+
+    def _columns(self, counts):
+        longest = int(counts.max())
+        return -(-longest // self.COLUMN_GRAIN) * self.COLUMN_GRAIN
+
+    def process_rows(self, x, lengths=None, out=None):
+        """x: a CUDA complex64 tensor [R, n] with contiguous rows (any row stride >= n), the next lengths[r] <= n items of
+        every row (None: n each), the layout MixedFftDdc.process_bulk returns.  Returns (rows, out_lengths): rows is CUDA
+        complex64 [R, columns] with rows[r, :out_lengths[r]] the items row r made in this call and +0 behind them;
+        columns is the smallest multiple of 2048 that holds the longest count, or out's (an optional CUDA complex64
+        [R, columns] tensor with contiguous rows; one that is too short for a row's count is refused, nothing is cut).
+        out_lengths is numpy int64.  Does not wait."""
+        torch = _torch()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
+                x.shape[0] == self.n_rows and (x.shape[1] <= 1 or x.stride(1) == 1) and
+                (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
+            raise TypeError(f"x must be a [{self.n_rows}, n] complex64 CUDA tensor with contiguous rows")
+        n_in = x.shape[1]
+        lengths = self._lengths(lengths, n_in)
+        if out is None:
+            out = _rows_output(None, self.n_rows, self._columns(self.items_for(lengths)), x.device, "StreamRowResampler")
+        else:
+            out = _rows_output(out, self.n_rows, 0, x.device, "StreamRowResampler")
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        n_cols = out.shape[1]
+        stride = x.stride(0) if self.n_rows > 1 else max(n_in, 1)
+        out_stride = out.stride(0) if self.n_rows > 1 else max(n_cols, 1)
+        out_lengths = np.zeros(self.n_rows, dtype=np.uint64)
+        check(lib().gr4pm_row_stream_process(self._h, x.data_ptr() if n_in else None, stride, n_in, _np_ptr(lengths),
+                                             out.data_ptr() if n_cols else None, out_stride, n_cols, _np_ptr(out_lengths)),
+              "StreamRowResampler.process_rows")
+        self._last = x  # the call does not wait: the input lives until the next call
+        return out, out_lengths.astype(np.int64)
+
+    def flush_lengths(self):
+        """the items flush() will make per row (numpy int64; host only): P - 1 items of +0 behind the last one"""
+        return self.items_for(np.full(self.n_rows, self.taps_per_phase - 1, dtype=np.uint64))
+
+    def flush(self, out=None):
+        """the items whose windows run out over +0 behind the rows' last items, as the one-shot block's M_r counts them;
+        then every row is back in its created state with its current step and freq.  Returns (rows, out_lengths) as
+        process_rows does; without out the tensor lives on the current device."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty((self.n_rows, self._columns(self.flush_lengths())), dtype=torch.complex64, device="cuda")
+        else:
+            out = _rows_output(out, self.n_rows, 0, out.device, "StreamRowResampler")
+        n_cols = out.shape[1]
+        out_stride = out.stride(0) if self.n_rows > 1 else max(n_cols, 1)
+        out_lengths = np.zeros(self.n_rows, dtype=np.uint64)
+        check(lib().gr4pm_row_stream_flush(self._h, out.data_ptr() if n_cols else None, out_stride, n_cols, _np_ptr(out_lengths)),
+              "StreamRowResampler.flush")
+        return out, out_lengths.astype(np.int64)
+
+    def reset(self):
+        """every row back to its created state, with its current step and freq; no output"""
+        check(lib().gr4pm_row_stream_reset(self._h), "StreamRowResampler.reset")
+
+    def set_row(self, r, step=None, freq=None):
+        """a new step and / or frequency word for row r from its next output item on: that item's position stays, later
+        ones follow it at the new step, and the phase is continuous there"""
+        r = int(r)
+        if not 0 <= r < self.n_rows:
+            raise Gr4pmError(f"StreamRowResampler: row {r} of {self.n_rows}")
+        step = self._steps[r] if step is None else int(step)
+        freq = self._freqs[r] if freq is None else int(freq)
+        if not (0 <= step < 1 << 64 and -(1 << 31) <= freq < 1 << 31):
+            raise Gr4pmError("StreamRowResampler: step must fit 64 unsigned bits and freq 32 signed bits")
+        check(lib().gr4pm_row_stream_set_row(self._h, r, step, freq), "StreamRowResampler.set_row")
+        self._steps[r], self._freqs[r] = step, freq
+
+    def set_rate(self, r, rate, offset=None, samples_per_symbol=4):
+        """set_row from a symbol rate in symbols per item and (None: unchanged) an offset in cycles per item"""
+        self.set_row(r, RowResampler.steps_for([rate], samples_per_symbol)[0], None if offset is None else self._freq_word(offset))
+
+    def state(self, r):
+        """(items_in, items_out) of row r: the absolute index of its next input item and the index of its next output item"""
+        a, m = C.c_uint64(0), C.c_uint64(0)
+        check(lib().gr4pm_row_stream_state(self._h, int(r), C.byref(a), C.byref(m)), "StreamRowResampler.state")
+        return a.value, m.value
+
+    def __del__(self):
+        _destroy(self, "gr4pm_row_stream_destroy")
+
+
+class RowPacketReceivers:
+    """one NativePacketReceiver(decode_headers=True, packets_only=True) per row behind a StreamRowResampler: host
+    composition of existing blocks, for rows that grow by different lengths per call.  Each row keeps the items its
+    receiver has not consumed yet and presents them again in front of the next ones; nothing is submitted below the
+    receiver's smallest batch of 3072 items.  max_items: the most items one batch holds.  receiver_kw: samples_per_symbol,
+    syncword_freq_bins, syncword_threshold, costas_constellation of the receivers."""
+
+    MIN_BATCH = 3072  # one header window and one FFT block
+    TAIL = 12288      # zeros flush() appends: the receiver delivers a packet once the stream goes on well behind it
+
+    def __init__(self, n_rows, max_items=1 << 20, **receiver_kw):
+        self.n_rows, self.max_items = int(n_rows), int(max_items)
+        if self.n_rows < 1 or self.max_items < self.MIN_BATCH:
+            raise Gr4pmError(f"RowPacketReceivers: need at least one row and batches of {self.MIN_BATCH} items or more")
+        self._rx = [NativePacketReceiver(max_items=self.max_items + 4096, tags_cap=self.max_items // 768 + 64,
+                                         decode_headers=True, packets_only=True, **receiver_kw) for _ in range(self.n_rows)]
+        self._left = [None] * self.n_rows
+        self.stats = [{"items": 0, "headers": 0, "invalid_headers": 0, "crc_failures": 0} for _ in range(self.n_rows)]
+
+    def _run(self, r, new):
+        """row r's receiver over what it has left and `new`; returns the packets"""
+        torch = _torch()
+        left = self._left[r]
+        work = new if left is None or not left.numel() else (torch.cat([left, new]) if new.numel() else left)
+        packets, stats = [], self.stats[r]
+        while work.numel() >= self.MIN_BATCH:
+            n = min(work.numel(), self.max_items)
+            res = self._rx[r].process_bulk(work[:n].contiguous())
+            if res.get("status", 0):
+                raise Gr4pmError(f"RowPacketReceivers: row {r}: the receiver lost a batch: {res.get('error')}")
+            m, lens = res["header_messages"], res["packet_lengths"]
+            stats["headers"] += int(m.size)
+            stats["invalid_headers"] += int(np.sum(m["invalid_header"] != 0))
+            stats["crc_failures"] += int(np.sum(lens == 0))
+            data, pos = res["packets"].cpu().numpy(), 0
+            for k in lens[lens > 0]:
+                packets.append(data[pos:pos + int(k)].tobytes())
+                pos += int(k)
+            c = int(res["consumed"])
+            stats["items"] += c
+            work = work[c:]
+            if c == 0 or (n < self.max_items and work.numel() < self.MIN_BATCH):
+                break
+        self._left[r] = work.clone()
+        return packets
+
+    def process_rows(self, rows, lengths):
+        """rows: CUDA complex64 [n_rows, columns]; lengths: the items of each row in this call.  Returns a list per row of
+        the packets (bytes) its receiver delivered."""
+        if rows.shape[0] != self.n_rows or len(lengths) != self.n_rows:
+            raise Gr4pmError(f"RowPacketReceivers: {rows.shape[0]} rows and {len(lengths)} lengths for {self.n_rows} receivers")
+        return [self._run(r, rows[r, :int(lengths[r])]) for r in range(self.n_rows)]
+
+    def flush(self):
+        """appends the zeros a last packet needs behind it to every row and returns the packets that come out; what a
+        receiver still has not consumed is dropped"""
+        torch = _torch()
+        out = []
+        for r in range(self.n_rows):
+            out.append(self._run(r, torch.zeros(self.TAIL, dtype=torch.complex64, device="cuda")))
+            self._left[r] = None
+        return out
+
+
 class MultiChannelPacketReceiver:
     """BASELINE config 3: `n_channels` independent receive chains on one GPU
     (packet_receiver.hpp:191-265 couples nothing across receivers).  The detector is ONE batched

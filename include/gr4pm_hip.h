@@ -1635,6 +1635,74 @@ gr4pm_status gr4pm_row_resampler_process(gr4pm_row_resampler* h, const gr4pm_c64
                                          const uint64_t* lengths, const gr4pm_row_record* rows, size_t n_rows,
                                          gr4pm_c64* out, size_t out_stride, size_t n_cols_out, uint64_t* out_lengths);
 
+/* ====================================================================================
+ * StreamRowResampler (gr4pm_row_stream) -- the RowResampler as a stream block: every row's position, history and
+ * phase are carried from call to call, and CUTTING THE ROWS INTO CALLS CHANGES NO BIT OF WHAT COMES OUT (the
+ * project's own block).  It closes the chain MixedFftDdc -> rows at 4 samples per symbol ->
+ * one receiver per row for recordings of any length and carriers of any symbol rate.
+ *
+ * Handle: the RowResampler's prototype and the two tables made from it: Q phases, P taps per phase, the same H and
+ * Dh, the same refusals of the sizes, NULL taps the same default design.  R = 1 .. 64 rows, each with a record
+ * {step, phase0, freq}, a gr4pm_row_record: the step's range is the one-shot's and phase0 < 2^63; and a start_index[r]
+ * (uint64; a NULL array: 0 for every row): the absolute index of the first item the row will ever be given, as the
+ * MixedFftDdc has a start_index.
+ * A row is an unbounded sequence of items x_r[a], a an absolute index; every x_r[a] with a < start_index[r] is +0.
+ * Output item m sits at pos_m = phase0 + m step, an unbounded integer with 32 fractional bits.  Its value is the
+ * RowResampler's: the branch, alpha, c_s, the single accumulator with s ascending and the rotator are unchanged, with
+ *     theta(pos) = Phi + floor(freq (pos - ref) / 2^32) mod 2^32
+ * At create Phi = 0 and ref = 0, so theta is the one-shot's floor(freq pos / 2^32) mod 2^32.
+ * Per-row state: A_r, the items taken so far (it starts at start_index[r]); the index of the next output item and
+ * its position (at create the first m with floor(pos_m) >= start_index[r]); Phi, ref, and the row's last P - 1 items
+ * on the device (+0 at create).
+ * process: the next lengths[r] <= n_cols items of each row, the layout gr4pm_fft_ddc_mixed_process returns.  Row r
+ *   makes every item not yet made with floor(pos) <= A_r + lengths[r] - 1, into out[r out_stride + 0 ..] with +0
+ *   behind them up to n_cols_out (out may be uninitialised), and their count into out_lengths[r].  Rows are
+ *   independent; any mix of lengths in one call, 0 and lengths below P - 1 included.
+ * flush: the items with floor(pos) <= A_r + P - 2 (the filter runs out over +0 behind the last item, as the one-
+ *   shot's M_r does), then every row is back in its created state with its current step and freq.
+ * reset: the same without the output.
+ * set_row(r, step, freq) takes effect at the next output item: with m* its index, its position p* does not move,
+ *   pos_m = p* + (m - m*) step_new from then on, Phi <- theta_old(p*), ref <- p*, freq <- freq_new: the phase is
+ *   continuous at item m*.
+ * items_for: host only, changes no state: what the next process would report for these lengths.
+ * state: the row's two counters, A_r and the index of the next output item (mod 2^64).
+ * The host's exact arithmetic: the kernel works with 64-bit positions relative to a per-call base.  The host moves the
+ * base, and ref with it, forward by whole items B and adds freq B mod 2^32 to Phi:
+ *     floor(freq (pos - ref - B 2^32) / 2^32) = floor(freq (pos - ref) / 2^32) - freq B
+ * so no theta changes, and no position wraps however long the stream is.
+ * Refusals enqueue nothing and change no state.  GR4PM_ERR_INVALID: a row count outside 1 .. 64, a step out of range
+ * (create, set_row), lengths[r] > n_cols, R > 1 with stride < n_cols or out_stride < n_cols_out, a NULL array that is
+ * needed.  GR4PM_ERR_OVERFLOW: phase0 >= 2^63, lengths[r] + P - 1 >= 2^32, n_cols_out > 2^31, an n_cols_out below some
+ * row's count of this call (a stream must not lose items, so the call is not cut).  Calls enqueue on the handle's
+ * stream, do not wait and read nothing back.  create, items_for, set_row, state and reset are host only: the device
+ * tables are made by the first process or flush, which is where a missing device is an error.
+ * ================================================================================== */
+typedef struct gr4pm_row_stream gr4pm_row_stream;
+typedef struct {
+    uint32_t phases;               /* Q */
+    uint32_t taps_per_phase;       /* P (0 with NULL taps: 12) */
+    const float* taps;             /* host: Q P floats, copied at create (NULL: gr4pm_row_resampler_taps(Q, P, 1, 0.25, 0.75)) */
+    size_t n_rows;                 /* R: 1 .. 64 */
+    const gr4pm_row_record* rows;  /* host: R records, copied at create */
+    const uint64_t* start_index;   /* host: R absolute indices (NULL: 0 each) */
+    void* stream;                  /* hipStream_t (NULL: the default stream) */
+} gr4pm_row_stream_params;
+gr4pm_status gr4pm_row_stream_create(const gr4pm_row_stream_params* params, gr4pm_row_stream** out);
+void gr4pm_row_stream_destroy(gr4pm_row_stream* h);
+gr4pm_status gr4pm_row_stream_reset(gr4pm_row_stream* h);
+/* lengths, out_lengths: HOST, R items each */
+gr4pm_status gr4pm_row_stream_items_for(const gr4pm_row_stream* h, const uint64_t* lengths, uint64_t* out_lengths);
+/* x: DEVICE, R rows of n_cols items, `stride` items apart (may be NULL when every length is 0).  lengths: HOST, R items
+ * (NULL: n_cols each).  out: DEVICE, R rows of n_cols_out items, out_stride apart (may be NULL when n_cols_out is 0).
+ * out_lengths: HOST, R items. */
+gr4pm_status gr4pm_row_stream_process(gr4pm_row_stream* h, const gr4pm_c64* x, size_t stride, size_t n_cols,
+                                      const uint64_t* lengths, gr4pm_c64* out, size_t out_stride, size_t n_cols_out,
+                                      uint64_t* out_lengths);
+gr4pm_status gr4pm_row_stream_flush(gr4pm_row_stream* h, gr4pm_c64* out, size_t out_stride, size_t n_cols_out,
+                                    uint64_t* out_lengths);
+gr4pm_status gr4pm_row_stream_set_row(gr4pm_row_stream* h, size_t row, uint64_t step, int32_t freq);
+gr4pm_status gr4pm_row_stream_state(const gr4pm_row_stream* h, size_t row, uint64_t* items_in, uint64_t* items_out);
+
 /* ---- FftDdc: K off-grid channels from one shared transform (the project's own block) ----------
  * The Ddc's drop-in for power-of-two decimations and many channels: a fast-convolution (overlap-save) filter bank.
  * N = 2048, K channels (1 .. 64), D a power of two in 4 .. 64, B = N / D, a real finite prototype h[0 .. L - 1], an

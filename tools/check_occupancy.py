@@ -155,6 +155,10 @@ BUDGETS = [
     # the RowResampler block: one accumulator, a coefficient pair and the double-precision rotator per lane, eight waves
     # per SIMD; its LDS is dynamic, at most 64 KiB of tables and stage
     (r"k_row_resample", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
+    # the StreamRowResampler block: k_row_resample's lane with the row's carried state as operands, the same eight waves per
+    # SIMD and dynamic LDS; and the copy of a row's last P - 1 items, a handful of registers
+    (r"k_row_stream_keep", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
+    (r"k_row_stream", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
 ]
 
 
