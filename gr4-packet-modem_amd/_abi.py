@@ -259,6 +259,24 @@ class RowStreamParams(C.Structure):
                 ("rows", C.c_void_p), ("start_index", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class RowGateParams(C.Structure):
+    _fields_ = [("n_rows", C.c_size_t), ("n_cols", C.c_size_t), ("block", C.c_uint32), ("hold_blocks", C.c_uint32),
+                ("min_blocks", C.c_uint32), ("pre_blocks", C.c_uint32), ("post_blocks", C.c_uint32), ("max_blocks", C.c_uint32),
+                ("open_sum", C.c_float), ("close_sum", C.c_float), ("stream", C.c_void_p)]
+
+
+class RowGateState(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("blocks", C.c_uint64), ("emitted", C.c_uint64), ("dropped", C.c_uint64),
+                ("truncated", C.c_uint64), ("open", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# gr4pm_row_gate_record: 48 bytes; GR4PM_ROW_GATE_TRUNCATED, GR4PM_ROW_GATE_AT_END
+ROW_GATE_RECORD_DTYPE = np.dtype([("first_item", "<u8"), ("first_active_item", "<u8"), ("power", "<f8"), ("row", "<u4"),
+                                  ("n_items", "<u4"), ("active_items", "<u4"), ("flags", "<u4"), ("peak", "<f4"),
+                                  ("reserved", "<u4")])
+ROW_GATE_TRUNCATED, ROW_GATE_AT_END = 1, 2
+
+
 class FftDdcParams(C.Structure):
     _fields_ = [("n_channels", C.c_size_t), ("decimation", C.c_size_t), ("frequencies", C.c_void_p), ("taps", C.c_void_p),
                 ("n_taps", C.c_size_t), ("taps_per_phase", C.c_size_t), ("overlap", C.c_int64), ("images", C.c_size_t),
@@ -382,6 +400,8 @@ EXPORTS = [
     "gr4pm_row_resampler_output_lengths", "gr4pm_row_resampler_tile_items", "gr4pm_row_resampler_process",
     "gr4pm_row_stream_create", "gr4pm_row_stream_destroy", "gr4pm_row_stream_reset", "gr4pm_row_stream_items_for",
     "gr4pm_row_stream_process", "gr4pm_row_stream_flush", "gr4pm_row_stream_set_row", "gr4pm_row_stream_state",
+    "gr4pm_row_gate_create", "gr4pm_row_gate_destroy", "gr4pm_row_gate_reset", "gr4pm_row_gate_set_thresholds",
+    "gr4pm_row_gate_state", "gr4pm_row_gate_sizes", "gr4pm_row_gate_process", "gr4pm_row_gate_flush", "gr4pm_row_gate_block_power",
     "gr4pm_fft_ddc_taps", "gr4pm_fft_ddc_create", "gr4pm_fft_ddc_destroy", "gr4pm_fft_ddc_reset", "gr4pm_fft_ddc_frames_for",
     "gr4pm_fft_ddc_frequencies", "gr4pm_fft_ddc_sizes", "gr4pm_fft_ddc_process", "gr4pm_fft_ddc_process_iq",
     "gr4pm_fft_ddc_mixed_create", "gr4pm_fft_ddc_mixed_destroy", "gr4pm_fft_ddc_mixed_reset", "gr4pm_fft_ddc_mixed_frames_for",
@@ -649,6 +669,16 @@ def lib():
     L.gr4pm_row_stream_flush.argtypes = [vp, vp, sz, sz, vp]
     L.gr4pm_row_stream_set_row.argtypes = [vp, sz, C.c_uint64, C.c_int32]
     L.gr4pm_row_stream_state.argtypes = [vp, sz, vp, vp]
+    L.gr4pm_row_gate_create.argtypes = [C.POINTER(RowGateParams), C.POINTER(vp)]
+    L.gr4pm_row_gate_destroy.argtypes = [vp]
+    L.gr4pm_row_gate_destroy.restype = None
+    L.gr4pm_row_gate_reset.argtypes = [vp]
+    L.gr4pm_row_gate_set_thresholds.argtypes = [vp, sz, C.c_float, C.c_float]
+    L.gr4pm_row_gate_state.argtypes = [vp, sz, C.POINTER(RowGateState)]
+    L.gr4pm_row_gate_sizes.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp]
+    L.gr4pm_row_gate_process.argtypes = [vp, vp, sz, vp, vp, sz, sz, vp, szp]
+    L.gr4pm_row_gate_flush.argtypes = [vp, vp, sz, sz, vp, szp]
+    L.gr4pm_row_gate_block_power.argtypes = [vp, vp, sz, vp, vp, sz]
     L.gr4pm_fft_ddc_taps.argtypes = [sz, sz, vp]
     L.gr4pm_fft_ddc_create.argtypes = [C.POINTER(FftDdcParams), C.POINTER(vp)]
     L.gr4pm_fft_ddc_destroy.argtypes = [vp]

@@ -3391,6 +3391,157 @@ class StreamRowResampler:
         _destroy(self, "gr4pm_row_stream_destroy")
 
 
+class RowBurstGate:
+    """gr4pm_row_gate: a power squelch on rows that carries its state from call to call.  Fed with
+    MixedFftDdc.process_bulk's ragged rows call after call, it delivers every burst of every row once, as a zero-padded row
+    of the [bursts, n_cols] layout that LineSpectrum, RowResampler and the receivers take; cutting the rows into calls
+    changes no byte of a row's records and burst rows.  block: B, a power of two 16 .. 1024; a block whose power sum
+    reaches the row's open_sum opens a burst, hold_blocks + 1 blocks in a row below its close_sum close it, bursts of
+    fewer than min_blocks blocks are dropped, pre_blocks and post_blocks (<= hold_blocks + 1) blocks of margin go with a
+    burst, and the block that completes max_blocks (None: n_cols // block) ends one that is still open (its record has
+    TRUNCATED).  The gate is shut until set_thresholds or set_floor.  The handle is made at construction and is host only
+    until the first process_rows, flush or block_power, which run on the stream that was current at construction."""
+
+    TRUNCATED, AT_END = _abi.ROW_GATE_TRUNCATED, _abi.ROW_GATE_AT_END
+
+    def __init__(self, n_rows, n_cols=4096, block=64, hold_blocks=3, min_blocks=2, pre_blocks=4, post_blocks=4, max_blocks=None):
+        self.n_rows, self.n_cols, self.block = int(n_rows), int(n_cols), int(block)
+        values = [self.n_rows, self.n_cols, self.block, int(hold_blocks), int(min_blocks), int(pre_blocks), int(post_blocks),
+                  0 if max_blocks is None else int(max_blocks)]
+        if any(not 0 <= v < 1 << 32 for v in values):
+            raise Gr4pmError("RowBurstGate: the sizes must fit 32 unsigned bits")
+        if max_blocks is not None and values[7] == 0:
+            raise Gr4pmError("RowBurstGate: max_blocks is 1 or more")
+        try:
+            stream = _stream_handle()
+        except Gr4pmError:  # no GPU: the host-only calls still work, the others report the missing device
+            stream = C.c_void_p()
+        self._stream = stream.value
+        p = _abi.RowGateParams(*values, 0.0, 0.0, stream)
+        self._h = C.c_void_p()
+        check(lib().gr4pm_row_gate_create(C.byref(p), C.byref(self._h)), "RowBurstGate")
+        b, m, n = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+        check(lib().gr4pm_row_gate_sizes(self._h, C.byref(b), C.byref(m), C.byref(n)), "RowBurstGate")
+        self.max_blocks = m.value
+
+    def _rows(self, x):
+        torch = _torch()
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
+                x.shape[0] == self.n_rows and (x.shape[1] <= 1 or x.stride(1) == 1) and
+                (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
+            raise TypeError(f"rows must be a [{self.n_rows}, n] complex64 CUDA tensor with contiguous rows")
+        if torch.cuda.current_stream(x.device).cuda_stream != self._stream:
+            _inputs_ready(x)  # made on another stream than the handle's
+        return x.shape[1], (x.stride(0) if self.n_rows > 1 else max(x.shape[1], 1))
+
+    def _lengths(self, lengths, n_in):
+        if lengths is None:
+            return np.full(self.n_rows, n_in, dtype=np.uint64)
+        lengths = RowResampler._row_lengths(self.n_rows, 0, lengths)
+        if lengths.size != self.n_rows:
+            raise Gr4pmError(f"RowBurstGate: {lengths.size} lengths for {self.n_rows} rows")
+        return lengths
+
+    def _emit(self, what, call, cap, out, device):
+        """runs call(out_ptr, out_stride, cap, records_ptr, count_ptr); with cap None a capacity refusal is followed by one
+        more call with the count the library reports"""
+        torch = _torch()
+        given, want = cap is not None or out is not None, (4 * self.n_rows + 12 if cap is None else int(cap))
+        if out is not None:
+            out = _rows_output(out, out.shape[0], self.n_cols, device, "RowBurstGate")
+            want = out.shape[0] if cap is None else min(want, out.shape[0])
+        count = C.c_size_t(0)
+        for attempt in range(2):
+            rows = out if out is not None else torch.empty((want, self.n_cols), dtype=torch.complex64, device=device)
+            records = np.zeros(max(want, 1), dtype=_abi.ROW_GATE_RECORD_DTYPE)
+            stride = rows.stride(0) if rows.shape[0] > 1 else self.n_cols
+            status = call(rows.data_ptr() if want else None, stride, want, _np_ptr(records), C.byref(count))
+            if status == -5 and count.value > want and not given and attempt == 0:  # GR4PM_ERR_OVERFLOW: the capacity
+                want = count.value
+                continue
+            check(status, what)
+            break
+        n = count.value
+        records = records[:n].copy()
+        return rows[:n], records["n_items"].astype(np.int64), records
+
+    def process_rows(self, rows, lengths=None, cap=None, out=None):
+        """rows: a CUDA complex64 tensor [n_rows, n] with contiguous rows, the next lengths[r] <= n items of every row
+        (None: n each).  Returns (burst_rows, burst_lengths, records): burst_rows is CUDA complex64 [bursts, n_cols] with
+        the span's items and +0 behind them, in the order (row, time); burst_lengths numpy int64; records a structured
+        array (row, first_item, n_items, first_active_item, active_items, flags, peak, power).  cap: the most bursts the
+        call may emit (None: a guess, and a second call with the library's count if it was too small; nothing is ever
+        lost); a call that would emit more raises and changes nothing.  out: an optional CUDA complex64 [cap, >= n_cols]
+        tensor.  Waits for the block sums; the copies into burst_rows are enqueued, not waited for."""
+        n_in, stride = self._rows(rows)
+        lengths = self._lengths(lengths, n_in)
+        res = self._emit("RowBurstGate.process_rows", lambda o, os_, c, rec, cnt: lib().gr4pm_row_gate_process(
+            self._h, rows.data_ptr() if n_in else None, stride, _np_ptr(lengths), o, os_, c, rec, cnt), cap, out, rows.device)
+        self._last = rows  # the copies do not wait: the input lives until the next call
+        return res
+
+    def flush(self, cap=None, out=None):
+        """the end of the rows: an incomplete block is decided with +0 behind it, open bursts close (AT_END) with their
+        margins clipped to the items that exist; then every row is in its created state, thresholds kept.  Returns what
+        process_rows returns."""
+        device = out.device if out is not None else _torch().device("cuda", _torch().cuda.current_device())
+        return self._emit("RowBurstGate.flush", lambda o, os_, c, rec, cnt: lib().gr4pm_row_gate_flush(self._h, o, os_, c, rec, cnt),
+                          cap, out, device)
+
+    def reset(self):
+        """every row back to its created state without output; the thresholds stay"""
+        check(lib().gr4pm_row_gate_reset(self._h), "RowBurstGate.reset")
+
+    def state(self, row):
+        """dict(items, blocks, open, emitted, dropped, truncated) of a row (host only)"""
+        s = _abi.RowGateState()
+        check(lib().gr4pm_row_gate_state(self._h, int(row), C.byref(s)), "RowBurstGate.state")
+        return dict(items=s.items, blocks=s.blocks, open=bool(s.open), emitted=s.emitted, dropped=s.dropped, truncated=s.truncated)
+
+    def set_thresholds(self, row, open_sum, close_sum):
+        """the block sums (float32) that open and keep open a burst of this row, from the next block decided:
+        0 < close_sum <= open_sum"""
+        check(lib().gr4pm_row_gate_set_thresholds(self._h, int(row), float(np.float32(open_sum)), float(np.float32(close_sum))),
+              "RowBurstGate.set_thresholds")
+
+    def set_floor(self, floors, open_db=10.0, close_db=6.0):
+        """set_thresholds for every row from its noise floor in power per item: floor * block * 10^(dB / 10), rounded to
+        float32 once"""
+        floors = np.asarray(floors, dtype=np.float64).reshape(-1)
+        if floors.size != self.n_rows:
+            raise Gr4pmError(f"RowBurstGate: {floors.size} floors for {self.n_rows} rows")
+        for r, f in enumerate(floors):
+            self.set_thresholds(r, np.float32(f * self.block * 10.0 ** (open_db / 10.0)),
+                                np.float32(f * self.block * 10.0 ** (close_db / 10.0)))
+
+    def block_power(self, rows, lengths=None):
+        """the block sums of rows that begin at item 0, by the gate's kernel and in its order; changes no state.  Returns a
+        list of numpy float32 arrays, lengths[r] // block sums each.  Waits."""
+        torch = _torch()
+        n_in, stride = self._rows(rows)
+        lengths = self._lengths(lengths, n_in)
+        cols = max(n_in // self.block, 1)
+        out = torch.empty((self.n_rows, cols), dtype=torch.float32, device=rows.device)
+        check(lib().gr4pm_row_gate_block_power(self._h, rows.data_ptr() if n_in else None, stride, _np_ptr(lengths), out.data_ptr(), cols),
+              "RowBurstGate.block_power")
+        torch.cuda.synchronize(rows.device)  # the handle's stream need not be torch's current one
+        sums = out.cpu().numpy()
+        return [sums[r, :int(lengths[r]) // self.block].copy() for r in range(self.n_rows)]
+
+    def measure_floor(self, rows, lengths=None, quantile=0.1):
+        """per row the `quantile` order statistic (the sorted block powers' item floor(quantile * count)) of its block
+        powers per item, 0 for a row without a complete block: a low quantile, because a band may be on the air most of
+        the time"""
+        out = np.zeros(self.n_rows, dtype=np.float64)
+        for r, s in enumerate(self.block_power(rows, lengths)):
+            if s.size:
+                out[r] = float(np.sort(s)[min(int(quantile * s.size), s.size - 1)]) / self.block
+        return out
+
+    def __del__(self):
+        _destroy(self, "gr4pm_row_gate_destroy")
+
+
 class RowPacketReceivers:
     """one NativePacketReceiver(decode_headers=True, packets_only=True) per row behind a StreamRowResampler: host
     composition of existing blocks, for rows that grow by different lengths per call.  Each row keeps the items its

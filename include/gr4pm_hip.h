@@ -1703,6 +1703,110 @@ gr4pm_status gr4pm_row_stream_flush(gr4pm_row_stream* h, gr4pm_c64* out, size_t 
 gr4pm_status gr4pm_row_stream_set_row(gr4pm_row_stream* h, size_t row, uint64_t step, int32_t freq);
 gr4pm_status gr4pm_row_stream_state(const gr4pm_row_stream* h, size_t row, uint64_t* items_in, uint64_t* items_out);
 
+/* ====================================================================================
+ * RowBurstGate (gr4pm_row_gate) -- a power squelch on rows that carries its state from call to call: fed with the
+ * ragged rows of gr4pm_fft_ddc_mixed_process call after call, it delivers every burst of every row once, as a
+ * zero-padded row of the [bursts, n_cols] layout that the LineSpectrum, the RowResampler and the receivers take.
+ * CUTTING THE ROWS INTO CALLS CHANGES NO BYTE OF A ROW'S RECORDS AND BURST ROWS (the project's own block; DESIGN.md
+ * section 30).
+ *
+ * Handle: R = 1 .. 64 rows of complex64 items and a block length B, a power of two from 16 to 1024 (0: 64).  Each
+ * row counts its items from 0 at create, reset and flush, as uint64; block b of a row is its items [b B, (b + 1) B).
+ * Block power, bit for bit: per item p = fl32(fl32(re re) + fl32(im im)), no contraction.  The block sum s_b is
+ * float32 over the B values in this order, fixed per B: with W = min(B, 64), t[l] (l = 0 .. W - 1) takes p of the
+ * block's item l and then adds those of items l + W, l + 2 W, ... in ascending order, one float32 addition each;
+ * then log2(W) folds with offset = W / 2, W / 4, .. 1: t[l] <- fl32(t[l] + t[l + offset]) for l < offset; s_b = t[0].
+ * It does not depend on how the row is cut into calls.
+ * Per-row state machine over s_b in block order; comparisons are float32 against the row's open_sum and close_sum,
+ * 0 < close_sum <= open_sum (a NaN sum compares false: inactive).
+ *   idle: a block with s_b >= open_sum opens a burst: first_active = last_active = b, start = max(0, b - pre_blocks).
+ *   open: a block with s_b >= close_sum is active: last_active = b.  The (hold_blocks + 1)-th inactive block in a row
+ *     closes the burst: with last_active - first_active + 1 < min_blocks it is dropped and counted, else the span of
+ *     blocks [start, last_active + post_blocks] is emitted.  post_blocks <= hold_blocks + 1, so the post margin has
+ *     arrived at the closing block, and a burst is emitted in the call that holds its closing block.
+ *   forced split: a block c behind which the burst is still open and with c - start + 1 == max_blocks ends it: the
+ *     span [start, c] is emitted with GR4PM_ROW_GATE_TRUNCATED whatever its active extent, the row goes idle and
+ *     the next block is judged from idle; its pre margin may reach back into the emitted span (a copy, no error).
+ *     No span exceeds max_blocks blocks.
+ *   set_thresholds(row, open_sum, close_sum) holds from the next block decided.
+ * create refuses (GR4PM_ERR_INVALID) R outside 1 .. 64, a B that is no power of two in 16 .. 1024, min_blocks = 0,
+ * post_blocks > hold_blocks + 1, pre_blocks + min_blocks + post_blocks > max_blocks, max_blocks B > n_cols,
+ * n_cols > 2^30, and sums other than 0 < close_sum <= open_sum (both 0: the gate stays shut until set_thresholds).
+ * process appends lengths[r] <= stride items to row r.  Items of an incomplete trailing block are kept and have no
+ *   power yet.  Per emitted burst, in the order (row, time) within a call, out[i out_stride + 0 .. n_items) holds the
+ *   span's items and +0 fills the rest up to n_cols (out may be uninitialised; rows at and behind *n_bursts are not
+ *   touched), and records[i] goes with it: row, first_item (of the span), n_items, first_active_item, active_items
+ *   ((last_active - first_active + 1) B), flags, peak (the largest s_b of the active extent) and power (the sum of the
+ *   active blocks' s_b in block order, in double on the host, divided by active_items).
+ *   Capacity: a call that emits more than `cap` bursts returns GR4PM_ERR_OVERFLOW with the count in *n_bursts and
+ *   changes nothing: the plan is made before anything is committed, so the same call with that cap succeeds.  Every
+ *   other refusal leaves the state untouched too: a NULL array that is needed (GR4PM_ERR_INVALID), lengths[r] >
+ *   stride (GR4PM_ERR_INVALID), lengths[r] >= 2^32 - max_blocks B (GR4PM_ERR_OVERFLOW), cap > 1 with out_stride <
+ *   n_cols (GR4PM_ERR_INVALID).
+ * flush: a trailing incomplete block is completed with +0 for its power only and decided; then the row counts as
+ *   followed by inactive blocks without end: an open burst closes at once (dropped below min_blocks), with
+ *   GR4PM_ROW_GATE_AT_END and its post margin, n_items and active_items clipped to the items that exist.  What closes
+ *   is emitted as process emits; then every row is in its created state, its thresholds and burst counters kept.
+ * reset: the created state (counters at 0) without emitting; the thresholds stay.
+ * state: items taken, blocks decided, open or idle, bursts emitted, dropped and truncated.
+ * block_power: a one-shot entry that changes no state: the floor(lengths[r] / B) block sums of rows that begin at
+ *   item 0, into out[r out_stride + b]: the same kernel body, the same bits.  Enqueues and does not wait.
+ * Per row, the sequence of records and the bytes of the burst rows do not depend on the cutting into calls; only the
+ * interleaving of different rows' bursts across calls does.  A row retains at most (max_blocks + 1) B - 1 items on
+ * the device.  process and flush enqueue on the handle's stream, copy the call's block sums to the host and wait for
+ * them once, in front of the plan; the copies into `out` are enqueued behind it and not waited for, so x lives until
+ * the stream has run them.  create, set_thresholds, state, sizes and reset are host only: the device side is made by
+ * the first process, flush or block_power, which is where a missing device is an error.
+ * ================================================================================== */
+#define GR4PM_ROW_GATE_TRUNCATED 1u
+#define GR4PM_ROW_GATE_AT_END 2u
+typedef struct gr4pm_row_gate gr4pm_row_gate;
+typedef struct {
+    size_t n_rows;        /* R: 1 .. 64 */
+    size_t n_cols;        /* columns of a burst row */
+    uint32_t block;       /* B (0: 64) */
+    uint32_t hold_blocks;
+    uint32_t min_blocks;
+    uint32_t pre_blocks;
+    uint32_t post_blocks;
+    uint32_t max_blocks;  /* 0: n_cols / B */
+    float open_sum;       /* every row's at create (both 0: +inf, shut) */
+    float close_sum;
+    void* stream;         /* hipStream_t (NULL: the default stream) */
+} gr4pm_row_gate_params;
+typedef struct {
+    uint64_t first_item;        /* of the span, counted in the row */
+    uint64_t first_active_item;
+    double power;               /* per item of the active extent */
+    uint32_t row;
+    uint32_t n_items;
+    uint32_t active_items;
+    uint32_t flags;             /* GR4PM_ROW_GATE_* */
+    float peak;
+    uint32_t reserved;
+} gr4pm_row_gate_record;
+typedef struct {
+    uint64_t items, blocks, emitted, dropped, truncated;
+    uint32_t open;
+    uint32_t reserved;
+} gr4pm_row_gate_state_t;
+gr4pm_status gr4pm_row_gate_create(const gr4pm_row_gate_params* params, gr4pm_row_gate** out);
+void gr4pm_row_gate_destroy(gr4pm_row_gate* h);
+gr4pm_status gr4pm_row_gate_reset(gr4pm_row_gate* h);
+gr4pm_status gr4pm_row_gate_set_thresholds(gr4pm_row_gate* h, size_t row, float open_sum, float close_sum);
+gr4pm_status gr4pm_row_gate_state(const gr4pm_row_gate* h, size_t row, gr4pm_row_gate_state_t* out);
+gr4pm_status gr4pm_row_gate_sizes(const gr4pm_row_gate* h, uint32_t* block, uint32_t* max_blocks, size_t* n_cols);
+/* x: DEVICE, R rows `stride` items apart (may be NULL when every length is 0).  lengths: HOST, R items.  out: DEVICE,
+ * cap rows of n_cols items, out_stride apart.  records: HOST, cap records.  n_bursts: HOST. */
+gr4pm_status gr4pm_row_gate_process(gr4pm_row_gate* h, const gr4pm_c64* x, size_t stride, const uint64_t* lengths,
+                                    gr4pm_c64* out, size_t out_stride, size_t cap, gr4pm_row_gate_record* records,
+                                    size_t* n_bursts);
+gr4pm_status gr4pm_row_gate_flush(gr4pm_row_gate* h, gr4pm_c64* out, size_t out_stride, size_t cap,
+                                  gr4pm_row_gate_record* records, size_t* n_bursts);
+/* out: DEVICE float, R rows out_stride apart */
+gr4pm_status gr4pm_row_gate_block_power(gr4pm_row_gate* h, const gr4pm_c64* x, size_t stride, const uint64_t* lengths,
+                                        float* out, size_t out_stride);
+
 /* ---- FftDdc: K off-grid channels from one shared transform (the project's own block) ----------
  * The Ddc's drop-in for power-of-two decimations and many channels: a fast-convolution (overlap-save) filter bank.
  * N = 2048, K channels (1 .. 64), D a power of two in 4 .. 64, B = N / D, a real finite prototype h[0 .. L - 1], an

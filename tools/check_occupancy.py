@@ -159,6 +159,11 @@ BUDGETS = [
     # SIMD and dynamic LDS; and the copy of a row's last P - 1 items, a handful of registers
     (r"k_row_stream_keep", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
     (r"k_row_stream", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
+    # the RowBurstGate block: the power pass holds 16 loads of 8 bytes per lane and their powers, eight waves per SIMD and
+    # no LDS, so it runs beside anything; the two copies take a handful of registers
+    (r"k_row_gate_power", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
+    (r"k_row_gate_gather", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
+    (r"k_row_gate_keep", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
 ]
 
 
