@@ -1008,7 +1008,7 @@ class PacketReceiver:
     candidate's header; (B) the real
     chain runs with those messages, and the headers it decodes itself are compared with the ones
     it was given (`header_mismatches` in the result; its payload LLRs leave descrambled as
-    "payload_llr" / "payload_tags").  Pass A runs on a compact stream of one 912-sample window
+    "payload_llr" / "payload_tags").  Pass A runs on a compact stream of one 228-symbol window
     per detection, so it costs a few percent of the real pass.  A header whose symbols continue in
     the next batch stays pending until then.  The payload tail follows (:140-147): BinarySlicer<true>,
     PackBits, CrcCheck(discard_crc) -- "packets" holds the bytes of the packets whose CRC-32 matches,
@@ -1026,6 +1026,9 @@ class PacketReceiver:
         self.soft_bits = soft_bits
         sps = samples_per_symbol
         self.samples_per_symbol = sps
+        if decode_headers and sps < 4:  # as gr4pm_packet_receiver_create (see there)
+            raise Gr4pmError(f"decode_headers needs at least 4 samples per symbol ({sps} given): below that the reference's "
+                             "symbol filter loses the symbol clock at a detection and no header decodes")
         rrc = root_raised_cosine(1.0, float(sps), 1.0, 0.35, sps * 11)            # :60-65
         norm = np.float32(0.0)
         for v in rrc:                                                            # :67-74 (float accumulate)
@@ -1064,7 +1067,9 @@ class PacketReceiver:
                 self._awaiting_tags = np.zeros(0, dtype=TAG_DTYPE)
                 self._spec_order = np.zeros(0, dtype=np.uint64)  # detections in pass A, header not out yet
                 self._spec_fifo = np.zeros(0, dtype=_abi.HEADER_MSG_DTYPE)
-                self._tail = torch.zeros(self._SPEC_W + self._SPEC_PRE, dtype=torch.complex64, device="cuda")
+                # pass A's window, in items: 64 and 912 at 4 samples per symbol (see _predecode)
+                self._spec_pre, self._spec_w = self._SPEC_PRE_SYMBOLS * sps, self._SPEC_W_SYMBOLS * sps
+                self._tail = torch.zeros(self._spec_w + self._spec_pre, dtype=torch.complex64, device="cuda")
                 self._known_idx = np.zeros(0, dtype=np.uint64)  # candidates with a decoded header ...
                 self._known_msg = np.zeros(0, dtype=_abi.HEADER_MSG_DTYPE)  # ... and the message
                 self._pending_real = None                       # accepted packet waiting for its header
@@ -1137,11 +1142,12 @@ class PacketReceiver:
         return {"status": 0, "consumed": n, "symbols": w, "tags": sym_tags, "detector_tags": det_tags,
                 "accepted": acc, "headers": hdrs}
 
-    # pass A works on a compact stream: one window of _SPEC_W samples per detection, starting
-    # _SPEC_PRE samples before the tagged one (room for the matched filter's history) and long
-    # enough for syncword + header behind the filter delay: 16 + 11 + 192 < 228 symbols
-    _SPEC_PRE = 64
-    _SPEC_W = 912
+    # pass A works on a compact stream: one window of _SPEC_W_SYMBOLS symbols per detection, starting
+    # _SPEC_PRE_SYMBOLS symbols before the tagged sample (room for the matched filter's history) and long
+    # enough for syncword + header behind the filter delay: 16 + 11 + 192 < 228 symbols.  In items
+    # (self._spec_pre, self._spec_w) that is samples_per_symbol times as much, as in the native receiver.
+    _SPEC_PRE_SYMBOLS = 16
+    _SPEC_W_SYMBOLS = 228
 
     def _predecode(self, y, det_tags, idx_abs, base):
         """pass A: the header of every detection (see the class docstring); updates the table of
@@ -1150,7 +1156,7 @@ class PacketReceiver:
         tail of this one)."""
         torch = _torch()
         sp = self._spec
-        n, W, pre = y.numel(), self._SPEC_W, self._SPEC_PRE
+        n, W, pre = y.numel(), self._spec_w, self._spec_pre
         # window starts relative to y[0]: waiting detections of the last batch first (negative)
         old = self._awaiting.astype(np.int64) - np.int64(base) - pre
         new = det_tags["index"].astype(np.int64) - pre
@@ -1264,7 +1270,7 @@ class PacketReceiver:
                 self._pm_carry = None
             pm = self.payload_metadata_insert.process_bulk(sym_in, tags_in, hdrs_in, per_tag=True)
             if pm["consumed"] != sym_in.numel():
-                # the block waits for a header that pass A delivers with the next batch (a batch that ends 816 .. 848 items
+                # the block waits for a header that pass A delivers with the next batch (a batch that ends 204 .. 212 symbols
                 # behind a syncword, payload_metadata_insert.hpp:243-247): the rest is carried, as in the native receiver
                 rest = sym_in.numel() - pm["consumed"]
                 if rest > 1024:
@@ -3823,10 +3829,14 @@ class NativePacketReceiver:
 
     def _new_outputs(self, n, device):
         torch = _torch()
-        n_sym = n // self.samples_per_symbol + 4160
+        sps = self.samples_per_symbol
+        n_sym = n // sps + 4160
+        # packets: a QPSK stream carries at most n / (4 sps) payload bytes -- n // 16 at 4 samples per symbol, the lowest
+        # rate decode_headers takes, and never less above it; 65536 for the packet that a batch finishes for the one before
         return (torch.empty(n_sym, dtype=torch.complex64, device=device),
                 torch.empty(2 * n_sym if self.soft_bits and not self.packets_only else 1, dtype=torch.float32, device=device),
-                torch.empty((self._packets_cap or n // 16 + 65536) if self.decode_headers else 1, dtype=torch.uint8, device=device))
+                torch.empty((self._packets_cap or n // (4 * min(sps, 4)) + 65536) if self.decode_headers else 1,
+                            dtype=torch.uint8, device=device))
 
     def _outputs(self, n, device):
         """the output set of the next submit; _out_next moves on only once the library has taken the batch"""

@@ -292,7 +292,10 @@ struct gr4pm_packet_receiver {
     uint64_t hist = 0;
     std::deque<gr4pm_header_msg> hdr_fifo; // gate -> PayloadMetadataInsert (stage 1 -> 2, in the slot)
     // ---- decode_headers: pass A (stage 1 thread) ----
-    static constexpr unsigned kPre = 64, kW = 912; // window: 64 items before the tag, 228 symbols in all
+    // window: 16 symbols before the tag (room for the matched filter's history), 228 symbols in all -- syncword + header
+    // behind the filter delay: 16 + 11 + 192 < 228.  Item counts, so per handle: 64 and 912 at 4 samples per symbol.
+    static constexpr unsigned kPreSymbols = 16, kWSymbols = 228;
+    unsigned kPre = 0, kW = 0;
     gr4pm_rotator* a_cfc = nullptr;
     gr4pm_symbol_filter* a_symf = nullptr;
     gr4pm_syncword_wipeoff* a_wipe = nullptr;
@@ -682,7 +685,7 @@ gr4pm_status gr4pm_packet_receiver::predecode(Slot& s, const gr4pm_c64* y)
         }
     }
     const size_t k = starts.size();
-    const size_t tail_len = kW + kPre;
+    const size_t tail_len = static_cast<size_t>(kW) + kPre;
     if (k) {
         if (a_starts.n < k) GR4PM_TRY(a_starts.alloc(k * 2));
         if (a_compact.n < k * kW) GR4PM_TRY(a_compact.alloc(k * kW * 2));
@@ -931,10 +934,11 @@ gr4pm_status gr4pm_packet_receiver::stage2_decode(Slot& s)
                                                   &ignored, s.pm_spans));
     if (consumed != n) {
         // PayloadMetadataInsert has reached the payload of a packet whose header is still pending: pass A decodes a
-        // header from a 912-item window, and a detection within the last ~848 items of a batch gets its message with
-        // the NEXT batch (invalid_header == 2, gr4pm_payload_metadata_insert_resolve) -- while the real chain may
-        // already have produced the packet's 192 syncword + header symbols when the batch ends 816 .. 848 items behind
-        // the tag.  The reference block waits there (payload_metadata_insert.hpp:243-247); so does this stage: the few
+        // header from a window of 228 symbols (kW items, 16 of the symbols in front of the tag), and a detection within
+        // the last 212 symbols of a batch gets its message with the NEXT batch (invalid_header == 2,
+        // gr4pm_payload_metadata_insert_resolve) -- while the real chain may already have produced the packet's 192
+        // syncword + header symbols when the batch ends 204 .. 212 symbols behind the tag (816 .. 848 items at 4 samples
+        // per symbol).  The reference block waits there (payload_metadata_insert.hpp:243-247); so does this stage: the few
         // symbols it could not take (and their tags) are carried to the front of the next batch.  (Round 3 failed the
         // batch here: one cut in ~200 random ones, found by tools/stress_receiver.py ... decode.)
         const size_t rest = n - consumed;
@@ -1072,8 +1076,8 @@ gr4pm_status gr4pm_packet_receiver::stage3_decode(Slot& s)
         const gr4pm_header_msg given = used_msgs.front();
         used_msgs.pop_front();
         if (given.invalid_header == 2) {
-            // pass A's message for this packet is still pending (it arrives with the next batch: a batch that ends 816 ..
-            // 848 items behind the syncword, stage2_decode) while the chain has already decoded the header itself
+            // pass A's message for this packet is still pending (it arrives with the next batch: a batch that ends 204 ..
+            // 212 symbols behind the syncword, stage2_decode) while the chain has already decoded the header itself
             early_hdrs.push_back(got);
             continue;
         }
@@ -1175,6 +1179,16 @@ gr4pm_status gr4pm_packet_receiver_create(const gr4pm_packet_receiver_params* p,
 try {
     if (!p || !out || p->samples_per_symbol == 0 || p->max_items < 2048) return GR4PM_ERR_INVALID;
     *out = nullptr;
+    if (p->decode_headers && p->samples_per_symbol < 4) {
+        // SymbolFilter's tag-driven clock phase (symbol_filter.hpp:141-197) moves by one sample through two special cases
+        // written for 4 samples per symbol: at 2 the first one (0 -> 1, then one more) leaves the clock half a symbol off
+        // for the packet.  The blocks stay the reference's bit for bit, so the front end exists at these rates, but its
+        // symbols do not decode: of twelve packets at Es/N0 = 20 dB the reference chain itself (the CPU oracle's blocks,
+        // several seeds) loses all at 1, seven to ten at 2 and one to five at 3, none at 4 .. 8.
+        set_error("decode_headers needs at least 4 samples per symbol (%zu given): below that the reference's symbol "
+                  "filter loses the symbol clock at a detection and no header decodes", p->samples_per_symbol);
+        return GR4PM_ERR_INVALID;
+    }
     GR4PM_TRY(require_device());
     auto* h = new (std::nothrow) gr4pm_packet_receiver;
     if (!h) return GR4PM_ERR_NOMEM;
@@ -1300,10 +1314,12 @@ try {
         if ((st = h->b_loop.create(p->header_alist, s2)) != GR4PM_OK) return bail(st); // :131-139
         gr4pm_crc_check_params cc{ 32, 0x4C11DB7, 0xFFFFFFFF, 0xFFFFFFFF, 1, 1, 0, 1, 0, s2 }; // :145-147
         if ((st = gr4pm_crc_check_create(&cc, &h->crc)) != GR4PM_OK) return bail(st);
-        const size_t tail_len = gr4pm_packet_receiver::kW + gr4pm_packet_receiver::kPre;
+        h->kPre = static_cast<unsigned>(gr4pm_packet_receiver::kPreSymbols * sps);
+        h->kW = static_cast<unsigned>(gr4pm_packet_receiver::kWSymbols * sps);
+        const size_t tail_len = static_cast<size_t>(h->kW) + h->kPre;
         if ((st = h->a_tail.alloc(tail_len)) != GR4PM_OK) return bail(st);
         if ((st = h->a_tail.zero(s1)) != GR4PM_OK) return bail(st);
-        if ((st = h->a_head.alloc(tail_len + gr4pm_packet_receiver::kW)) != GR4PM_OK) return bail(st);
+        if ((st = h->a_head.alloc(tail_len + h->kW)) != GR4PM_OK) return bail(st);
         if (hipStreamSynchronize(s1) != hipSuccess) return bail(GR4PM_ERR_HIP);
     }
     const size_t tags_cap = std::max<size_t>(p->tags_cap, 64);
@@ -1435,9 +1451,8 @@ gr4pm_status gr4pm_packet_receiver_submit(gr4pm_packet_receiver* h, const gr4pm_
 try {
     if (!h || !in || !out_symbols || (h->p.soft_bits && !h->p.packets_only && !out_llr) || (h->p.decode_headers && !out_packets))
         return GR4PM_ERR_INVALID;
-    if (h->p.decode_headers && n_in < gr4pm_packet_receiver::kW + gr4pm_packet_receiver::kPre + 2048) {
-        set_error("decode_headers needs batches of at least %u items",
-                  gr4pm_packet_receiver::kW + gr4pm_packet_receiver::kPre + 2048);
+    if (h->p.decode_headers && n_in < static_cast<size_t>(h->kW) + h->kPre + 2048) {
+        set_error("decode_headers needs batches of at least %u items", h->kW + h->kPre + 2048u);
         return GR4PM_ERR_INVALID;
     }
     if (h->inflight >= gr4pm_packet_receiver_max_inflight()) {

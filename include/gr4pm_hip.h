@@ -695,7 +695,8 @@ typedef struct {
     size_t tags_cap;           /* most detections per batch */
     int pipelined;             /* 0: submit() runs the three stages itself */
     int soft_bits;             /* continue to the LLR decoder (:123-131) */
-    int decode_headers;        /* (needs soft_bits) close the header feedback loop on the device and run the
+    int decode_headers;        /* (needs soft_bits and samples_per_symbol >= 4: create refuses the mode below that with
+                                  GR4PM_ERR_INVALID) close the header feedback loop on the device and run the
                                   payload tail: descrambler, HeaderPayloadSplit, HeaderFecDecoder, HeaderParser
                                   (:131-139) answer SyncwordDetectionFilter and PayloadMetadataInsert instead of
                                   packet_length; BinarySlicer, PackBits, CrcCheck (:140-147) deliver the packets.
@@ -756,8 +757,12 @@ void gr4pm_packet_receiver_destroy(gr4pm_packet_receiver* h);
  * stream relative to in[0] when `in` is a window of a device ring (the chain then reads the
  * delayed stream in place).  next_in/next_n: the following batch (look-ahead) or NULL.
  * out_symbols (device, out_cap >= n_in / samples_per_symbol + tags + 2) and out_llr (device,
- * soft_bits, 2 floats per symbol) and out_packets (device, decode_headers, n_in / 16 bytes is
- * always enough) stay the caller's; the result points at them.  The receiver works on streams of its
+ * soft_bits, 2 floats per symbol) and out_packets (device, decode_headers; a QPSK stream carries at most
+ * n_in / (4 samples_per_symbol) payload bytes, n_in / 16 at the lowest rate that decode_headers takes, plus the
+ * packet a batch finishes for the one before) stay the caller's; the result points at them.  decode_headers: a batch
+ * has at least (228 + 16) samples_per_symbol + 2048 items (3024 at 4 samples per symbol) -- the first pass decodes
+ * every detection's header from a window of 228 symbols that begins 16 symbols in front of the tag; a shorter batch
+ * is refused with GR4PM_ERR_INVALID.  The receiver works on streams of its
  * own, which are not ordered against the caller's: `in` (and `next_in`, and what announce names) must be
  * complete when the call is made. */
 gr4pm_status gr4pm_packet_receiver_submit(gr4pm_packet_receiver* h, const gr4pm_c64* in, size_t n_in,

@@ -3349,15 +3349,19 @@ def test_tag_driven_costas_chains_in_the_32_register_form():
 
 @pytest.mark.parametrize("tool,cases,env", [("fuzz_detector.py", 8, {}), ("fuzz_cfc_symf.py", 6, {}), ("fuzz_costas.py", 9, {}),
                                             ("fuzz_costas.py", 9, {"GR4PM_COSTAS_FORM": "1"}),
-                                            ("fuzz_costas.py", 12, {"GR4PM_COSTAS_FORM": "2", "GR4PM_COSTAS_CAP_MIN_LOG2": "0"})])
+                                            ("fuzz_costas.py", 12, {"GR4PM_COSTAS_FORM": "2", "GR4PM_COSTAS_CAP_MIN_LOG2": "0"}),
+                                            ("fuzz_cfc_symf.py --sps 2", 6, {}), ("fuzz_cfc_symf.py --sps 3", 6, {}),
+                                            ("fuzz_cfc_symf.py --sps 8", 6, {})])
 def test_randomised_differential_tools(tool, cases, env):
     """a few cases of every randomised differential test under tools/ (random settings, tags, chunkings against the
     oracle; the long runs are quoted in HISTORY.md section 2).  GR4PM_COSTAS_FORM: the PLL kernel's 62-VGPR form and the
-    32-VGPR form the pipelined receivers run -- the same bits."""
+    32-VGPR form the pipelined receivers run -- the same bits.  --sps: the fused CFC + SymbolFilter at the receivers'
+    design for 2, 3 and 8 samples per symbol (the generic kernel; the row without it runs k_symbol_filter_fast)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", tool), str(cases), "12345"], capture_output=True,
+    tool, *options = tool.split()
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", tool), str(cases), "12345", *options], capture_output=True,
                        text=True, timeout=600, env=dict(os.environ, **env))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert f"{cases} of {cases} cases agree" in r.stdout

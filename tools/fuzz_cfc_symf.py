@@ -3,7 +3,9 @@
 k_symf_wg_plan, k_symbol_filter_fast) against the CPU oracle: hundreds of detection tags at ragged distances (shorter
 than a checkpoint chunk, around the tile size, longer than the renormalisation period), random frequencies and time
 estimates, random call boundaries.  Symbols bit-exact, re-timed tag indices identical.
-tools/fuzz_cfc_symf.py [cases=10] [seed=1]"""
+--sps N: the receivers' design at N samples per symbol (arm of 11 N taps, filter delay n_rrc - 1, CFC delay
+(n_rrc - 1) / 2 + N); anything but 4 runs the generic k_symbol_filter.  The default, 4, draws the cases it always drew.
+tools/fuzz_cfc_symf.py [cases=10] [seed=1] [--sps N]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,9 +15,18 @@ import __graft_entry__ as ge
 import _oracle as orc
 import test_gpu_parity as tp
 pkg = ge.load_package()
-cases = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-rrc, pfb = tp._receiver_pfb()
+argv = sys.argv[1:]
+sps = 4
+if "--sps" in argv:
+    k = argv.index("--sps")
+    sps = int(argv[k + 1])
+    del argv[k:k + 2]
+assert 1 <= sps <= 8, "--sps: 1 to 8"
+cases = int(argv[0]) if len(argv) > 0 else 10
+rng = np.random.default_rng(int(argv[1]) if len(argv) > 1 else 1)
+rrc, norm = orc.unit_norm_rrc(sps)
+pfb = orc.rrc_taps(32.0 / float(norm), 32.0 * sps, 1.0, 0.35, 32 * sps * 11)[:-1]  # packet_receiver.hpp:100-110
+symf_delay, cfc_delay = rrc.size - 1, (rrc.size - 1) // 2 + sps                      # 44 and 26 at 4 samples per symbol
 bad = 0
 for case in range(cases):
     n = int(rng.integers(60000, 300000))
@@ -33,13 +44,14 @@ for case in range(cases):
     tags["phase"] = rng.uniform(-3, 3, idx.size)
     tags["freq"] = rng.uniform(-0.04, 0.04, idx.size)
     tags["flags"] = pkg.TAG_SYNCWORD
-    delay = int(rng.choice([0, 26]))
+    delay = int(rng.choice([0, cfc_delay]))
     z = orc.coarse_frequency_correction(x, tags["index"], tags["freq"], delay=delay)
-    want, want_tags, wc = orc.symbol_filter(z, pfb, 32, 4, 44, tags=tags.astype(orc.TAG_DTYPE), out_cap=n // 4 + idx.size + 16)
+    want, want_tags, wc = orc.symbol_filter(z, pfb, 32, sps, symf_delay, tags=tags.astype(orc.TAG_DTYPE),
+                                            out_cap=n // sps + idx.size + 16)
     assert wc == n
     cuts = np.sort(rng.choice(np.arange(1, n), int(rng.integers(0, 6)), replace=False)).tolist()
     cuts = [0] + cuts + [n]
-    cfc, sf = pkg.CoarseFrequencyCorrection(delay), pkg.SymbolFilter(pfb, 32, 4, 44)
+    cfc, sf = pkg.CoarseFrequencyCorrection(delay), pkg.SymbolFilter(pfb, 32, sps, symf_delay)
     ys, ts, off = [], [], 0
     for lo, hi in zip(cuts[:-1], cuts[1:]):
         t = tags[(tags["index"] >= lo) & (tags["index"] < hi)].copy()
@@ -54,7 +66,7 @@ for case in range(cases):
     y, t = np.concatenate(ys), np.concatenate(ts)
     ok = y.size == want.size and np.array_equal(tp.bits(y), tp.bits(want)) and np.array_equal(t["index"], want_tags["index"])
     bad += not ok
-    print(f"case {case}: {n} items, {idx.size} tags, delay {delay}, {len(cuts) - 1} calls: {'ok' if ok else 'MISMATCH'}")
+    print(f"case {case}: sps {sps}, {n} items, {idx.size} tags, delay {delay}, {len(cuts) - 1} calls: {'ok' if ok else 'MISMATCH'}")
     if not ok:
         m = min(y.size, want.size)
         d = np.nonzero(tp.bits(y[:m]) != tp.bits(want[:m]))[0]
