@@ -10,17 +10,20 @@
 // k_fft_ddc_forward: the Spectrum's wave (spectrum.hip) without window and powers: one wave per run of consecutive
 //   segments on the one-exchange transform of fft2048_w64.hpp, fed by load_half_segment(); register j of lane l holds
 //   bin l + 64 j, and leaves as 32 rows of 64 consecutive bins to spec[segment][2048].
-// k_fft_ddc_channel: one wave per (segment, channel).  Lane l takes the folded bins v = l, l + 64, ...: R products
-//   X[(c + u) mod N] G[u] in ascending u, consecutive lanes on consecutive bins of the spectrum and of the table.  The
-//   B-point inverse transform is log2 B radix-2 autosort (Stockham) stages between two LDS buffers, natural order in and
-//   out, twiddles exp(+2 pi j m / 512) from a table made in double; then the kept items n' >= V / D take the rotator
-//   (the Ddc's: double sincospi of the exact phase, rounded to float, four fmaf from zero) and leave as hop / D
-//   consecutive frames of row k.
-// k_fft_ddc_mixed: the same wave (fft_ddc_channel_body(), one body for both kernels) with B, R, the kept items and the row
-//   from a per-channel descriptor, for the MixedFftDdc at the end of this file.
+// k_fft_ddc_mixed: one wave per (segment, channel), with B, R, the kept items and the row from a per-channel descriptor
+//   (k_fft_ddc_channel: the same body with them from the launch, for a bank whose channels are all alike).
+//   Lane l takes the folded bins v = l, l + 64, ...: R products X[(c + u) mod N] G[u] in ascending u, consecutive lanes on
+//   consecutive bins of the spectrum and of the table.  The B-point inverse transform is log2 B radix-2 autosort
+//   (Stockham) stages between two LDS buffers, natural order in and out, twiddles exp(+2 pi j m / 512) from a table made
+//   in double; then the kept items n' >= first take the rotator (the Ddc's: double sincospi of the exact phase, rounded
+//   to float, four fmaf from zero) and leave as hop / D consecutive frames of row k.
 // A launch pair covers at most kChunk segments, so the spectra of a call of any length stay within one 64 MiB buffer
 // that the next pair reuses in stream order.  No atomics, no scratch; every result is a function of (channel, frame,
 // stream) only, whatever the cuts into calls.
+// One handle (FftDdcBank), one create and one call serve both ABI types.  The MixedFftDdc gives every
+// channel its own D_k on the segment grid of Dmax; the FftDdc is the bank whose decimations are all equal, built by
+// gr4pm_fft_ddc_create from its scalars: Dmax = D, first = V / D, frames = hop / D, no zeros behind a row, and the
+// descriptors in channel order.  The call picks the channel kernel by what the bank holds, not by its ABI type.
 // Built with FFT_FLAGS: the transforms, the products and the fold may contract to FMA.  The rotator is written in
 // explicit fmaf (freq_xlate.hpp's cmac), so it is the Ddc's under either set of flags.
 #include "spectrum_segment.hpp"
@@ -37,16 +40,23 @@ namespace {
 namespace iq = gr4pm::iq;
 using namespace gr4pm;
 using gr4pm::hostlogic::fft_ddc_bin;
-using gr4pm::hostlogic::fft_ddc_default_overlap;
+using gr4pm::hostlogic::fft_ddc_mixed_channel;
+using gr4pm::hostlogic::fft_ddc_mixed_default_overlap;
+using gr4pm::hostlogic::fft_ddc_mixed_frames;
+using gr4pm::hostlogic::fft_ddc_mixed_max_decimation;
+using gr4pm::hostlogic::fft_ddc_mixed_table_offsets;
+using gr4pm::hostlogic::fft_ddc_mixed_validate;
+using gr4pm::hostlogic::fft_ddc_mixed_validate_channels;
 using gr4pm::hostlogic::fft_ddc_phi;
 using gr4pm::hostlogic::fft_ddc_plan;
 using gr4pm::hostlogic::fft_ddc_pow2;
 using gr4pm::hostlogic::fft_ddc_segment_index;
 using gr4pm::hostlogic::fft_ddc_shape;
 using gr4pm::hostlogic::fft_ddc_table_word;
-using gr4pm::hostlogic::fft_ddc_validate;
+using gr4pm::hostlogic::FftDdcMixedChannel;
+using gr4pm::hostlogic::FftDdcMixedRefusal;
+using gr4pm::hostlogic::FftDdcMixedVerdict;
 using gr4pm::hostlogic::FftDdcPlan;
-using gr4pm::hostlogic::FftDdcRefusal;
 using gr4pm::hostlogic::FftDdcShape;
 using gr4pm::hostlogic::kFftDdcMaxD;
 using gr4pm::hostlogic::kFftDdcMaxK;
@@ -119,21 +129,6 @@ __global__ __launch_bounds__(kW64Threads, 2) void k_fft_ddc_forward(FwdArgs a)
     }
 }
 
-struct ChanArgs {
-    const float2* spec; // [segments of the launch][2048]
-    const float2* G;    // [K][R B]: item t is u = t - R B / 2
-    const float2* tw;   // [256]
-    const uint32_t* w;  // [K] frequency words
-    float2* out;
-    size_t out_stride;
-    size_t frame0;      // the launch's first frame of the call's rows
-    uint64_t index0;    // absolute index of item 0 of the launch's first segment (its low 32 bits are all the phase needs)
-    uint32_t n_seg;
-    uint32_t D, logB, R;
-    uint32_t first;     // V / D
-    uint32_t hop;
-};
-
 // One wave's work for a (segment, channel), the arithmetic of both channel kernels: X the segment's spectrum, G the
 // channel's table (item t is u = t - R B / 2), w its frequency word, B = 2^logB; the items n' = first .. first + frames - 1 of the inverse
 // transform leave as o[0 .. frames - 1]; i0: the absolute index of the segment's item 0 (its low 32 bits).
@@ -191,18 +186,7 @@ __device__ __forceinline__ void fft_ddc_channel_body(const float2* __restrict__ 
     }
 }
 
-// blockIdx.x: the segment of the launch, blockIdx.y: the channel; 64 threads
-__global__ __launch_bounds__(64) void k_fft_ddc_channel(ChanArgs a)
-{
-    const uint32_t seg = blockIdx.x, k = blockIdx.y;
-    const uint32_t B = 1u << a.logB, RB = a.R << a.logB;
-    const uint32_t frames = B - a.first;
-    fft_ddc_channel_body(a.tw, a.spec + static_cast<size_t>(seg) * kN, a.G + static_cast<size_t>(k) * RB, a.w + k, a.logB, a.R, a.first, a.D,
-                         frames, static_cast<uint32_t>(a.index0) + seg * a.hop,
-                         a.out + static_cast<size_t>(k) * a.out_stride + a.frame0 + static_cast<size_t>(seg) * frames);
-}
-
-// What the MixedFftDdc's kernel takes per channel in the place of launch-wide constants.  The table is ordered by
+// What the channel kernel takes per channel in the place of launch-wide constants.  The table is ordered by
 // descending B, so the workgroups with the longest inverse transforms are dispatched first.
 struct MixedDesc {
     uint32_t w;      // the frequency word
@@ -214,6 +198,35 @@ struct MixedDesc {
     uint32_t table;  // the channel's first item of G
     uint32_t row;    // the output row
 };
+
+// A bank whose channels all have one D and one R: what the descriptors say is the same for every channel, and goes with
+// the launch (measured: a uniform K = 24 is 0.3 to 0.6 % faster this way, and K = 64 another 0.4 to 0.9 % with the words
+// packed and not 32 bytes apart in the descriptors: profiles/fft_ddc_bench.txt).  The tables are R B items apart then.
+struct ChanArgs {
+    const float2* spec;    // [segments of the launch][2048]
+    const float2* G;       // [K][R B]: item t is u = t - R B / 2
+    const float2* tw;      // [256]
+    const uint32_t* w;     // [K] frequency words, packed: a workgroup's first load, and 64 of them are four cache lines
+    float2* out;
+    size_t out_stride;
+    size_t frame0;         // the launch's first frame of the call's rows
+    uint64_t index0;       // absolute index of item 0 of the launch's first segment
+    uint32_t D, logB, R;
+    uint32_t first;        // V / D
+    uint32_t hop;
+};
+
+// blockIdx.x: the segment of the launch, blockIdx.y: the channel; 64 threads.  The body is k_fft_ddc_mixed's below, so the
+// bits are
+__global__ __launch_bounds__(64) void k_fft_ddc_channel(ChanArgs a)
+{
+    const uint32_t seg = blockIdx.x, k = blockIdx.y;
+    const uint32_t B = 1u << a.logB, RB = a.R << a.logB;
+    const uint32_t frames = B - a.first;
+    fft_ddc_channel_body(a.tw, a.spec + static_cast<size_t>(seg) * kN, a.G + static_cast<size_t>(k) * RB, a.w + k, a.logB, a.R, a.first, a.D,
+                         frames, static_cast<uint32_t>(a.index0) + seg * a.hop,
+                         a.out + static_cast<size_t>(k) * a.out_stride + a.frame0 + static_cast<size_t>(seg) * frames);
+}
 
 struct MixedArgs {
     const float2* spec;    // [segments of the launch][2048]
@@ -269,135 +282,279 @@ gr4pm_status check_decimation(size_t D)
     return GR4PM_OK;
 }
 
-// What both handles hold for the stream and the shared forward transform, and what their calls do alike.
-struct FftDdcCore {
+// The one handle behind both ABI types: K channels with a decimation each on the segment grid of (Dmax, V).  An FftDdc is
+// the bank whose decimations are all equal: Dmax = D, every row takes shape.frames frames a segment and no zeros follow.
+struct FftDdcBank {
+    virtual ~FftDdcBank() = default; // the ABI types derive from it and are deleted through it
+    const char* name = ""; // of the entry points' messages: fft_ddc or fft_ddc_mixed
+    size_t K = 0, V = 0;
+    uint32_t max_frames = 0; // hop / min D_k
+    MixedDesc alike = {};    // a channel's sizes where all channels have one D and one R (logB != 0 then): k_fft_ddc_channel serves
     uint64_t start_index = 0;
     uint64_t taken = 0; // samples since create or reset
-    FftDdcShape shape = {};
+    FftDdcShape shape = {}; // of (Dmax, V)
     hipStream_t stream = nullptr;
     size_t max_waves = 2048; // of one forward launch: eight per compute unit, at most 2048
     gr4pm::StreamTail tail; // keep = 0, frame = N: the virtual items of the incomplete segment
+    std::vector<uint32_t> words;
+    std::vector<FftDdcMixedChannel> channels;
     gr4pm::DevBuf<float4> d_tT;
     gr4pm::DevBuf<cf> d_cc, d_spec;
-    gr4pm::DevBuf<float2> d_tw;
-
-    // the segment grid of (D, V), the forward transform's tables, the inverse transforms' twiddles, the spectra and the tail
-    gr4pm_status init(size_t D, size_t V, uint64_t start, void* on_stream)
-    {
-        start_index = start;
-        shape = fft_ddc_shape(static_cast<uint32_t>(D), static_cast<uint32_t>(V));
-        stream = static_cast<hipStream_t>(on_stream);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            max_waves = std::min(max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
-        std::vector<float4> tT(kW64TwFloat4);
-        std::vector<cf> cc(64);
-        build_w64_tables(
-            [](int k) {
-                const double ang = -2.0 * M_PI * k / kFftN;
-                return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
-            },
-            tT.data(), cc.data());
-        std::vector<float2> tw(kTwiddles);
-        for (int m = 0; m < kTwiddles; ++m) {
-            double cs, sn;
-            unit_phasor(static_cast<uint32_t>(m) << 23, cs, sn); // m / 512 of a turn
-            tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
-        }
-        GR4PM_TRY(d_tT.alloc(tT.size()));
-        GR4PM_TRY(d_cc.alloc(cc.size()));
-        GR4PM_TRY(d_tw.alloc(tw.size()));
-        GR4PM_TRY(d_spec.alloc(kChunk * kN));
-        GR4PM_TRY(d_tT.upload(tT.data(), tT.size(), stream));
-        GR4PM_TRY(d_cc.upload(cc.data(), cc.size(), stream));
-        GR4PM_TRY(d_tw.upload(tw.data(), tw.size(), stream));
-        GR4PM_HIP_TRY(hipStreamSynchronize(stream)); // the uploads read this function's vectors
-        return tail.alloc(0, kN, 1, stream);
-    }
-
-    // A call that was validated: per launch pair the forward kernel, then channels(done, segs), which launches the
-    // handle's channel kernel for the segments [done, done + segs) of the call; then the tail.  format iq::kC64 for
-    // complex64 samples
-    template <class Channels>
-    gr4pm_status run(const FftDdcPlan& p, const void* in, int format, float scale, size_t n_in, Channels&& channels)
-    {
-        // the samples in front of the virtual stream (V = 0 only) belong to no frame
-        const size_t item = format == iq::kC64 ? sizeof(float2) : iq::item_bytes(format);
-        const void* x = static_cast<const char*>(in) + p.drop * item;
-        const StreamTail::Plan t = {tail.d_hist[tail.cur].p, tail.d_hist[1 - tail.cur].p, p.tail, p.n_segments, p.tail_new, p.tail_new};
-        FwdArgs a = {};
-        a.hist = t.hist, a.in = x, a.H = p.tail;
-        a.tT = d_tT.p, a.cc = d_cc.p, a.spec = d_spec.p;
-        a.hop = shape.hop, a.scale = scale;
-        iq::with_format(format, [&](auto f) {
-            for (size_t done = 0; done < p.n_segments;) {
-                const size_t segs = std::min(p.n_segments - done, kChunk);
-                const size_t per_wave = (segs + max_waves - 1) / max_waves;
-                const size_t waves = (segs + per_wave - 1) / per_wave;
-                a.seg0 = done, a.n_seg = static_cast<uint32_t>(segs), a.run = static_cast<uint32_t>(per_wave);
-                hipLaunchKernelGGL(k_fft_ddc_forward<decltype(f)::value>, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)),
-                                   dim3(kW64Threads), 0, stream, a);
-                channels(done, segs);
-                done += segs;
-            }
-            tail.launch_history<decltype(f)::value>(t, x, 0, p.n_used, scale, stream);
-        });
-        GR4PM_HIP_TRY(hipGetLastError());
-        tail.commit(t);
-        taken += n_in;
-        return GR4PM_OK;
-    }
+    gr4pm::DevBuf<float2> d_tw, d_G;
+    gr4pm::DevBuf<MixedDesc> d_desc;
+    gr4pm::DevBuf<uint32_t> d_w; // the words again, packed, for k_fft_ddc_channel
 };
+
+// The create of both handles, behind the fronts' checks of their own arguments: words the K frequency words, D and R per
+// channel, taps[k] channel k's prototype or empty for the default design of taps_per_phase D_k taps, overlap < 0 for the
+// default.  Messages speak of the arrays of gr4pm_fft_ddc_mixed_params; the FftDdc's front has refused every scalar they
+// could name before it calls this.
+gr4pm_status create_bank(FftDdcBank& h, const char* name, std::vector<uint32_t> words, const std::vector<size_t>& D,
+                         const std::vector<size_t>& R, std::vector<std::vector<float>> taps, size_t taps_per_phase, ptrdiff_t overlap,
+                         uint64_t start_index, void* stream)
+{
+    const size_t K = words.size();
+    std::vector<size_t> L(K);
+    for (size_t k = 0; k < K; ++k) {
+        if (!fft_ddc_pow2(D[k]) || D[k] < kFftDdcMinD || D[k] > kFftDdcMaxD) {
+            set_error("%s: decimations[%zu] must be a power of two in [%u, %u], not %zu", name, k, kFftDdcMinD, kFftDdcMaxD, D[k]);
+            return GR4PM_ERR_INVALID;
+        }
+        if (taps[k].empty() && (taps_per_phase < 1 || taps_per_phase * D[k] > kN)) {
+            set_error("%s: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", name, taps_per_phase, D[k], kN);
+            return GR4PM_ERR_INVALID;
+        }
+        L[k] = taps[k].empty() ? taps_per_phase * D[k] : taps[k].size();
+    }
+    const FftDdcMixedVerdict sizes = fft_ddc_mixed_validate_channels(K, D.data(), R.data(), L.data());
+    if (sizes.refusal == FftDdcMixedRefusal::images) {
+        set_error("%s: images[%zu] must be a power of two in [1, %zu], not %zu", name, sizes.channel, D[sizes.channel], R[sizes.channel]);
+        return GR4PM_ERR_INVALID;
+    }
+    if (sizes.refusal != FftDdcMixedRefusal::none) {
+        set_error("%s: invalid sizes of channel %zu", name, sizes.channel);
+        return GR4PM_ERR_INVALID;
+    }
+    for (size_t k = 0; k < K; ++k) {
+        if (taps[k].empty()) {
+            taps[k].resize(L[k]);
+            GR4PM_TRY(gr4pm_ddc_taps(D[k], taps_per_phase, 0.25, 0.75, taps[k].data()));
+        }
+        for (size_t t = 0; t < L[k]; ++t)
+            if (!std::isfinite(taps[k][t])) {
+                set_error("%s: taps[%zu] of channel %zu is not finite", name, t, k);
+                return GR4PM_ERR_INVALID;
+            }
+    }
+    const size_t Dmax = fft_ddc_mixed_max_decimation(K, D.data());
+    const size_t V = overlap < 0 ? fft_ddc_mixed_default_overlap(K, D.data(), L.data()) : static_cast<size_t>(overlap);
+    const FftDdcMixedVerdict v = fft_ddc_mixed_validate(K, D.data(), R.data(), L.data(), V);
+    switch (v.refusal) {
+    case FftDdcMixedRefusal::none: break;
+    case FftDdcMixedRefusal::overlap_multiple:
+        set_error("%s: the overlap %zu is no multiple of the largest decimation %zu", name, V, Dmax);
+        return GR4PM_ERR_INVALID;
+    case FftDdcMixedRefusal::overlap_low:
+        set_error("%s: the overlap %zu is below the reach of channel %zu: %zu taps at a decimation of %zu beside %zu need %zu", name, V,
+                  v.channel, L[v.channel], D[v.channel], Dmax, Dmax - D[v.channel] + L[v.channel] - 1);
+        return GR4PM_ERR_INVALID;
+    case FftDdcMixedRefusal::overlap_high:
+        set_error("%s: the overlap %zu leaves a hop below %u: at most %zu", name, V, kFftDdcMinHop, kN - kFftDdcMinHop);
+        return GR4PM_ERR_INVALID;
+    default: set_error("%s: invalid sizes", name); return GR4PM_ERR_INVALID;
+    }
+    GR4PM_TRY(require_device());
+    h.name = name, h.K = K, h.V = V;
+    h.words = std::move(words);
+    h.start_index = start_index;
+    h.shape = fft_ddc_shape(static_cast<uint32_t>(Dmax), static_cast<uint32_t>(V));
+    h.stream = static_cast<hipStream_t>(stream);
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+        h.max_waves = std::min(h.max_waves, static_cast<size_t>(prop.multiProcessorCount) * kW64Waves);
+    std::vector<float4> tT(kW64TwFloat4);
+    std::vector<cf> cc(64);
+    build_w64_tables(
+        [](int k) {
+            const double ang = -2.0 * M_PI * k / kFftN;
+            return mk(static_cast<float>(std::cos(ang)), static_cast<float>(std::sin(ang)));
+        },
+        tT.data(), cc.data());
+    std::vector<float2> tw(kTwiddles);
+    for (int m = 0; m < kTwiddles; ++m) {
+        double cs, sn;
+        unit_phasor(static_cast<uint32_t>(m) << 23, cs, sn); // m / 512 of a turn
+        tw[m] = float2{static_cast<float>(cs), static_cast<float>(sn)};
+    }
+    std::vector<size_t> offsets(K);
+    std::vector<float2> G(fft_ddc_mixed_table_offsets(K, D.data(), R.data(), offsets.data()));
+    std::vector<MixedDesc> desc(K);
+    h.channels.resize(K);
+    for (size_t k = 0; k < K; ++k) {
+        const uint32_t w = h.words[k], c = fft_ddc_bin(w);
+        const size_t RB = R[k] * (kN / D[k]);
+        for (size_t t = 0; t < RB; ++t)
+            G[offsets[k] + t] = response(taps[k], w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
+        h.channels[k] = fft_ddc_mixed_channel(static_cast<uint32_t>(Dmax), static_cast<uint32_t>(V), static_cast<uint32_t>(D[k]));
+        h.max_frames = std::max(h.max_frames, h.channels[k].frames);
+        desc[k] = MixedDesc{w, static_cast<uint32_t>(__builtin_ctzll(kN / D[k])), static_cast<uint32_t>(R[k]), h.channels[k].first,
+                            static_cast<uint32_t>(D[k]), h.channels[k].frames, static_cast<uint32_t>(offsets[k]), static_cast<uint32_t>(k)};
+    }
+    if (std::all_of(desc.begin(), desc.end(), [&](const MixedDesc& d) { return d.D == desc[0].D && d.R == desc[0].R; })) h.alike = desc[0];
+    // the longest inverse transforms first: a workgroup at B = 512 costs many times one at B = 32
+    std::stable_sort(desc.begin(), desc.end(), [](const MixedDesc& x, const MixedDesc& y) { return x.logB > y.logB; });
+    GR4PM_TRY(h.d_tT.alloc(tT.size()));
+    GR4PM_TRY(h.d_cc.alloc(cc.size()));
+    GR4PM_TRY(h.d_tw.alloc(tw.size()));
+    GR4PM_TRY(h.d_spec.alloc(kChunk * kN));
+    GR4PM_TRY(h.tail.alloc(0, kN, 1, h.stream));
+    GR4PM_TRY(h.d_G.alloc(G.size()));
+    GR4PM_TRY(h.d_desc.alloc(K));
+    GR4PM_TRY(h.d_w.alloc(K));
+    GR4PM_TRY(h.d_tT.upload(tT.data(), tT.size(), h.stream));
+    GR4PM_TRY(h.d_cc.upload(cc.data(), cc.size(), h.stream));
+    GR4PM_TRY(h.d_tw.upload(tw.data(), tw.size(), h.stream));
+    GR4PM_TRY(h.d_G.upload(G.data(), G.size(), h.stream));
+    GR4PM_TRY(h.d_desc.upload(desc.data(), K, h.stream));
+    GR4PM_TRY(h.d_w.upload(h.words.data(), K, h.stream));
+    GR4PM_HIP_TRY(hipStreamSynchronize(h.stream)); // the uploads read this function's vectors
+    return GR4PM_OK;
+}
+
+gr4pm_status check_samples(const FftDdcBank& h, size_t n_in)
+{
+    if (n_in > (size_t(1) << 40)) {
+        set_error("%s: %zu samples in one call, at most 2^40", h.name, n_in);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    return GR4PM_OK;
+}
+
+// frames per row of a call: counts[k]
+void frames_of(const FftDdcBank& h, const FftDdcPlan& p, size_t* counts)
+{
+    for (size_t k = 0; k < h.K; ++k) counts[k] = fft_ddc_mixed_frames(p, h.channels[k]);
+}
+
+// The call of both handles: per launch pair of at most kChunk segments the forward kernel, then the channel kernel; then
+// the tail.  format iq::kC64 for complex64 samples; counts[K]
+gr4pm_status process_any(FftDdcBank& h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                         size_t out_cap_frames, size_t* counts)
+{
+    std::fill(counts, counts + h.K, size_t(0));
+    GR4PM_TRY(check_samples(h, n_in));
+    if (n_in == 0) return GR4PM_OK;
+    if (!in) {
+        set_error("%s: no input array", h.name);
+        return GR4PM_ERR_INVALID;
+    }
+    const FftDdcPlan p = fft_ddc_plan(h.shape, h.taken, n_in);
+    const size_t longest = p.n_segments * h.max_frames;
+    if (longest > out_cap_frames) {
+        set_error("%s: %zu frames a row, room for %zu", h.name, longest, out_cap_frames);
+        return GR4PM_ERR_OVERFLOW;
+    }
+    if (longest && (!out || (h.K > 1 && out_stride < longest))) {
+        set_error("%s: no output array, or a row stride of %zu items for %zu frames", h.name, out_stride, longest);
+        return GR4PM_ERR_INVALID;
+    }
+    // the samples in front of the virtual stream (V = 0 only) belong to no frame
+    const size_t item = format == iq::kC64 ? sizeof(float2) : iq::item_bytes(format);
+    const void* x = static_cast<const char*>(in) + p.drop * item;
+    const StreamTail::Plan t = {h.tail.d_hist[h.tail.cur].p, h.tail.d_hist[1 - h.tail.cur].p, p.tail, p.n_segments, p.tail_new, p.tail_new};
+    FwdArgs a = {};
+    a.hist = t.hist, a.in = x, a.H = p.tail;
+    a.tT = h.d_tT.p, a.cc = h.d_cc.p, a.spec = h.d_spec.p;
+    a.hop = h.shape.hop, a.scale = scale;
+    MixedArgs b = {};
+    b.spec = reinterpret_cast<const float2*>(h.d_spec.p), b.G = h.d_G.p, b.tw = h.d_tw.p, b.desc = h.d_desc.p;
+    b.out = reinterpret_cast<float2*>(out), b.out_stride = out_stride;
+    b.call_segments = p.n_segments, b.hop = h.shape.hop, b.max_frames = h.max_frames;
+    ChanArgs c = {};
+    c.spec = b.spec, c.G = b.G, c.tw = b.tw, c.w = h.d_w.p, c.out = b.out, c.out_stride = out_stride;
+    c.D = h.alike.D, c.logB = h.alike.logB, c.R = h.alike.R, c.first = h.alike.first, c.hop = h.shape.hop;
+    iq::with_format(format, [&](auto f) {
+        for (size_t done = 0; done < p.n_segments;) {
+            const size_t segs = std::min(p.n_segments - done, kChunk);
+            const size_t per_wave = (segs + h.max_waves - 1) / h.max_waves;
+            const size_t waves = (segs + per_wave - 1) / per_wave;
+            a.seg0 = done, a.n_seg = static_cast<uint32_t>(segs), a.run = static_cast<uint32_t>(per_wave);
+            hipLaunchKernelGGL(k_fft_ddc_forward<decltype(f)::value>, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)),
+                               dim3(kW64Threads), 0, h.stream, a);
+            const dim3 grid(static_cast<unsigned>(segs), static_cast<unsigned>(h.K));
+            b.seg0 = done, c.frame0 = done * h.alike.frames;
+            b.index0 = c.index0 = fft_ddc_segment_index(h.shape, h.start_index, p.segments_before + done);
+            if (h.alike.logB)
+                hipLaunchKernelGGL(k_fft_ddc_channel, grid, dim3(64), 0, h.stream, c);
+            else
+                hipLaunchKernelGGL(k_fft_ddc_mixed, grid, dim3(64), 0, h.stream, b);
+            done += segs;
+        }
+        h.tail.launch_history<decltype(f)::value>(t, x, 0, p.n_used, scale, h.stream);
+    });
+    GR4PM_HIP_TRY(hipGetLastError());
+    h.tail.commit(t);
+    h.taken += n_in;
+    frames_of(h, p, counts);
+    return GR4PM_OK;
+}
+
+// process_iq() of both handles
+gr4pm_status process_iq(FftDdcBank& h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out, size_t out_stride,
+                        size_t out_cap_frames, size_t* counts)
+{
+    std::fill(counts, counts + h.K, size_t(0));
+    if (!iq::valid(format)) {
+        set_error("%s: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", h.name, format);
+        return GR4PM_ERR_INVALID;
+    }
+    return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames, counts);
+}
+
+gr4pm_status frames_for(const FftDdcBank& h, size_t n_in, size_t* counts)
+{
+    std::fill(counts, counts + h.K, size_t(0));
+    GR4PM_TRY(check_samples(h, n_in));
+    frames_of(h, fft_ddc_plan(h.shape, h.taken, n_in), counts);
+    return GR4PM_OK;
+}
+
+void destroy(FftDdcBank* h)
+{
+    if (!h) return;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+}
+
+gr4pm_status reset(FftDdcBank* h)
+{
+    if (!h) return GR4PM_ERR_INVALID;
+    GR4PM_TRY(h->tail.reset(h->stream));
+    h->taken = 0;
+    return GR4PM_OK;
+}
+
+gr4pm_status frequencies(const FftDdcBank* h, double* out)
+{
+    if (!h || !out) return GR4PM_ERR_INVALID;
+    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
+    return GR4PM_OK;
+}
+
+gr4pm_status sizes(const FftDdcBank* h, size_t* overlap, size_t* hop)
+{
+    if (!h || !overlap || !hop) return GR4PM_ERR_INVALID;
+    *overlap = h->V;
+    *hop = h->shape.hop;
+    return GR4PM_OK;
+}
 
 } // namespace
 
-struct gr4pm_fft_ddc : FftDdcCore {
-    size_t K = 0, D = 0, R = 0, V = 0;
-    std::vector<uint32_t> words;
-    gr4pm::DevBuf<float2> d_G;
-    gr4pm::DevBuf<uint32_t> d_w;
-};
-
-// process() and process_iq(): format iq::kC64 for complex64 samples
-static gr4pm_status process_any(gr4pm_fft_ddc* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
-                                size_t out_stride, size_t out_cap_frames, size_t* n_frames)
-{
-    if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    *n_frames = 0;
-    if (n_in > (size_t(1) << 40)) {
-        set_error("fft_ddc: %zu samples in one call, at most 2^40", n_in);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (n_in == 0) return GR4PM_OK;
-    if (!in) {
-        set_error("fft_ddc: no input array");
-        return GR4PM_ERR_INVALID;
-    }
-    const FftDdcPlan p = fft_ddc_plan(h->shape, h->taken, n_in);
-    if (p.frames > out_cap_frames) {
-        set_error("fft_ddc: %zu frames, room for %zu", p.frames, out_cap_frames);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (p.frames && (!out || (h->K > 1 && out_stride < p.frames))) {
-        set_error("fft_ddc: no output array, or a row stride of %zu items for %zu frames", out_stride, p.frames);
-        return GR4PM_ERR_INVALID;
-    }
-    ChanArgs b = {};
-    b.spec = reinterpret_cast<const float2*>(h->d_spec.p), b.G = h->d_G.p, b.tw = h->d_tw.p, b.w = h->d_w.p;
-    b.out = reinterpret_cast<float2*>(out), b.out_stride = out_stride;
-    b.D = static_cast<uint32_t>(h->D), b.R = static_cast<uint32_t>(h->R);
-    b.logB = static_cast<uint32_t>(__builtin_ctzll(kN / h->D));
-    b.first = h->shape.first, b.hop = h->shape.hop;
-    GR4PM_TRY(h->run(p, in, format, scale, n_in, [&](size_t done, size_t segs) {
-        b.n_seg = static_cast<uint32_t>(segs);
-        b.frame0 = done * h->shape.frames;
-        b.index0 = fft_ddc_segment_index(h->shape, h->start_index, p.segments_before + done);
-        hipLaunchKernelGGL(k_fft_ddc_channel, dim3(static_cast<unsigned>(segs), static_cast<unsigned>(h->K)), dim3(64), 0, h->stream, b);
-    }));
-    *n_frames = p.frames;
-    return GR4PM_OK;
-}
+// distinct types for the ABI, one bank behind both
+struct gr4pm_fft_ddc : FftDdcBank {};
+struct gr4pm_fft_ddc_mixed : FftDdcBank {};
 
 extern "C" {
 
@@ -409,6 +566,7 @@ try {
 }
 GR4PM_ABI_CATCH
 
+// the bank of K equal channels, behind the checks that name this entry's own scalars
 gr4pm_status gr4pm_fft_ddc_create(const gr4pm_fft_ddc_params* p, gr4pm_fft_ddc** out)
 try {
     if (!p || !out) return GR4PM_ERR_INVALID;
@@ -422,108 +580,79 @@ try {
         return GR4PM_ERR_INVALID;
     }
     GR4PM_TRY(prototype_length("fft_ddc", p->taps, p->n_taps, kN));
-    std::vector<float> taps;
-    if (p->taps) {
-        taps.assign(p->taps, p->taps + p->n_taps);
-    } else {
-        if (p->taps_per_phase < 1 || p->taps_per_phase * D > kN) {
-            set_error("fft_ddc: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", p->taps_per_phase, D, kN);
-            return GR4PM_ERR_INVALID;
-        }
-        taps.resize(p->taps_per_phase * D);
-        GR4PM_TRY(gr4pm_ddc_taps(D, p->taps_per_phase, 0.25, 0.75, taps.data()));
+    if (!p->taps && (p->taps_per_phase < 1 || p->taps_per_phase * D > kN)) {
+        set_error("fft_ddc: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", p->taps_per_phase, D, kN);
+        return GR4PM_ERR_INVALID;
     }
-    const size_t L = taps.size();
-    for (size_t t = 0; t < L; ++t)
-        if (!std::isfinite(taps[t])) {
+    const size_t L = p->taps ? p->n_taps : p->taps_per_phase * D;
+    for (size_t t = 0; p->taps && t < L; ++t)
+        if (!std::isfinite(p->taps[t])) {
             set_error("fft_ddc: taps[%zu] is not finite", t);
             return GR4PM_ERR_INVALID;
         }
-    const size_t V = p->overlap < 0 ? fft_ddc_default_overlap(L) : static_cast<size_t>(p->overlap);
-    switch (fft_ddc_validate(K, D, R, L, V)) {
-    case FftDdcRefusal::none: break;
-    case FftDdcRefusal::overlap_multiple:
-        set_error("fft_ddc: the overlap %zu is no multiple of the decimation %zu", V, D);
-        return GR4PM_ERR_INVALID;
-    case FftDdcRefusal::overlap_low:
-        set_error("fft_ddc: the overlap %zu is below the %zu taps' reach of %zu samples", V, L, L - 1);
-        return GR4PM_ERR_INVALID;
-    case FftDdcRefusal::overlap_high:
-        set_error("fft_ddc: the overlap %zu leaves a hop below %u: at most %zu", V, kFftDdcMinHop, kN - kFftDdcMinHop);
-        return GR4PM_ERR_INVALID;
-    default: set_error("fft_ddc: invalid sizes"); return GR4PM_ERR_INVALID;
+    if (p->overlap >= 0) { // the default is a multiple of 256 that reaches; at most it is too high, which the bank says
+        const size_t V = static_cast<size_t>(p->overlap);
+        if (V % D) {
+            set_error("fft_ddc: the overlap %zu is no multiple of the decimation %zu", V, D);
+            return GR4PM_ERR_INVALID;
+        }
+        if (V <= kN - kFftDdcMinHop && V + 1 < L) {
+            set_error("fft_ddc: the overlap %zu is below the %zu taps' reach of %zu samples", V, L, L - 1);
+            return GR4PM_ERR_INVALID;
+        }
     }
-    GR4PM_TRY(require_device());
     std::unique_ptr<gr4pm_fft_ddc> h(new (std::nothrow) gr4pm_fft_ddc);
     if (!h) return GR4PM_ERR_NOMEM;
-    h->K = K, h->D = D, h->R = R, h->V = V;
-    h->words = std::move(words);
-    GR4PM_TRY(h->init(D, V, p->start_index, p->stream));
-    const size_t B = kN / D, RB = R * B;
-    std::vector<float2> G(K * RB);
-    for (size_t k = 0; k < K; ++k) {
-        const uint32_t w = h->words[k], c = fft_ddc_bin(w);
-        for (size_t t = 0; t < RB; ++t) G[k * RB + t] = response(taps, w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
-    }
-    GR4PM_TRY(h->d_G.alloc(G.size()));
-    GR4PM_TRY(h->d_w.alloc(K));
-    GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
-    GR4PM_TRY(h->d_w.upload(h->words.data(), K, h->stream));
-    return finish_create(h, out, "fft_ddc");
+    const std::vector<float> taps = p->taps ? std::vector<float>(p->taps, p->taps + L) : std::vector<float>();
+    GR4PM_TRY(create_bank(*h, "fft_ddc", std::move(words), std::vector<size_t>(K, D), std::vector<size_t>(K, R),
+                          std::vector<std::vector<float>>(K, taps), p->taps_per_phase, p->overlap, p->start_index, p->stream));
+    *out = h.release();
+    return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
 
 void gr4pm_fft_ddc_destroy(gr4pm_fft_ddc* h)
 try {
-    if (!h) return;
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
+    destroy(h);
 }
 GR4PM_ABI_CATCH_VOID
 
 gr4pm_status gr4pm_fft_ddc_reset(gr4pm_fft_ddc* h)
 try {
-    if (!h) return GR4PM_ERR_INVALID;
-    GR4PM_TRY(h->tail.reset(h->stream));
-    h->taken = 0;
-    return GR4PM_OK;
+    return reset(h);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_frames_for(const gr4pm_fft_ddc* h, size_t n_in, size_t* n_frames)
 try {
     if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    *n_frames = 0;
-    if (n_in > (size_t(1) << 40)) {
-        set_error("fft_ddc: %zu samples in one call, at most 2^40", n_in);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    *n_frames = fft_ddc_plan(h->shape, h->taken, n_in).frames;
-    return GR4PM_OK;
+    size_t counts[kFftDdcMaxK];
+    const gr4pm_status st = frames_for(*h, n_in, counts);
+    *n_frames = counts[0]; // every row's
+    return st;
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_frequencies(const gr4pm_fft_ddc* h, double* out)
 try {
-    if (!h || !out) return GR4PM_ERR_INVALID;
-    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
-    return GR4PM_OK;
+    return frequencies(h, out);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_sizes(const gr4pm_fft_ddc* h, size_t* overlap, size_t* hop)
 try {
-    if (!h || !overlap || !hop) return GR4PM_ERR_INVALID;
-    *overlap = h->V;
-    *hop = h->shape.hop;
-    return GR4PM_OK;
+    return sizes(h, overlap, hop);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_process(gr4pm_fft_ddc* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
                                    size_t out_cap_frames, size_t* n_frames)
 try {
-    return process_any(h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    size_t counts[kFftDdcMaxK];
+    const gr4pm_status st = process_any(*h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, counts);
+    *n_frames = counts[0];
+    return st;
 }
 GR4PM_ABI_CATCH
 
@@ -531,89 +660,15 @@ gr4pm_status gr4pm_fft_ddc_process_iq(gr4pm_fft_ddc* h, const void* in, int form
                                       size_t out_stride, size_t out_cap_frames, size_t* n_frames)
 try {
     if (n_frames) *n_frames = 0;
-    if (!iq::valid(format)) {
-        set_error("fft_ddc: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
-        return GR4PM_ERR_INVALID;
-    }
-    return process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
-                       n_frames);
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    size_t counts[kFftDdcMaxK];
+    const gr4pm_status st = process_iq(*h, in, format, scale, n_in, out, out_stride, out_cap_frames, counts);
+    *n_frames = counts[0];
+    return st;
 }
 GR4PM_ABI_CATCH
 
-} // extern "C"
-
-// ---- MixedFftDdc: a decimation per channel from the same shared transform ------------------------
-// The segment grid is the FftDdc's at Dmax (fft_ddc_shape(Dmax, V), fft_ddc_plan() unchanged), the forward kernel is used
-// as it is, and k_fft_ddc_mixed runs fft_ddc_channel_body() with each channel's own B_k, R_k, first_k and frames_k.
-
-namespace {
-
-using gr4pm::hostlogic::fft_ddc_mixed_channel;
-using gr4pm::hostlogic::fft_ddc_mixed_default_overlap;
-using gr4pm::hostlogic::fft_ddc_mixed_frames;
-using gr4pm::hostlogic::fft_ddc_mixed_max_decimation;
-using gr4pm::hostlogic::fft_ddc_mixed_table_offsets;
-using gr4pm::hostlogic::fft_ddc_mixed_validate;
-using gr4pm::hostlogic::fft_ddc_mixed_validate_channels;
-using gr4pm::hostlogic::FftDdcMixedChannel;
-using gr4pm::hostlogic::FftDdcMixedRefusal;
-using gr4pm::hostlogic::FftDdcMixedVerdict;
-
-} // namespace
-
-struct gr4pm_fft_ddc_mixed : FftDdcCore { // the core's shape is that of (Dmax, V)
-    size_t K = 0, Dmax = 0, V = 0;
-    uint32_t max_frames = 0; // hop / min D_k
-    std::vector<uint32_t> words;
-    std::vector<FftDdcMixedChannel> channels;
-    gr4pm::DevBuf<float2> d_G;
-    gr4pm::DevBuf<MixedDesc> d_desc;
-};
-
-// frames per row of a call: counts[k]
-static void mixed_frames(const gr4pm_fft_ddc_mixed* h, const FftDdcPlan& p, size_t* counts)
-{
-    for (size_t k = 0; k < h->K; ++k) counts[k] = fft_ddc_mixed_frames(p, h->channels[k]);
-}
-
-static gr4pm_status mixed_process_any(gr4pm_fft_ddc_mixed* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
-                                      size_t out_stride, size_t out_cap_frames, size_t* n_frames)
-{
-    if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    std::fill(n_frames, n_frames + h->K, size_t(0));
-    if (n_in > (size_t(1) << 40)) {
-        set_error("fft_ddc_mixed: %zu samples in one call, at most 2^40", n_in);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (n_in == 0) return GR4PM_OK;
-    if (!in) {
-        set_error("fft_ddc_mixed: no input array");
-        return GR4PM_ERR_INVALID;
-    }
-    const FftDdcPlan p = fft_ddc_plan(h->shape, h->taken, n_in);
-    const size_t longest = p.n_segments * h->max_frames;
-    if (longest > out_cap_frames) {
-        set_error("fft_ddc_mixed: %zu frames on the longest row, room for %zu", longest, out_cap_frames);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    if (longest && (!out || (h->K > 1 && out_stride < longest))) {
-        set_error("fft_ddc_mixed: no output array, or a row stride of %zu items for %zu frames", out_stride, longest);
-        return GR4PM_ERR_INVALID;
-    }
-    MixedArgs b = {};
-    b.spec = reinterpret_cast<const float2*>(h->d_spec.p), b.G = h->d_G.p, b.tw = h->d_tw.p, b.desc = h->d_desc.p;
-    b.out = reinterpret_cast<float2*>(out), b.out_stride = out_stride;
-    b.call_segments = p.n_segments, b.hop = h->shape.hop, b.max_frames = h->max_frames;
-    GR4PM_TRY(h->run(p, in, format, scale, n_in, [&](size_t done, size_t segs) {
-        b.seg0 = done;
-        b.index0 = fft_ddc_segment_index(h->shape, h->start_index, p.segments_before + done);
-        hipLaunchKernelGGL(k_fft_ddc_mixed, dim3(static_cast<unsigned>(segs), static_cast<unsigned>(h->K)), dim3(64), 0, h->stream, b);
-    }));
-    mixed_frames(h, p, n_frames);
-    return GR4PM_OK;
-}
-
-extern "C" {
+// ---- MixedFftDdc: a decimation per channel ---------------------------------------------------------
 
 gr4pm_status gr4pm_fft_ddc_mixed_create(const gr4pm_fft_ddc_mixed_params* p, gr4pm_fft_ddc_mixed** out)
 try {
@@ -630,146 +685,57 @@ try {
         set_error("fft_ddc_mixed: taps and n_taps come together or not at all");
         return GR4PM_ERR_INVALID;
     }
-    const std::vector<size_t> D(p->decimations, p->decimations + K);
-    const std::vector<size_t> R = p->images ? std::vector<size_t>(p->images, p->images + K) : std::vector<size_t>(K, 2);
-    std::vector<size_t> L(K);
-    for (size_t k = 0; k < K; ++k) {
-        if (!fft_ddc_pow2(D[k]) || D[k] < kFftDdcMinD || D[k] > kFftDdcMaxD) {
-            set_error("fft_ddc_mixed: decimations[%zu] must be a power of two in [%u, %u], not %zu", k, kFftDdcMinD, kFftDdcMaxD, D[k]);
-            return GR4PM_ERR_INVALID;
-        }
-        if (p->taps) {
-            GR4PM_TRY(prototype_length("fft_ddc_mixed", p->taps, p->n_taps[k], kN));
-            L[k] = p->n_taps[k];
-        } else {
-            if (p->taps_per_phase < 1 || p->taps_per_phase * D[k] > kN) {
-                set_error("fft_ddc_mixed: %zu taps per phase at a decimation of %zu: the prototype has 1 .. %zu taps", p->taps_per_phase, D[k], kN);
-                return GR4PM_ERR_INVALID;
-            }
-            L[k] = p->taps_per_phase * D[k];
-        }
-    }
-    const FftDdcMixedVerdict sizes = fft_ddc_mixed_validate_channels(K, D.data(), R.data(), L.data());
-    if (sizes.refusal == FftDdcMixedRefusal::images) {
-        set_error("fft_ddc_mixed: images[%zu] must be a power of two in [1, %zu], not %zu", sizes.channel, D[sizes.channel], R[sizes.channel]);
-        return GR4PM_ERR_INVALID;
-    }
-    if (sizes.refusal != FftDdcMixedRefusal::none) {
-        set_error("fft_ddc_mixed: invalid sizes of channel %zu", sizes.channel);
-        return GR4PM_ERR_INVALID;
-    }
     std::vector<std::vector<float>> taps(K);
-    for (size_t k = 0, at = 0; k < K; at += L[k], ++k) {
-        if (p->taps) {
-            taps[k].assign(p->taps + at, p->taps + at + L[k]);
-        } else {
-            taps[k].resize(L[k]);
-            GR4PM_TRY(gr4pm_ddc_taps(D[k], p->taps_per_phase, 0.25, 0.75, taps[k].data()));
-        }
-        for (size_t t = 0; t < L[k]; ++t)
-            if (!std::isfinite(taps[k][t])) {
-                set_error("fft_ddc_mixed: taps[%zu] of channel %zu is not finite", t, k);
-                return GR4PM_ERR_INVALID;
-            }
+    for (size_t k = 0, at = 0; p->taps && k < K; at += p->n_taps[k], ++k) {
+        GR4PM_TRY(prototype_length("fft_ddc_mixed", p->taps, p->n_taps[k], kN));
+        taps[k].assign(p->taps + at, p->taps + at + p->n_taps[k]);
     }
-    const size_t Dmax = fft_ddc_mixed_max_decimation(K, D.data());
-    const size_t V = p->overlap < 0 ? fft_ddc_mixed_default_overlap(K, D.data(), L.data()) : static_cast<size_t>(p->overlap);
-    const FftDdcMixedVerdict v = fft_ddc_mixed_validate(K, D.data(), R.data(), L.data(), V);
-    switch (v.refusal) {
-    case FftDdcMixedRefusal::none: break;
-    case FftDdcMixedRefusal::overlap_multiple:
-        set_error("fft_ddc_mixed: the overlap %zu is no multiple of the largest decimation %zu", V, Dmax);
-        return GR4PM_ERR_INVALID;
-    case FftDdcMixedRefusal::overlap_low:
-        set_error("fft_ddc_mixed: the overlap %zu is below the reach of channel %zu: %zu taps at a decimation of %zu beside %zu need %zu", V,
-                  v.channel, L[v.channel], D[v.channel], Dmax, Dmax - D[v.channel] + L[v.channel] - 1);
-        return GR4PM_ERR_INVALID;
-    case FftDdcMixedRefusal::overlap_high:
-        set_error("fft_ddc_mixed: the overlap %zu leaves a hop below %u: at most %zu", V, kFftDdcMinHop, kN - kFftDdcMinHop);
-        return GR4PM_ERR_INVALID;
-    default: set_error("fft_ddc_mixed: invalid sizes"); return GR4PM_ERR_INVALID;
-    }
-    GR4PM_TRY(require_device());
     std::unique_ptr<gr4pm_fft_ddc_mixed> h(new (std::nothrow) gr4pm_fft_ddc_mixed);
     if (!h) return GR4PM_ERR_NOMEM;
-    h->K = K, h->Dmax = Dmax, h->V = V;
-    h->words = std::move(words);
-    GR4PM_TRY(h->init(Dmax, V, p->start_index, p->stream));
-    std::vector<size_t> offsets(K);
-    std::vector<float2> G(fft_ddc_mixed_table_offsets(K, D.data(), R.data(), offsets.data()));
-    std::vector<MixedDesc> desc(K);
-    h->channels.resize(K);
-    for (size_t k = 0; k < K; ++k) {
-        const uint32_t w = h->words[k], c = fft_ddc_bin(w);
-        const size_t RB = R[k] * (kN / D[k]);
-        for (size_t t = 0; t < RB; ++t)
-            G[offsets[k] + t] = response(taps[k], w, c, static_cast<int32_t>(t) - static_cast<int32_t>(RB / 2));
-        h->channels[k] = fft_ddc_mixed_channel(static_cast<uint32_t>(Dmax), static_cast<uint32_t>(V), static_cast<uint32_t>(D[k]));
-        h->max_frames = std::max(h->max_frames, h->channels[k].frames);
-        desc[k] = MixedDesc{w, static_cast<uint32_t>(__builtin_ctzll(kN / D[k])), static_cast<uint32_t>(R[k]), h->channels[k].first,
-                            static_cast<uint32_t>(D[k]), h->channels[k].frames, static_cast<uint32_t>(offsets[k]), static_cast<uint32_t>(k)};
-    }
-    // the longest inverse transforms first: a workgroup at B = 512 costs many times one at B = 32
-    std::stable_sort(desc.begin(), desc.end(), [](const MixedDesc& x, const MixedDesc& y) { return x.logB > y.logB; });
-    GR4PM_TRY(h->d_G.alloc(G.size()));
-    GR4PM_TRY(h->d_desc.alloc(K));
-    GR4PM_TRY(h->d_G.upload(G.data(), G.size(), h->stream));
-    GR4PM_TRY(h->d_desc.upload(desc.data(), K, h->stream));
-    return finish_create(h, out, "fft_ddc_mixed");
+    GR4PM_TRY(create_bank(*h, "fft_ddc_mixed", std::move(words), std::vector<size_t>(p->decimations, p->decimations + K),
+                          p->images ? std::vector<size_t>(p->images, p->images + K) : std::vector<size_t>(K, 2), std::move(taps),
+                          p->taps_per_phase, p->overlap, p->start_index, p->stream));
+    *out = h.release();
+    return GR4PM_OK;
 }
 GR4PM_ABI_CATCH
 
 void gr4pm_fft_ddc_mixed_destroy(gr4pm_fft_ddc_mixed* h)
 try {
-    if (!h) return;
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
+    destroy(h);
 }
 GR4PM_ABI_CATCH_VOID
 
 gr4pm_status gr4pm_fft_ddc_mixed_reset(gr4pm_fft_ddc_mixed* h)
 try {
-    if (!h) return GR4PM_ERR_INVALID;
-    GR4PM_TRY(h->tail.reset(h->stream));
-    h->taken = 0;
-    return GR4PM_OK;
+    return reset(h);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_mixed_frames_for(const gr4pm_fft_ddc_mixed* h, size_t n_in, size_t* n_frames)
 try {
     if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    std::fill(n_frames, n_frames + h->K, size_t(0));
-    if (n_in > (size_t(1) << 40)) {
-        set_error("fft_ddc_mixed: %zu samples in one call, at most 2^40", n_in);
-        return GR4PM_ERR_OVERFLOW;
-    }
-    mixed_frames(h, fft_ddc_plan(h->shape, h->taken, n_in), n_frames);
-    return GR4PM_OK;
+    return frames_for(*h, n_in, n_frames);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_mixed_frequencies(const gr4pm_fft_ddc_mixed* h, double* out)
 try {
-    if (!h || !out) return GR4PM_ERR_INVALID;
-    for (size_t k = 0; k < h->K; ++k) out[k] = folded_frequency(h->words[k]);
-    return GR4PM_OK;
+    return frequencies(h, out);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_mixed_sizes(const gr4pm_fft_ddc_mixed* h, size_t* overlap, size_t* hop)
 try {
-    if (!h || !overlap || !hop) return GR4PM_ERR_INVALID;
-    *overlap = h->V;
-    *hop = h->shape.hop;
-    return GR4PM_OK;
+    return sizes(h, overlap, hop);
 }
 GR4PM_ABI_CATCH
 
 gr4pm_status gr4pm_fft_ddc_mixed_process(gr4pm_fft_ddc_mixed* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_stride,
                                          size_t out_cap_frames, size_t* n_frames)
 try {
-    return mixed_process_any(h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
+    if (!h || !n_frames) return GR4PM_ERR_INVALID;
+    return process_any(*h, in, iq::kC64, 0.0f, n_in, out, out_stride, out_cap_frames, n_frames);
 }
 GR4PM_ABI_CATCH
 
@@ -777,13 +743,7 @@ gr4pm_status gr4pm_fft_ddc_mixed_process_iq(gr4pm_fft_ddc_mixed* h, const void* 
                                             gr4pm_c64* out, size_t out_stride, size_t out_cap_frames, size_t* n_frames)
 try {
     if (!h || !n_frames) return GR4PM_ERR_INVALID;
-    std::fill(n_frames, n_frames + h->K, size_t(0));
-    if (!iq::valid(format)) {
-        set_error("fft_ddc_mixed: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
-        return GR4PM_ERR_INVALID;
-    }
-    return mixed_process_any(h, in, format, scale == 0.0f ? iq::default_scale(format) : scale, n_in, out, out_stride, out_cap_frames,
-                             n_frames);
+    return process_iq(*h, in, format, scale, n_in, out, out_stride, out_cap_frames, n_frames);
 }
 GR4PM_ABI_CATCH
 

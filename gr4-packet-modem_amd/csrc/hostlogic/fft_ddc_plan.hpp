@@ -1,6 +1,6 @@
 // hostlogic/fft_ddc_plan.hpp -- the integer side of the FftDdc block (fft_ddc.hip), HIP-free: the
-// nearest bin of a frequency word, the rotator's phase, the validation of a handle's sizes and the segment and tail
-// arithmetic of a call.
+// nearest bin of a frequency word, the rotator's phase and the segment and tail arithmetic of a call.  The validation of a
+// handle's sizes and the default overlap are fft_ddc_mixed_plan.hpp's, at K equal decimations.
 //
 // N = 2048, D a power of two in 4 .. 64, B = N / D, an overlap V with D | V and L - 1 <= V <= N - 64, hop = N - V.  The
 // stream is x[0], x[1], ... over all calls since create or reset, x[i] = 0 for i < 0.  Segment s is the N items from
@@ -44,24 +44,6 @@ constexpr uint32_t fft_ddc_table_word(uint32_t w, uint32_t c, int32_t u)
 }
 
 constexpr bool fft_ddc_pow2(uint64_t v) { return v != 0 && (v & (v - 1)) == 0; }
-
-// the smallest multiple of 256 that is >= L - 1 (L >= 1)
-constexpr size_t fft_ddc_default_overlap(size_t L) { return (L - 1 + 255) / 256 * 256; }
-
-enum class FftDdcRefusal { none, channels, decimation, images, taps, overlap_multiple, overlap_low, overlap_high };
-
-// K channels, decimation D, R images, L taps, overlap V
-constexpr FftDdcRefusal fft_ddc_validate(uint64_t K, uint64_t D, uint64_t R, uint64_t L, uint64_t V)
-{
-    if (K < 1 || K > kFftDdcMaxK) return FftDdcRefusal::channels;
-    if (!fft_ddc_pow2(D) || D < kFftDdcMinD || D > kFftDdcMaxD) return FftDdcRefusal::decimation;
-    if (!fft_ddc_pow2(R) || R > D) return FftDdcRefusal::images;
-    if (L < 1) return FftDdcRefusal::taps;
-    if (V % D) return FftDdcRefusal::overlap_multiple;
-    if (V > kFftDdcN - kFftDdcMinHop) return FftDdcRefusal::overlap_high;
-    if (V + 1 < L) return FftDdcRefusal::overlap_low;
-    return FftDdcRefusal::none;
-}
 
 // what a handle's D and V fix
 struct FftDdcShape {

@@ -1,5 +1,6 @@
 // hostlogic/fft_duc_plan.hpp -- the integer side of the FftDuc block (fft_duc.hip), HIP-free: the
-// validation of a handle's sizes, the segment grid and the arithmetic of a call.  The nearest bin of a frequency word and
+// segment grid and the arithmetic of a call; the validation of a handle's sizes and the default overlap are
+// fft_duc_mixed_plan.hpp's, at K equal interpolations.  The nearest bin of a frequency word and
 // the response table's word are the FftDdc's (fft_ddc_plan.hpp), used as they are.
 //
 // N = 2048, I a power of two in 4 .. 64, B = N / I, an overlap V with I | V and L - 1 <= V <= N - 64, hop = N - V,
@@ -20,24 +21,6 @@ namespace hostlogic {
 
 constexpr uint32_t kFftDucN = kFftDdcN;
 constexpr uint32_t kFftDucMaxK = 64, kFftDucMinI = 4, kFftDucMaxI = 64, kFftDucMinHop = 64;
-
-// the smallest multiple of 256 that is >= L - 1 (L >= 1): a multiple of every I the block takes
-constexpr size_t fft_duc_default_overlap(size_t L) { return fft_ddc_default_overlap(L); }
-
-enum class FftDucRefusal { none, channels, interpolation, images, taps, overlap_multiple, overlap_low, overlap_high };
-
-// K channels, interpolation I, R images, L taps, overlap V
-constexpr FftDucRefusal fft_duc_validate(uint64_t K, uint64_t I, uint64_t R, uint64_t L, uint64_t V)
-{
-    if (K < 1 || K > kFftDucMaxK) return FftDucRefusal::channels;
-    if (!fft_ddc_pow2(I) || I < kFftDucMinI || I > kFftDucMaxI) return FftDucRefusal::interpolation;
-    if (!fft_ddc_pow2(R) || R > I) return FftDucRefusal::images;
-    if (L < 1) return FftDucRefusal::taps;
-    if (V % I) return FftDucRefusal::overlap_multiple;
-    if (V > kFftDucN - kFftDucMinHop) return FftDucRefusal::overlap_high;
-    if (V + 1 < L) return FftDucRefusal::overlap_low;
-    return FftDucRefusal::none;
-}
 
 // what a handle's I and V fix
 struct FftDucShape {

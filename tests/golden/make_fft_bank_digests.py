@@ -1,0 +1,32 @@
+#!/usr/bin/env python3
+"""Regenerates tests/golden/fft_bank_digests.json: the SHA-256 of the raw output bytes of the FftDdc, MixedFftDdc, FftDuc
+and MixedFftDuc blocks on the inputs that tests/test_fft_bank_digests.py names.
+
+Needs the built library and an MI355X.  The cases, their inputs and the order of the bytes are the test's own
+(OUTPUTS and digest() there), run through the public classes; only the digests are written.  The file was first written
+from the commit before the uniform handles became fronts of the mixed ones, and a run on a later tree must rewrite it
+byte for byte.
+"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+sys.path.insert(0, os.path.dirname(HERE))
+
+import test_fft_bank_digests as cases  # noqa: E402
+
+
+def main():
+    digests = {}
+    for key in sorted(cases.OUTPUTS):
+        digests[key] = cases.digest(key)
+        print(key, digests[key], flush=True)
+    with open(cases.GOLDEN, "w") as f:
+        json.dump({"device": "MI355X", "digests": digests}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    sys.exit(main())

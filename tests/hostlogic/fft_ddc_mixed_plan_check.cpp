@@ -110,18 +110,6 @@ static void check_validation()
         for (size_t Db : {4, 64})
             for (size_t La : {1, 2})
                 check_one_validation({Da, Db}, {1, 1}, {La, 1}, 0);
-    // all equal: the FftDdc's validation, refusal for refusal
-    for (uint64_t D : {2ull, 4ull, 16ull, 64ull, 128ull})
-        for (uint64_t R : {0ull, 1ull, 2ull, 3ull, 64ull})
-            for (uint64_t L : {0ull, 1ull, 192ull, 257ull, 1986ull})
-                for (uint64_t V : {0ull, 64ull, 100ull, 191ull, 192ull, 256ull, 1984ull, 1985ull, 2048ull}) {
-                    ++cases;
-                    const std::vector<size_t> Ds(3, D), Rs(3, R), Ls(3, L);
-                    const FftDdcRefusal one = fft_ddc_validate(3, D, R, L, V);
-                    const FftDdcMixedRefusal all = fft_ddc_mixed_validate(3, Ds.data(), Rs.data(), Ls.data(), V).refusal;
-                    CHECK((one == FftDdcRefusal::none) == (all == FftDdcMixedRefusal::none), "equal D %llu R %llu L %llu V %llu",
-                          (unsigned long long)D, (unsigned long long)R, (unsigned long long)L, (unsigned long long)V);
-                }
     // the default overlap: the smallest multiple of 256 that the overlap_low condition accepts for every channel
     for (int r = 0; r < 2000; ++r) {
         ++cases;

@@ -1,8 +1,9 @@
 // Sweeps csrc/hostlogic/fft_ddc_plan.hpp (the FftDdc's host side) against restatements in __int128:
-// the nearest bin, the rotator's phase and the table's word, the validation, and for every D in 4 .. 64 with a set of
-// overlaps the segments, tails and frames of sequences of calls.  Stand-alone, built with -fsanitize=undefined,address by
+// the nearest bin, the rotator's phase and the table's word, the validation (fft_ddc_mixed_plan.hpp's, asked with K equal
+// entries, which is what an FftDdc's create asks), and for every D in 4 .. 64 with a set of overlaps the segments, tails
+// and frames of sequences of calls.  Stand-alone, built with -fsanitize=undefined,address by
 // tests/test_fft_ddc_plan_check.py.
-#include "hostlogic/fft_ddc_plan.hpp"
+#include "hostlogic/fft_ddc_mixed_plan.hpp"
 
 #include <cstdio>
 #include <vector>
@@ -78,13 +79,16 @@ static void check_validation()
                         const bool okR = (R == 1 || R == 2 || R == 16 || R == 64) && R <= D;
                         const bool ok = K >= 1 && K <= 64 && pow2D && okR && L >= 1 && V % (D ? D : 1) == 0 &&
                                         static_cast<i128>(V) >= static_cast<i128>(L) - 1 && V <= 2048 - 64;
-                        CHECK((fft_ddc_validate(K, D, R, L, V) == FftDdcRefusal::none) == ok, "K %llu D %llu R %llu L %llu V %llu",
+                        const std::vector<size_t> Ds(K, D), Rs(K, R), Ls(K, L); // K equal channels
+                        CHECK((fft_ddc_mixed_validate(K, Ds.data(), Rs.data(), Ls.data(), V).refusal == FftDdcMixedRefusal::none) == ok,
+                              "K %llu D %llu R %llu L %llu V %llu",
                               (unsigned long long)K, (unsigned long long)D, (unsigned long long)R, (unsigned long long)L,
                               (unsigned long long)V);
                     }
     for (size_t L : {1, 2, 48, 192, 256, 257, 258, 768, 1985}) {
         ++cases;
-        const size_t V = fft_ddc_default_overlap(L);
+        const size_t Ds[3] = {16, 16, 16}, Ls[3] = {L, L, L};
+        const size_t V = fft_ddc_mixed_default_overlap(3, Ds, Ls);
         CHECK(V % 256 == 0 && V + 1 >= L && (V == 0 || V - 256 + 1 < L), "L %zu V %zu", L, V);
     }
 }

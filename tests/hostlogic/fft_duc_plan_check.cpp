@@ -1,8 +1,9 @@
 // Sweeps csrc/hostlogic/fft_duc_plan.hpp (the FftDuc's host side) against restatements in __int128
-// from a_s = s hop - V alone: every refusal of the validation, the shape, and for every I in 4 .. 64 with a set of
+// from a_s = s hop - V alone: every refusal of the validation (fft_duc_mixed_plan.hpp's, asked with K equal entries, which
+// is what an FftDuc's create asks), the shape, and for every I in 4 .. 64 with a set of
 // overlaps the segments, carried items, samples and segment positions of sequences of calls.  Stand-alone, built with
 // -fsanitize=undefined,address by tests/test_fft_duc_plan_check.py.
-#include "hostlogic/fft_duc_plan.hpp"
+#include "hostlogic/fft_duc_mixed_plan.hpp"
 
 #include <cstdio>
 #include <vector>
@@ -43,21 +44,21 @@ static uint64_t rng()
     return rng_state;
 }
 
-static FftDucRefusal refusal_128(i128 K, i128 I, i128 R, i128 L, i128 V)
+static FftDucMixedRefusal refusal_128(i128 K, i128 I, i128 R, i128 L, i128 V)
 {
     auto pow2 = [](i128 v) {
         for (i128 p = 1; p <= 4096; p *= 2)
             if (v == p) return true;
         return false;
     };
-    if (K < 1 || K > 64) return FftDucRefusal::channels;
-    if (!pow2(I) || I < 4 || I > 64) return FftDucRefusal::interpolation;
-    if (!pow2(R) || R > I) return FftDucRefusal::images;
-    if (L < 1) return FftDucRefusal::taps;
-    if (mod(V, I) != 0) return FftDucRefusal::overlap_multiple;
-    if (N - V < 64) return FftDucRefusal::overlap_high;
-    if (V < L - 1) return FftDucRefusal::overlap_low;
-    return FftDucRefusal::none;
+    if (K < 1 || K > 64) return FftDucMixedRefusal::channels;
+    if (!pow2(I) || I < 4 || I > 64) return FftDucMixedRefusal::interpolation;
+    if (!pow2(R) || R > I) return FftDucMixedRefusal::images;
+    if (L < 1) return FftDucMixedRefusal::taps;
+    if (mod(V, I) != 0) return FftDucMixedRefusal::overlap_multiple;
+    if (N - V < 64) return FftDucMixedRefusal::overlap_high;
+    if (V < L - 1) return FftDucMixedRefusal::overlap_low;
+    return FftDucMixedRefusal::none;
 }
 
 static void check_validation()
@@ -69,7 +70,8 @@ static void check_validation()
                 for (uint64_t L : {0ull, 1ull, 2ull, 192ull, 257ull, 1985ull, 1986ull})
                     for (uint64_t V : {0ull, 4ull, 64ull, 100ull, 191ull, 192ull, 256ull, 1984ull, 1985ull, 2048ull, 4096ull}) {
                         ++cases;
-                        const FftDucRefusal got = fft_duc_validate(K, I, R, L, V);
+                        const std::vector<size_t> Is(K, I), Rs(K, R), Ls(K, L); // K equal rows
+                        const FftDucMixedRefusal got = fft_duc_mixed_validate(K, Is.data(), Rs.data(), Ls.data(), V).refusal;
                         seen[static_cast<int>(got)] = true;
                         CHECK(got == refusal_128(K, I, R, L, V), "K %llu I %llu R %llu L %llu V %llu", (unsigned long long)K,
                               (unsigned long long)I, (unsigned long long)R, (unsigned long long)L, (unsigned long long)V);
@@ -77,7 +79,8 @@ static void check_validation()
     for (int r = 0; r < 8; ++r) CHECK(seen[r], "refusal %d was never given", r);
     for (size_t L : {1, 2, 48, 192, 256, 257, 258, 768, 1985}) {
         ++cases;
-        const size_t V = fft_duc_default_overlap(L);
+        const size_t Ls[3] = {L, L, L};
+        const size_t V = fft_duc_mixed_default_overlap(3, Ls);
         CHECK(V % 256 == 0 && V + 1 >= L && (V == 0 || V - 256 + 1 < L), "L %zu V %zu", L, V);
     }
 }
