@@ -3099,6 +3099,20 @@ def row_resampler_taps(phases=32, taps_per_phase=12, max_step=1.0, passband=0.25
     return out[:n]
 
 
+def _check_rows_input(x, n_rows=None):
+    """x is a [rows, n] complex64 CUDA tensor with contiguous rows (any row stride >= n), of n_rows rows where given"""
+    torch = _torch()
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
+            (n_rows is None or x.shape[0] == n_rows) and (x.shape[1] <= 1 or x.stride(1) == 1) and
+            (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
+        raise TypeError(f"x must be a [{'rows' if n_rows is None else n_rows}, n] complex64 CUDA tensor with contiguous rows")
+
+
+def _row_freq_word(offset):
+    """round(offset 2^32) in Python integers: the frequency word of an offset in cycles per item"""
+    return int(round(fractions.Fraction(float(offset)) * (1 << 32)))
+
+
 class RowResampler:
     """gr4pm_row_resampler: rows of channel items (Ddc.extract's [rows, n]) to any real rate with the residual carrier
     removed, every row with a step and a frequency word of its own: what acts on LineSpectrum's per-row symbol rate and
@@ -3196,9 +3210,7 @@ class RowResampler:
         the layout NativeMultiChannelReceiver.submit takes; out_lengths is numpy int64.  out: an optional CUDA complex64
         [R, >= n_cols] tensor with contiguous rows.  Any number of rows: 64 go into one call.  Does not wait."""
         torch = _torch()
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
-                (x.shape[1] <= 1 or x.stride(1) == 1) and (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
-            raise TypeError("x must be a [rows, n] complex64 CUDA tensor with contiguous rows")
+        _check_rows_input(x)
         n_rows, n_in = x.shape
         lengths = self._row_lengths(n_rows, n_in, lengths)
         rec = self._records(n_rows, steps, phase0, freqs)
@@ -3237,9 +3249,7 @@ class RowResampler:
         rates in symbols per item and offsets in cycles per item, as LineSpectrum.symbol_rate and .carrier_offset give
         them.  Returns (rows, out_lengths) with samples_per_symbol items per symbol and the offsets removed."""
         steps = self.steps_for(rates, samples_per_symbol)
-        freqs = None
-        if offsets is not None:
-            freqs = [int(round(fractions.Fraction(float(d)) * (1 << 32))) for d in offsets]
+        freqs = None if offsets is None else [_row_freq_word(d) for d in offsets]
         return self.process_rows(x, lengths, steps, None, freqs, n_cols)
 
     def __del__(self):
@@ -3288,12 +3298,10 @@ class StreamRowResampler:
         """a handle whose row r has rates[r] symbols per item and offsets[r] (None: 0) cycles per item of residual
         carrier: step_r = round(2^32 / (samples_per_symbol rates[r])), freq_r = round(offsets[r] 2^32)"""
         steps = RowResampler.steps_for(rates, samples_per_symbol)
-        freqs = None if offsets is None else [cls._freq_word(d) for d in offsets]
+        freqs = None if offsets is None else [_row_freq_word(d) for d in offsets]
         return cls(steps, freqs, **kw)
 
-    @staticmethod
-    def _freq_word(offset):
-        return int(round(fractions.Fraction(float(offset)) * (1 << 32)))
+    _freq_word = staticmethod(_row_freq_word)
 
     def _lengths(self, lengths, n_cols=None):
         if lengths is None and n_cols is not None:
@@ -3324,10 +3332,7 @@ class StreamRowResampler:
         [R, columns] tensor with contiguous rows; one that is too short for a row's count is refused, nothing is cut).
         out_lengths is numpy int64.  Does not wait."""
         torch = _torch()
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.complex64 and x.dim() == 2 and
-                x.shape[0] == self.n_rows and (x.shape[1] <= 1 or x.stride(1) == 1) and
-                (x.shape[0] <= 1 or x.stride(0) >= x.shape[1])):
-            raise TypeError(f"x must be a [{self.n_rows}, n] complex64 CUDA tensor with contiguous rows")
+        _check_rows_input(x, self.n_rows)
         n_in = x.shape[1]
         lengths = self._lengths(lengths, n_in)
         if out is None:
@@ -3385,7 +3390,7 @@ class StreamRowResampler:
 
     def set_rate(self, r, rate, offset=None, samples_per_symbol=4):
         """set_row from a symbol rate in symbols per item and (None: unchanged) an offset in cycles per item"""
-        self.set_row(r, RowResampler.steps_for([rate], samples_per_symbol)[0], None if offset is None else self._freq_word(offset))
+        self.set_row(r, RowResampler.steps_for([rate], samples_per_symbol)[0], None if offset is None else _row_freq_word(offset))
 
     def state(self, r):
         """(items_in, items_out) of row r: the absolute index of its next input item and the index of its next output item"""

@@ -36,6 +36,8 @@ constexpr uint32_t row_log2(uint32_t Q)
     return l;
 }
 constexpr bool row_step_valid(uint64_t step) { return step >= kRowMinStep && step <= kRowMaxStep; }
+// a row of n items, or a call that brings a carried row n more: n + P - 1 < 2^32
+constexpr bool row_stream_items_valid(uint64_t n, uint64_t P) { return n <= UINT64_MAX - (P - 1) && n + (P - 1) < (uint64_t(1) << 32); }
 
 // the branch q and the numerator of alpha for the fraction mu with b = 32 - log2 Q
 constexpr uint32_t row_branch(uint32_t mu, uint32_t b) { return mu >> b; }
@@ -90,7 +92,7 @@ constexpr uint64_t row_tile_span(uint64_t pos0, uint32_t nv, uint64_t step, uint
 // whether input index k of a row of n items exists: every other one is the operand +0 and is not loaded
 constexpr bool row_item_loaded(int64_t k, uint64_t n) { return k >= 0 && static_cast<uint64_t>(k) < n; }
 
-enum class RowRefusal {
+enum class RowRefusal { // of a one-shot call (row_plan) and of a stream's (row_stream_plan.hpp)
     none,     // launch
     nothing,  // no row or no column: OK, nothing to launch (out_lengths are written when there are rows)
     rows,     // more than kRowMaxRows
@@ -102,6 +104,7 @@ enum class RowRefusal {
     columns,  // n_cols_out > 2^31
     stride,   // R > 1 with a stride below the column count, on either side
     lengths,  // no out_lengths array
+    room,     // a stream's row `at` makes more than n_cols_out items in this call: a stream loses none, so nothing is cut
     output,   // no output array
     input,    // no input array although a row has items
 };
@@ -133,7 +136,7 @@ inline RowPlan row_plan(uint64_t P, bool have_x, size_t stride, size_t n_cols, c
         const uint64_t n = lengths ? lengths[r] : n_cols;
         if (n > n_cols) return refuse(RowRefusal::length, r);
         if (!row_step_valid(rows[r].step)) return refuse(RowRefusal::step, r);
-        if (n > UINT64_MAX - (P - 1) || n + (P - 1) >= (uint64_t(1) << 32)) return refuse(RowRefusal::items, r);
+        if (!row_stream_items_valid(n, P)) return refuse(RowRefusal::items, r);
         if (rows[r].phase0 >= (uint64_t(1) << 63)) return refuse(RowRefusal::phase, r);
         const uint64_t M = row_output_items(n, P, rows[r].step, rows[r].phase0);
         p.n[r] = static_cast<uint32_t>(n);

@@ -109,17 +109,9 @@ constexpr void row_stream_retune(RowStreamRow& s, uint64_t step, int32_t freq)
     s.phi = at - static_cast<uint32_t>(freq) * static_cast<uint32_t>((s.d >> 32) + 1);
 }
 
-enum class RowStreamRefusal {
-    none,
-    length,  // lengths[at] > n_cols
-    items,   // lengths[at] + P - 1 >= 2^32
-    columns, // n_cols_out > 2^31
-    stride,  // R > 1 with a stride below the column count, on either side
-    lengths, // no out_lengths array
-    room,    // row `at` makes more than n_cols_out items in this call: a stream loses none, so the call is not cut
-    output,  // no output array although there are columns
-    input,   // no input array although a row has items
-};
+// of RowRefusal a stream's call has none, length, items, columns, stride, lengths, room, output (no output array although
+// there are columns) and input
+using RowStreamRefusal = RowRefusal;
 
 struct RowStreamPlan {
     RowStreamRefusal why;
@@ -129,9 +121,6 @@ struct RowStreamPlan {
     uint32_t n[kRowMaxRows]; // the rows' input items of this call (0 in a flush)
     uint32_t M[kRowMaxRows]; // the rows' output items of this call
 };
-
-// a row's count for n further items, or the refusal of n
-constexpr bool row_stream_items_valid(uint64_t n, uint64_t P) { return n <= UINT64_MAX - (P - 1) && n + (P - 1) < (uint64_t(1) << 32); }
 
 // validates process (flush = false) or flush (flush = true: x, stride, n_cols and lengths are not looked at) and gives
 // the counts and the grid; changes nothing
@@ -171,12 +160,13 @@ inline RowStreamPlan row_stream_plan(const RowStreamRow* rows, size_t n_rows, ui
 }
 
 // the stage of a tile: item j is the row's item A - (P - 1) + i0 + j for the tile's first i0 = (d + m0 step) >> 32.
-// k = i0 - (P - 1) + j is its index relative to A: below 0 it is history item (P - 1) + k, in [0, n) it is x[k], and at or
-// behind n it is +0 and not loaded (only a flush reaches those)
+// k = i0 - (P - 1) + j is its index relative to A: below 0 it is history item (P - 1) + k (+0, and not loaded, in a
+// one-shot call: a fresh row's history), in [0, n) it is x[k], and at or behind n it is +0 and not loaded (of a stream
+// only a flush reaches those)
 enum class RowStreamSource { history, input, zero };
 constexpr RowStreamSource row_stream_source(int64_t k, uint64_t n)
 {
-    return k < 0 ? RowStreamSource::history : static_cast<uint64_t>(k) < n ? RowStreamSource::input : RowStreamSource::zero;
+    return row_item_loaded(k, n) ? RowStreamSource::input : k < 0 ? RowStreamSource::history : RowStreamSource::zero;
 }
 
 // the keep kernel: new history item j of a row that took n > 0 items is the item at k = n - (P - 1) + j relative to A

@@ -1,7 +1,8 @@
 // Sweeps csrc/hostlogic/row_stream_plan.hpp (the StreamRowResampler's host side) against the
 // unbounded definition restated in __int128: the first item behind start_index, the count of a call and of a flush, the
 // advance and the rebase over any cutting of a row into calls, the positions and theta of the items, set_row, and every
-// refusal of row_stream_plan().  Stand-alone, built with -fsanitize=undefined,address by
+// refusal of row_stream_plan(); and that a one-shot call is a stream call on a fresh row (check_fresh_row), which is
+// what lets k_row_resample and k_row_stream be one body.  Stand-alone, built with -fsanitize=undefined,address by
 // tests/test_row_stream_plan_check.py.
 //
 // theta in 128 bits: floor(freq v / 2^32) mod 2^32 depends on v mod 2^64 only (v + k 2^64 adds freq k 2^32), so the
@@ -311,11 +312,55 @@ static void check_refusals()
     CHECK(why(true, false, 0, 0, nullptr, 2, false, 22, 22, true).why == RowStreamRefusal::output, "a flush without output");
 }
 
+// the one-shot call is a stream call on a fresh row (start = 0): the state the one-shot host code hands the shared kernel
+// body, the rotator's operand in either form, and the count of a row of n > 0 items; a row of no items makes nothing
+// whatever the stream's count over P - 1 items is, which is why the one-shot host code keeps row_output_items()
+static void check_fresh_row()
+{
+    const uint64_t S = uint64_t(1) << 32;
+    uint64_t lcg = 2024;
+    auto rnd = [&] {
+        lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+        return lcg >> 11;
+    };
+    std::vector<int32_t> words = {0, 1, -1, INT32_MAX, INT32_MIN, INT32_MIN + 1, 12884902, -12884902};
+    for (int i = 0; i < 8; ++i) words.push_back(static_cast<int32_t>(static_cast<uint32_t>(rnd())));
+    for (uint64_t P : {uint64_t(1), uint64_t(2), uint64_t(12), uint64_t(2048)})
+        for (uint64_t step : {kRowMinStep, kRowMinStep + 1, S - 1, S, S + 1, static_cast<uint64_t>(2.27 * 4294967296.0), kRowMaxStep - 1, kRowMaxStep})
+            for (uint64_t phase0 : {uint64_t(0), uint64_t(1), S / 2 + 3, S - 1, (P + 5) * S + S / 4, (uint64_t(1) << 63) - 1})
+                for (uint64_t n : {uint64_t(0), uint64_t(1), P - 1, P, S - P})
+                    for (int32_t freq : words) {
+                        ++cases;
+                        const RowStreamRow s = make_row(step, phase0, 0, freq);
+                        CHECK(s.d == phase0 && s.ref_frac == 0 && s.items_out == 0 && s.items_in == 0 && s.hist == 0, "the fresh row");
+                        CHECK(s.phi == 0u - static_cast<uint32_t>(freq), "the fresh row's Phi");
+                        CHECK(row_stream_items_valid(n, P), "the row's length");
+                        const uint64_t span = n + P - 1, M = row_output_items(n, P, step, phase0);
+                        if (n == 0) {
+                            CHECK(M == 0, "a row of no items makes %llu", static_cast<unsigned long long>(M));
+                            continue;
+                        }
+                        CHECK(M == row_stream_count(s, span), "the one-shot's count %llu, the stream's %llu",
+                              static_cast<unsigned long long>(M), static_cast<unsigned long long>(row_stream_count(s, span)));
+                        // positions below (n + P - 1) 2^32: the first, the last and random ones, whether an item sits there or not
+                        const uint64_t end = span << 32;
+                        uint64_t at[8] = {0, end - 1, phase0 < end ? phase0 : 0, M ? phase0 + (M - 1) * step : 0};
+                        for (int i = 4; i < 8; ++i) at[i] = (rnd() << 11 | (rnd() & 0x7ffu)) % end;
+                        for (uint64_t pos : at) {
+                            CHECK(pos < end && static_cast<i128>(row_stream_theta_pos(pos, s.ref_frac)) == static_cast<i128>(pos) + kOne,
+                                  "the carried operand wraps");
+                            CHECK(row_stream_theta(s, pos) == row_theta(freq, pos), "theta at %llu: carried %u, one-shot %u",
+                                  static_cast<unsigned long long>(pos), row_stream_theta(s, pos), row_theta(freq, pos));
+                        }
+                    }
+}
+
 int main()
 {
     const uint64_t S = uint64_t(1) << 32;
     check_div();
     check_refusals();
+    check_fresh_row();
     for (uint32_t Q : {2u, 32u, 256u})
         for (uint64_t P : {uint64_t(1), uint64_t(12), uint64_t(128)}) {
             if (!row_sizes_valid(Q, P)) { // 256 phases of 128 taps: no such handle

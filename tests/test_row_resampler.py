@@ -52,20 +52,39 @@ def assert_padding(rows, lens):
 WORST = {}
 
 
+N_COLS = 6144
+
+
+def bound_rows(P):
+    """the 21 rows of the comparison: every length of row_lengths(P) at every phase0 of PHASES"""
+    lengths = row_lengths(P) * len(PHASES)
+    return lengths, [PHASES[r // 7] for r in range(len(lengths))], rows_of(len(lengths))
+
+
+def bound_call(rs, xd, lengths, phase0, k):
+    """call k of the comparison, at STEPS[k] with the frequency words rotated by k: the [21, N_COLS] array on the host,
+    the lengths the call reported and the words"""
+    freqs = [WORDS[(r + k) % len(WORDS)] for r in range(len(lengths))]
+    y, lens = rs.process_rows(xd, lengths, [STEPS[k]] * len(lengths), phase0, freqs, n_cols=N_COLS)
+    return host(y), lens, freqs
+
+
+def bound_output(Q, P, k):
+    """bound_call's array from a handle of its own"""
+    lengths, phase0, x = bound_rows(P)
+    return bound_call(load_package().RowResampler(phases=Q, taps=taps_of(Q, P)), dev(x), lengths, phase0, k)[0]
+
+
 @pytest.mark.parametrize("Q,P", SIZES)
 def test_within_the_derived_bound_of_float64(pkg, Q, P):
     h = taps_of(Q, P)
     rs = pkg.RowResampler(phases=Q, taps=h)
-    lengths = row_lengths(P) * len(PHASES)
-    x = rows_of(len(lengths))
+    lengths, phase0, x = bound_rows(P)
     xd = dev(x)
     worst = 0.0
     for k, step in enumerate(STEPS):
-        phase0 = [PHASES[r // 7] for r in range(len(lengths))]
-        freqs = [WORDS[(r + k) % len(WORDS)] for r in range(len(lengths))]
-        n_cols = 6144
-        y, lens = rs.process_rows(xd, lengths, [step] * len(lengths), phase0, freqs, n_cols=n_cols)
-        y = host(y)
+        n_cols = N_COLS
+        y, lens, freqs = bound_call(rs, xd, lengths, phase0, k)
         assert y.shape == (len(lengths), n_cols)
         assert lens.tolist() == rs.output_lengths(lengths, [step] * len(lengths), phase0, n_cols=n_cols).tolist()
         assert_padding(y, lens)
@@ -118,18 +137,28 @@ def test_continuation_is_bit_exact_at_the_tile_edges(pkg, step):
         assert np.array_equal(bits(host(part)[0, :M - m0]), bits(full[m0:M])), (step, T, m0)
 
 
-def test_rows_alone_split_calls_and_repeats(pkg):
+def seventy_rows(pkg):
+    """70 rows of 600 items, every one with a length, a step, a phase0 and a word of its own, and the call on all of them
+    (64 + 6 through the ABI)"""
     Q, P = 32, 12
     rs = pkg.RowResampler(phases=Q, taps=taps_of(Q, P))
     R = 70
-    x = rows_of(R, 600, seed=9)
-    xd = dev(x)
+    xd = dev(rows_of(R, 600, seed=9))
     rng = np.random.default_rng(10)
     lengths = [int(v) for v in rng.integers(0, 601, R)]
     steps = [int(v) for v in rng.integers(TWO32 // 2, 3 * TWO32, R)]
     phase0 = [int(v) for v in rng.integers(0, 4 * TWO32, R)]
     freqs = [int(v) for v in rng.integers(-(1 << 31), 1 << 31, R)]
     all_rows, all_lens = rs.process_rows(xd, lengths, steps, phase0, freqs, n_cols=2048)
+    return rs, xd, lengths, steps, phase0, freqs, all_rows, all_lens
+
+
+def seventy_rows_output():
+    return host(seventy_rows(load_package())[6])
+
+
+def test_rows_alone_split_calls_and_repeats(pkg):
+    rs, xd, lengths, steps, phase0, freqs, all_rows, all_lens = seventy_rows(pkg)
     again, again_lens = rs.process_rows(xd, lengths, steps, phase0, freqs, n_cols=2048)
     all_rows, again = host(all_rows), host(again)
     assert np.array_equal(bits(all_rows), bits(again)) and all_lens.tolist() == again_lens.tolist()

@@ -1,5 +1,9 @@
-"""The StreamRowResampler on the GPU (gr4pm_row_stream).  The one-shot RowResampler is the yardstick,
-bit for bit: one handle of six rows (steps 2^26 .. 2^38), cut into calls differently per row -- forty calls of 1 item, then
+"""The StreamRowResampler on the GPU (gr4pm_row_stream) beside the one-shot RowResampler, bit for bit.
+The two are fronts of one kernel body (csrc/row_kernel.hpp: k_row_stream and k_row_resample instantiate it), so these
+comparisons show that carrying a row across calls changes nothing, not that two implementations agree: the float64 bound of
+test_row_resampler.py holds the values, and the recorded digests of test_row_resampler_digests.py hold the bits.
+
+One handle of six rows (steps 2^26 .. 2^38), cut into calls differently per row -- forty calls of 1 item, then
 P - 2, P - 1, P, 0, 255, 257 and the rest, rotated per row so that every call is ragged -- and flushed, gives the bytes of
 RowResampler.process_rows on the whole rows; +0 behind every call's counts in an output pre-filled with NaN; items_for is
 what each call reports; a second pass behind the flush gives the same bytes.  A start_index beyond 2^33 gives the one-
@@ -31,10 +35,14 @@ def pkg():
     return load_package()
 
 
-@pytest.fixture(scope="module")
-def rows():
+def make_rows():
     rng = np.random.default_rng(29)
     return (rng.standard_normal((R, N)) + 1j * rng.standard_normal((R, N))).astype(np.complex64)
+
+
+@pytest.fixture(scope="module")
+def rows():
+    return make_rows()
 
 
 def taps_of(Q, P):
@@ -88,6 +96,17 @@ def one_shot(pkg, Q, h, x, steps, phase0, freqs):
     return [y[r, :lens[r]] for r in range(x.shape[0])]
 
 
+def cutting_case(pkg, Q, P, k):
+    """the handle of the comparison's case k (phases_of(P)[k], the frequency words rotated by k) and its words"""
+    freqs = [WORDS[(r + k) % len(WORDS)] for r in range(R)]
+    return pkg.StreamRowResampler(STEPS, freqs, [phases_of(P)[k]] * R, phases=Q, taps=taps_of(Q, P)), freqs
+
+
+def cutting_output(Q, P, k):
+    """per row, what the 47 ragged calls and the flush of case k deliver"""
+    return feed(cutting_case(load_package(), Q, P, k)[0], make_rows(), cuts_of(P))
+
+
 @pytest.mark.parametrize("Q,P", SIZES)
 def test_any_cutting_gives_the_one_shot_blocks_bytes(pkg, rows, Q, P):
     h = taps_of(Q, P)
@@ -96,10 +115,8 @@ def test_any_cutting_gives_the_one_shot_blocks_bytes(pkg, rows, Q, P):
         "calls in which some rows get nothing while others get items"
     assert sum(len({cuts[r][c] for r in range(R)}) > 1 for c in range(len(cuts[0]))) >= 30, "ragged calls"  # (a special length of 1 beside rows that get 1 is not ragged)
     for k, phase in enumerate(phases_of(P)):
-        phase0 = [phase] * R
-        freqs = [WORDS[(r + k) % len(WORDS)] for r in range(R)]
-        want = one_shot(pkg, Q, h, rows, STEPS, phase0, freqs)
-        b = pkg.StreamRowResampler(STEPS, freqs, phase0, phases=Q, taps=h)
+        b, freqs = cutting_case(pkg, Q, P, k)
+        want = one_shot(pkg, Q, h, rows, STEPS, [phase] * R, freqs)
         got = feed(b, rows, cuts)
         for r in range(R):
             assert want[r].size == ref.output_items(N, P, STEPS[r], phase) > 0
@@ -111,38 +128,62 @@ def test_any_cutting_gives_the_one_shot_blocks_bytes(pkg, rows, Q, P):
                 assert again[r].tobytes() == want[r].tobytes(), (Q, P, r)
 
 
+FAR_START = (1 << 33) + 20480
+FAR_FREQS = [(3 << 20) * (1 if r % 2 else -1) for r in range(R)]
+FAR_PHASE0 = [12345 + 1000003 * r for r in range(R)]
+
+
+def far_output(rows=None):
+    """per row, what a handle that starts at FAR_START delivers over the ragged calls and the flush"""
+    Q, P = 32, 12
+    b = load_package().StreamRowResampler(STEPS, FAR_FREQS, FAR_PHASE0, [FAR_START] * R, phases=Q, taps=taps_of(Q, P))
+    return feed(b, make_rows() if rows is None else rows, cuts_of(P))
+
+
 def test_far_positions_give_the_one_shot_blocks_bytes(pkg, rows):
     Q, P = 32, 12
     h = taps_of(Q, P)
-    start = (1 << 33) + 20480
-    freqs = [(3 << 20) * (1 if r % 2 else -1) for r in range(R)]
+    start, freqs, phase0 = FAR_START, FAR_FREQS, FAR_PHASE0
     assert all((f * start) % TWO32 == 0 for f in freqs)
-    phase0 = [12345 + 1000003 * r for r in range(R)]
     # the first item's position from the row's first item, in Python integers
     first = [sref.Row(h, Q, STEPS[r], phase0[r], freqs[r], start).next_pos - (start << 32) for r in range(R)]
     assert all(0 <= first[r] < STEPS[r] for r in range(R))
     want = one_shot(pkg, Q, h, rows, STEPS, first, freqs)
-    b = pkg.StreamRowResampler(STEPS, freqs, phase0, [start] * R, phases=Q, taps=h)
-    got = feed(b, rows, cuts_of(P))
+    got = far_output(rows)
     for r in range(R):
         assert got[r].tobytes() == want[r].tobytes(), r
+
+
+SET_ROW_FREQS = [WORDS[r % len(WORDS)] for r in range(R)]
+SET_ROW_NEW_STEPS = [min(1 << 38, s + s // 8 + 1) for s in STEPS]
+SET_ROW_NEW_FREQS = [-7654321, 0, 1 << 30, -1, 99, -(1 << 31)]
+
+
+def set_row_calls(rows):
+    """2000 items, a set_row on every row, the other 3000 and the flush: the three calls' arrays and counts"""
+    Q, P = 32, 12
+    b = load_package().StreamRowResampler(STEPS, SET_ROW_FREQS, None, phases=Q, taps=taps_of(Q, P))
+    x = dev(rows)
+    a, la = b.process_rows(x[:, :2000].contiguous())
+    a = host(a)
+    for r in range(R):
+        b.set_row(r, SET_ROW_NEW_STEPS[r], SET_ROW_NEW_FREQS[r])
+    c, lc = b.process_rows(x[:, 2000:].contiguous())
+    f, lf = b.flush()
+    return (a, host(c), host(f)), (la, lc, lf)
+
+
+def set_row_output():
+    """per row, the items of the three calls one after the other"""
+    parts, lens = set_row_calls(make_rows())
+    return [np.concatenate([y[r, :n[r]] for y, n in zip(parts, lens)]) for r in range(R)]
 
 
 def test_set_row_within_the_derived_bound_of_float64(pkg, rows):
     Q, P = 32, 12
     h = taps_of(Q, P)
-    freqs = [WORDS[r % len(WORDS)] for r in range(R)]
-    new_steps = [min(1 << 38, s + s // 8 + 1) for s in STEPS]
-    new_freqs = [-7654321, 0, 1 << 30, -1, 99, -(1 << 31)]
-    b = pkg.StreamRowResampler(STEPS, freqs, None, phases=Q, taps=h)
-    x = dev(rows)
-    a, la = b.process_rows(x[:, :2000].contiguous())
-    a = host(a)
-    for r in range(R):
-        b.set_row(r, new_steps[r], new_freqs[r])
-    c, lc = b.process_rows(x[:, 2000:].contiguous())
-    f, lf = b.flush()
-    c, f = host(c), host(f)
+    freqs, new_steps, new_freqs = SET_ROW_FREQS, SET_ROW_NEW_STEPS, SET_ROW_NEW_FREQS
+    (a, c, f), (la, lc, lf) = set_row_calls(rows)
     worst = 0.0
     for r in range(R):
         row = sref.Row(h, Q, STEPS[r], 0, freqs[r], bits=64)
