@@ -16,7 +16,9 @@ back to back through one continuous filter, without ramp-down, flush or burst sh
 
 `--format sc16 | sc8 | cu8` writes interleaved little-endian int16, int8 or uint8 (I, Q) instead, what a DAC or
 packet_receiver_file.py --format takes: packed on the device (gr4pm_iq_pack: rint(x * gain), cu8 around 127.5,
-clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is printed at the end.
+clamped; `--gain`: default 2^15 or 2^7).  The number of clipped components is printed at the end.  With `--tune` the
+Duc or the FftDuc writes the integers itself (gr4pm_duc_process_iq / gr4pm_fft_duc_process_iq: the same bytes and count
+without the complex64 band in between).
 
 `--tune F --interpolate I`: the file is a wideband stream at I times the modem's rate with the carrier F cycles per file
 sample off centre: a one-channel `Duc` (gr4pm_duc: interpolate by I, mix by +F) sits behind the
@@ -90,20 +92,22 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
             duc = pkg.Duc([0.0 if tune is None else tune], up, decimation=down)
     written = 0
 
+    # a bank behind the transmitter writes an integer format itself: no complex64 band, no second pass
+    bank = {} if fmt == "cf32" else dict(format=fmt, gain=gain, clipped=clipped)
+
     def emit(f, x):
         if fast is not None:
-            emit_wide(f, fast.process_bulk(x))
+            write(f, fast.process_bulk(x, **bank))
         elif duc is not None:
             for lo in range(0, x.numel(), duc.max_items):
-                emit_wide(f, duc.process_bulk(x[lo:lo + duc.max_items]))
+                write(f, duc.process_bulk(x[lo:lo + duc.max_items], **bank))
         else:
-            emit_wide(f, x)
+            write(f, x if fmt == "cf32" else pkg.iq_pack(x, fmt, gain, clipped=clipped))
 
-    def emit_wide(f, x):
+    def write(f, x):
+        """x: complex64 [n], or the file's integer items [n, 2]"""
         nonlocal written
-        written += x.numel()
-        if fmt != "cf32":
-            x = pkg.iq_pack(x, fmt, gain, clipped=clipped)
+        written += x.shape[0]
         f.write(x.cpu().numpy().tobytes())
 
     with open(out_path, "wb") as f:
@@ -113,7 +117,7 @@ def transmit(packets, out_path, stream_mode=False, gap=0, batch=4096, pkg=None, 
             x, _, _ = tx.process_bulk(chunk, gaps=gaps)
             emit(f, x)
         if fast is not None:  # whole segments: what the items so far still owe, the filter's tail included
-            emit_wide(f, fast.flush())
+            write(f, fast.flush(**bank))
         if duc is not None:  # the filter's tail
             emit(f, torch.zeros(len(duc.taps) // duc.interpolation + 1, dtype=torch.complex64, device="cuda"))
     if stats is not None and clipped is not None:

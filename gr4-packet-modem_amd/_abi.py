@@ -387,7 +387,7 @@ EXPORTS = [
     "gr4pm_ddc_frequencies", "gr4pm_ddc_process", "gr4pm_ddc_process_iq",
     "gr4pm_ddc_rational_taps", "gr4pm_ddc_create_rational", "gr4pm_ddc_extract", "gr4pm_ddc_extract_iq",
     "gr4pm_duc_taps", "gr4pm_duc_create", "gr4pm_duc_destroy", "gr4pm_duc_reset", "gr4pm_duc_output_items",
-    "gr4pm_duc_frequencies", "gr4pm_duc_process",
+    "gr4pm_duc_frequencies", "gr4pm_duc_process", "gr4pm_duc_process_iq", "gr4pm_duc_tile_items",
     "gr4pm_duc_rational_taps", "gr4pm_duc_create_rational",
     "gr4pm_spectrum_window", "gr4pm_spectrum_float_run", "gr4pm_spectrum_create", "gr4pm_spectrum_destroy",
     "gr4pm_spectrum_reset", "gr4pm_spectrum_process", "gr4pm_spectrum_process_iq", "gr4pm_spectrum_read",
@@ -408,9 +408,10 @@ EXPORTS = [
     "gr4pm_fft_ddc_mixed_frequencies", "gr4pm_fft_ddc_mixed_sizes", "gr4pm_fft_ddc_mixed_process", "gr4pm_fft_ddc_mixed_process_iq",
     "gr4pm_fft_duc_taps", "gr4pm_fft_duc_create", "gr4pm_fft_duc_destroy", "gr4pm_fft_duc_reset", "gr4pm_fft_duc_output_items",
     "gr4pm_fft_duc_frequencies", "gr4pm_fft_duc_sizes", "gr4pm_fft_duc_pending", "gr4pm_fft_duc_process",
+    "gr4pm_fft_duc_process_iq",
     "gr4pm_fft_duc_mixed_create", "gr4pm_fft_duc_mixed_destroy", "gr4pm_fft_duc_mixed_reset", "gr4pm_fft_duc_mixed_items_for",
     "gr4pm_fft_duc_mixed_output_items", "gr4pm_fft_duc_mixed_frequencies", "gr4pm_fft_duc_mixed_sizes", "gr4pm_fft_duc_mixed_pending",
-    "gr4pm_fft_duc_mixed_process",
+    "gr4pm_fft_duc_mixed_process", "gr4pm_fft_duc_mixed_process_iq",
 ]
 
 _lib = None
@@ -708,6 +709,7 @@ def lib():
     L.gr4pm_fft_duc_sizes.argtypes = [vp, szp, szp]
     L.gr4pm_fft_duc_pending.argtypes = [vp, szp]
     L.gr4pm_fft_duc_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
+    L.gr4pm_fft_duc_process_iq.argtypes = [vp, vp, sz, sz, vp, C.c_int, C.c_float, sz, szp, vp]
     L.gr4pm_fft_duc_mixed_create.argtypes = [C.POINTER(FftDucMixedParams), C.POINTER(vp)]
     L.gr4pm_fft_duc_mixed_destroy.argtypes = [vp]
     L.gr4pm_fft_duc_mixed_destroy.restype = None
@@ -718,6 +720,7 @@ def lib():
     L.gr4pm_fft_duc_mixed_sizes.argtypes = [vp, szp, szp]
     L.gr4pm_fft_duc_mixed_pending.argtypes = [vp, szp]
     L.gr4pm_fft_duc_mixed_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
+    L.gr4pm_fft_duc_mixed_process_iq.argtypes = [vp, vp, sz, sz, vp, C.c_int, C.c_float, sz, szp, vp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]
@@ -726,6 +729,8 @@ def lib():
     L.gr4pm_duc_output_items.argtypes = [vp, sz, szp]
     L.gr4pm_duc_frequencies.argtypes = [vp, vp]
     L.gr4pm_duc_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
+    L.gr4pm_duc_tile_items.argtypes = [vp, szp]
+    L.gr4pm_duc_process_iq.argtypes = [vp, vp, sz, sz, vp, C.c_int, C.c_float, sz, szp, vp]
     L.gr4pm_duc_rational_taps.argtypes = [sz, sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create_rational.argtypes = [C.POINTER(DucRationalParams), C.POINTER(vp)]
     L.gr4pm_iq_unpack.argtypes = [vp, sz, C.c_int, C.c_float, sz, sz, vp, sz, vp]

@@ -1772,6 +1772,27 @@ def iq_pack(x, fmt, gain=None, out=None, clipped=None):
     return out
 
 
+def _iq_out(what, fmt, samples, out, clipped, device):
+    """the integer side of a transmit bank's process_bulk(format=...): the format's number, the tensor [>= samples, 2]
+    of iq_pack's dtype that the call writes (out, or a new one) and the counter's address or None"""
+    torch = _torch()
+    f = IQ_FORMATS.get(str(fmt).lower())
+    if f is None:
+        raise Gr4pmError(f"{what}: unknown format {fmt!r} (sc16, sc8 or cu8)")
+    dtype = {v: k for k, v in _iq_dtypes().items()}[f]
+    if out is None:
+        out = torch.empty((samples, 2), dtype=dtype, device=device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and out.dim() == 2 and out.shape[1] == 2
+              and out.is_contiguous()):
+        raise Gr4pmError(f"{what}: out must be a contiguous CUDA {dtype} tensor [n, 2] for format {fmt!r}")
+    elif out.shape[0] < samples:
+        raise Gr4pmError(f"{what}: out is {tuple(out.shape)}, the call makes [{samples}, 2]")
+    if clipped is not None and not (isinstance(clipped, torch.Tensor) and clipped.is_cuda and clipped.dtype == torch.int64
+                                    and clipped.numel() == 1):
+        raise TypeError("clipped must be a one-element int64 CUDA tensor")
+    return f, out, (None if clipped is None else clipped.data_ptr())
+
+
 def _design_taps(entry, ratio, per, passband, stopband, what):
     """a gr4pm_*_taps entry: the design of per * ratio float32 taps"""
     n = int(ratio) * int(per)
@@ -2367,11 +2388,23 @@ class Duc:
         """back to start_index: zero history"""
         check(lib().gr4pm_duc_reset(self._h), "Duc.reset")
 
-    def process_bulk(self, v, out=None):
+    @property
+    def tile_items(self):
+        """consecutive output samples that one workgroup of the handle's kernel owns; no result depends on it"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_duc_tile_items(self._h, C.byref(n)), "Duc.tile_items")
+        return n.value
+
+    def process_bulk(self, v, out=None, format=None, gain=None, clipped=None):
         """v: a CUDA complex64 tensor [n_channels, n] with contiguous rows and any row stride (a window of a wider
         tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[output_items(n)] (n * interpolation
         samples with decimation = 1); out: an optional contiguous CUDA complex64 tensor of at least that many samples to
-        write into."""
+        write into.
+        format "sc16", "sc8" or "cu8" (gr4pm_duc_process_iq): the kernel writes integer IQ itself, and
+        the call returns iq_pack(process_bulk(v), format, gain, clipped=clipped) byte for byte, [samples, 2] of iq_pack's
+        dtype, without the complex64 band in between; out is then a contiguous tensor [>= samples, 2] of that dtype,
+        gain None the format's default, clipped iq_pack's one-element int64 CUDA tensor.  Calls of any format mix on
+        one handle."""
         torch = _torch()
         if isinstance(v, torch.Tensor) and self.n_channels == 1 and (v.dim() == 1 or (v.dim() == 2 and v.shape[0] == 1)):
             v = _dev_c64(v.reshape(-1) if v.dim() == 2 else v, "v")  # one row: its stride means nothing
@@ -2384,13 +2417,18 @@ class Duc:
         if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
             _inputs_ready(v)  # made on another stream than the handle's
         samples = self.output_items(n_in)
+        n = C.c_size_t(0)
+        if format is not None:
+            f, out, counter = _iq_out("Duc", format, samples, out, clipped, v.device)
+            check(lib().gr4pm_duc_process_iq(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), f, 0.0 if gain is None else float(gain),
+                                             out.shape[0], C.byref(n), counter), "Duc.process_iq")
+            return out[: n.value]
         if out is None:
             out = torch.empty(samples, dtype=torch.complex64, device=v.device)
         else:
             out = _dev_c64(out, "out")
             if out.dim() != 1 or out.numel() < samples:
                 raise Gr4pmError(f"Duc: out is {tuple(out.shape)}, the call makes [{samples}]")
-        n = C.c_size_t(0)
         check(lib().gr4pm_duc_process(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), out.numel(), C.byref(n)),
               "Duc.process")
         return out[: n.value]
@@ -2473,10 +2511,12 @@ class FftDuc:
         check(lib().gr4pm_fft_duc_reset(self._h), "FftDuc.reset")
         self._taken = 0
 
-    def process_bulk(self, v, out=None):
+    def process_bulk(self, v, out=None, format=None, gain=None, clipped=None):
         """v: a CUDA complex64 tensor [n_channels, n] with contiguous rows and any row stride (a window of a wider
         tensor), or a contiguous 1-D tensor when there is one channel.  Returns x[output_items(n)]; out: an optional
-        contiguous CUDA complex64 tensor of at least that many samples to write into."""
+        contiguous CUDA complex64 tensor of at least that many samples to write into.
+        format, gain, clipped: as Duc.process_bulk's (gr4pm_fft_duc_process_iq): integer IQ [samples, 2] from the kernel,
+        iq_pack's bytes and count."""
         torch = _torch()
         if isinstance(v, torch.Tensor) and self.n_channels == 1 and (v.dim() == 1 or (v.dim() == 2 and v.shape[0] == 1)):
             v = _dev_c64(v.reshape(-1) if v.dim() == 2 else v, "v")  # one row: its stride means nothing
@@ -2489,13 +2529,20 @@ class FftDuc:
         if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
             _inputs_ready(v)  # made on another stream than the handle's
         samples = self.output_items(n_in)
+        n = C.c_size_t(0)
+        if format is not None:
+            f, out, counter = _iq_out("FftDuc", format, samples, out, clipped, v.device)
+            check(lib().gr4pm_fft_duc_process_iq(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), f,
+                                                 0.0 if gain is None else float(gain), out.shape[0], C.byref(n), counter),
+                  "FftDuc.process_iq")
+            self._taken += n_in
+            return out[: n.value]
         if out is None:
             out = torch.empty(samples, dtype=torch.complex64, device=v.device)
         else:
             out = _dev_c64(out, "out")
             if out.dim() != 1 or out.numel() < samples:
                 raise Gr4pmError(f"FftDuc: out is {tuple(out.shape)}, the call makes [{samples}]")
-        n = C.c_size_t(0)
         check(lib().gr4pm_fft_duc_process(self._h, v.data_ptr(), stride, n_in, out.data_ptr(), out.numel(), C.byref(n)),
               "FftDuc.process")
         self._taken += n_in
@@ -2511,13 +2558,15 @@ class FftDuc:
         segments = -(-need // self.hop)
         return max(segments * (self.hop // self.interpolation) - self._taken, 0)
 
-    def flush(self):
+    def flush(self, format=None, gain=None, clipped=None):
         """feeds flush_items() zero items per row and returns the samples that come out: with them every sample
         influenced by the items so far is delivered, the prototype's len(taps) - 1 samples of tail included.  The result
-        is bit-equal to process_bulk() of that many zeros, and the stream goes on behind it."""
+        is bit-equal to process_bulk() of that many zeros, and the stream goes on behind it.  format, gain, clipped:
+        process_bulk's."""
         torch = _torch()
         n = self.flush_items()
-        return self.process_bulk(torch.zeros((self.n_channels, n), dtype=torch.complex64, device="cuda"))
+        return self.process_bulk(torch.zeros((self.n_channels, n), dtype=torch.complex64, device="cuda"), format=format, gain=gain,
+                                 clipped=clipped)
 
     def __del__(self):
         _destroy(self, "gr4pm_fft_duc_destroy")
@@ -2608,11 +2657,13 @@ class MixedFftDuc:
         check(lib().gr4pm_fft_duc_mixed_reset(self._h), "MixedFftDuc.reset")
         self._taken = 0
 
-    def process_bulk(self, v, slots=None, out=None):
+    def process_bulk(self, v, slots=None, out=None, format=None, gain=None, clipped=None):
         """v: a CUDA complex64 tensor [n_channels, n_cols] with contiguous rows and any row stride; row k's first
         items_for(slots)[k] items are used.  slots: None for the most that n_cols covers for every row, n_cols *
         min(interpolations) // slot.  Returns x[output_items(slots)]; out: an optional contiguous CUDA complex64 tensor of
-        at least that many samples to write into."""
+        at least that many samples to write into.
+        format, gain, clipped: as Duc.process_bulk's (gr4pm_fft_duc_mixed_process_iq): integer IQ [samples, 2] from the
+        kernel, iq_pack's bytes and count."""
         torch = _torch()
         if isinstance(v, torch.Tensor) and self.n_channels == 1 and v.dim() == 1:
             v = v.reshape(1, -1)
@@ -2627,13 +2678,20 @@ class MixedFftDuc:
         if torch.cuda.current_stream(v.device).cuda_stream != self._stream:
             _inputs_ready(v)  # made on another stream than the handle's
         samples = self.output_items(slots)
+        n = C.c_size_t(0)
+        if format is not None:
+            f, out, counter = _iq_out("MixedFftDuc", format, samples, out, clipped, v.device)
+            check(lib().gr4pm_fft_duc_mixed_process_iq(self._h, v.data_ptr(), stride, slots, out.data_ptr(), f,
+                                                       0.0 if gain is None else float(gain), out.shape[0], C.byref(n), counter),
+                  "MixedFftDuc.process_iq")
+            self._taken += slots
+            return out[: n.value]
         if out is None:
             out = torch.empty(samples, dtype=torch.complex64, device=v.device)
         else:
             out = _dev_c64(out, "out")
             if out.dim() != 1 or out.numel() < samples:
                 raise Gr4pmError(f"MixedFftDuc: out is {tuple(out.shape)}, the call makes [{samples}]")
-        n = C.c_size_t(0)
         check(lib().gr4pm_fft_duc_mixed_process(self._h, v.data_ptr(), stride, slots, out.data_ptr(), out.numel(), C.byref(n)),
               "MixedFftDuc.process")
         self._taken += slots
@@ -2649,14 +2707,15 @@ class MixedFftDuc:
         segments = -(-need // self.hop)
         return max(segments * (self.hop // self.slot) - self._taken, 0)
 
-    def flush(self):
+    def flush(self, format=None, gain=None, clipped=None):
         """feeds flush_items() zero slots and returns the samples that come out: with them every sample influenced by the
         items so far is delivered, the prototypes' tails included.  The result is bit-equal to process_bulk() of that
-        many slots of zeros, and the stream goes on behind it."""
+        many slots of zeros, and the stream goes on behind it.  format, gain, clipped: process_bulk's."""
         torch = _torch()
         n = self.flush_items()
         cols = n * self.slot // int(self.interpolations.min()) if self.n_channels else 0
-        return self.process_bulk(torch.zeros((self.n_channels, cols), dtype=torch.complex64, device="cuda"), slots=n)
+        return self.process_bulk(torch.zeros((self.n_channels, cols), dtype=torch.complex64, device="cuda"), slots=n, format=format,
+                                 gain=gain, clipped=clipped)
 
     def pack(self, rows):
         """rows: a list of n_channels one-dimensional CUDA complex64 tensors, bursts of different lengths at the rows' own

@@ -48,6 +48,12 @@
 // A sample is a function of (absolute output index, the rows' streams) only.  The tile is rduc_geometry()'s, the
 // position hostlogic/resample_position.hpp's with lead = 0: 64-bit integers on the host, by value to the kernel.
 // Both creates are one create(): gr4pm_duc_create's is the ratio I / 1.
+//
+// Integer output (gr4pm_duc_process_iq): both kernels are templated on the output format and pack
+// a sample where the tile leaves (freq_xlate.hpp's store_tile_iq: iq_format.hpp's pack_item on the two samples a lane
+// would have stored, one 8- or 4-byte store); everything in front of the store is the complex64 kernel's, and the
+// handle's state stays complex64.  The clipped components are counted per lane, summed per workgroup and added with one
+// atomic.  The complex64 instantiations take an empty iq::Out behind their arguments and compile to what they were.
 #include "freq_xlate.hpp"
 #include "hostlogic/resample_position.hpp"
 #include "kaiser_design.hpp"
@@ -60,13 +66,14 @@ namespace {
 using namespace gr4pm::hostlogic;
 using gr4pm::cmac;
 using gr4pm::ConstTaps;
+namespace iq = gr4pm::iq;
 
 constexpr size_t kMaxK = 64, kMaxI = 1024, kMaxD = 64, kMaxL = 8192;
 
 struct DucArgs {
     const float2* hist;  // [K][P - 1]: the items in front of in[k][0]
     const float2* in;    // row k at in + k in_stride
-    float2* out;
+    float2* out;         // of an integer format: its items, aligned to the item only
     const uint32_t* w;   // [K] frequency words
     size_t in_stride, n_in, n_out;
     uint32_t pos;        // absolute index of this call's first output sample: the low 32 bits are all the phase needs
@@ -80,8 +87,8 @@ struct TapBlock {
     float2 v[R];
 };
 
-template <int R>
-__global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict__ g)
+template <int R, int F>
+__global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict__ g, iq::Out<F> q)
 {
     extern __shared__ float2 s_duc[];
     const unsigned tid = threadIdx.x;
@@ -164,7 +171,12 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
         const unsigned m = I == 1 ? j : __umulhi(j, a.tile.rcpI);
         return tile[(j - m * I) * TS + m];
     };
-    if (a.vec) { // j0 is even (T I is), so out + j0 keeps the alignment of out
+    if constexpr (F != iq::kC64) { // a.out counts items of F: the tile is packed on its way out, a.vec is not looked at
+        unsigned clip = 0;
+        gr4pm::store_tile_iq<F>(reinterpret_cast<unsigned char*>(a.out) + j0 * iq::Fmt<F>::item_bytes, n, q.gain, clip, sample);
+        // the stage (at least T + Pc - 1 >= 2 items) was last read in front of the barrier above
+        iq::add_clipped<kNt / 64>(clip, q.clipped, reinterpret_cast<unsigned*>(stage));
+    } else if (a.vec) { // j0 is even (T I is), so out + j0 keeps the alignment of out
         gr4pm::store_tile(out, n, 0, sample);
     } else {
         for (unsigned j = tid; j < n; j += kNt) out[j] = sample(j);
@@ -174,7 +186,7 @@ __global__ __launch_bounds__(kNt) void k_duc(DucArgs a, const float2* __restrict
 struct RducArgs {
     const float2* hist;  // [K][P - 1]: the items in front of in[k][0]
     const float2* in;    // row k at in + k in_stride
-    float2* out;
+    float2* out;         // of an integer format: its items, aligned to the item only
     const uint32_t* w;   // [K] frequency words
     size_t in_stride;
     size_t total;        // P - 1 + n_in: items of a row's virtual stream hist ++ in
@@ -187,7 +199,9 @@ struct RducArgs {
 
 // taps: [K][I][P] real taps g_k[p I + r] at [k][r][p], zero where p I + r >= L.  rot: [K][kRotBlock] phasors T_k.
 // Both are written at create only and are parameters of their own.
-__global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* __restrict__ taps, const float2* __restrict__ rot)
+template <int F>
+__global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* __restrict__ taps, const float2* __restrict__ rot,
+                                                      iq::Out<F> q)
 {
     extern __shared__ float2 s_rduc[];
     const unsigned tid = threadIdx.x, lane = tid & 63;
@@ -267,11 +281,19 @@ __global__ __launch_bounds__(kNt) void k_duc_rational(RducArgs a, const float* _
     __syncthreads();
 
     // sample t of the tile is at tile[t mod I][t div I]; one sample alone where out + n0 is only 8-byte aligned
-    float2* __restrict__ out = a.out + n0;
-    gr4pm::store_tile(out, n, static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) >> 3) & 1u, [&](unsigned t) {
+    auto sample = [&](unsigned t) {
         const unsigned l = div_I(t);
         return tile[(t - l * I) * TS + l];
-    });
+    };
+    if constexpr (F != iq::kC64) { // a.out counts items of F
+        unsigned clip = 0;
+        gr4pm::store_tile_iq<F>(reinterpret_cast<unsigned char*>(a.out) + n0 * iq::Fmt<F>::item_bytes, n, q.gain, clip, sample);
+        static_assert(kRotSpan * sizeof(float2) >= kNt / 64 * sizeof(unsigned), "the waves' counts rest in the first group's blocks");
+        iq::add_clipped<kNt / 64>(clip, q.clipped, reinterpret_cast<unsigned*>(blk)); // last read in front of the barrier above
+    } else {
+        float2* __restrict__ out = a.out + n0;
+        gr4pm::store_tile(out, n, static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) >> 3) & 1u, sample);
+    }
 }
 
 // the two designs share their sizes' checks only; their band edges differ: the integer Duc admits passband + stopband
@@ -323,10 +345,34 @@ struct gr4pm_duc {
 
 using namespace gr4pm;
 
-template <int R>
-static void launch_r(dim3 grid, size_t smem, hipStream_t s, const DucArgs& a, const float2* g)
+// the handle's kernel for the output format F
+template <int F>
+static void launch(const gr4pm_duc& h, dim3 grid, const DucArgs& a, iq::Out<F> q)
 {
-    hipLaunchKernelGGL(k_duc<R>, grid, dim3(kNt), smem, s, a, g);
+    switch (h.R) {
+    case 1: hipLaunchKernelGGL((k_duc<1, F>), grid, dim3(kNt), h.smem, h.stream, a, h.d_g.p, q); break;
+    case 2: hipLaunchKernelGGL((k_duc<2, F>), grid, dim3(kNt), h.smem, h.stream, a, h.d_g.p, q); break;
+    case 4: hipLaunchKernelGGL((k_duc<4, F>), grid, dim3(kNt), h.smem, h.stream, a, h.d_g.p, q); break;
+    default: hipLaunchKernelGGL((k_duc<8, F>), grid, dim3(kNt), h.smem, h.stream, a, h.d_g.p, q); break;
+    }
+}
+
+template <int F>
+static void launch(const gr4pm_duc& h, dim3 grid, const RducArgs& a, iq::Out<F> q)
+{
+    hipLaunchKernelGGL(k_duc_rational<F>, grid, dim3(kNt), h.smem, h.stream, a, h.d_taps.p, h.d_rot.p, q);
+}
+
+// either argument struct to the handle's kernel, in the format of the call
+template <typename Args>
+static void launch_format(const gr4pm_duc& h, dim3 grid, const Args& a, int format, float gain, unsigned long long* clipped)
+{
+    switch (format) {
+    case GR4PM_IQ_SC16: launch(h, grid, a, iq::Out<GR4PM_IQ_SC16>{gain, clipped}); break;
+    case GR4PM_IQ_SC8: launch(h, grid, a, iq::Out<GR4PM_IQ_SC8>{gain, clipped}); break;
+    case GR4PM_IQ_CU8: launch(h, grid, a, iq::Out<GR4PM_IQ_CU8>{gain, clipped}); break;
+    default: launch(h, grid, a, iq::Out<iq::kC64>{}); break;
+    }
 }
 
 // both creates: gr4pm_duc_create's handle is the ratio I / 1
@@ -380,7 +426,11 @@ static gr4pm_status create(const gr4pm_duc_rational_params* p, gr4pm_duc** out)
         GR4PM_TRY(h->d_taps.upload(g.data(), g.size(), h->stream));
         GR4PM_TRY(h->d_rot.upload(rot.data(), rot.size(), h->stream));
         if (h->smem > 48 * 1024)
-            GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_duc_rational)}, kRducLdsItemsMost * sizeof(float2), "duc"));
+            GR4PM_TRY(raise_dynamic_lds({reinterpret_cast<const void*>(&k_duc_rational<iq::kC64>),
+                                         reinterpret_cast<const void*>(&k_duc_rational<GR4PM_IQ_SC16>),
+                                         reinterpret_cast<const void*>(&k_duc_rational<GR4PM_IQ_SC8>),
+                                         reinterpret_cast<const void*>(&k_duc_rational<GR4PM_IQ_CU8>)},
+                                        kRducLdsItemsMost * sizeof(float2), "duc"));
     } else {
         DucArgs& a = h->args;
         a.w = h->d_w.p;
@@ -470,6 +520,14 @@ try {
 }
 GR4PM_ABI_CATCH
 
+gr4pm_status gr4pm_duc_tile_items(const gr4pm_duc* h, size_t* samples)
+try {
+    if (!h || !samples) return GR4PM_ERR_INVALID;
+    *samples = h->I * static_cast<size_t>(h->D > 1 ? h->rargs.tile.T : h->args.tile.T);
+    return GR4PM_OK;
+}
+GR4PM_ABI_CATCH
+
 gr4pm_status gr4pm_duc_frequencies(const gr4pm_duc* h, double* out)
 try {
     if (!h || !out) return GR4PM_ERR_INVALID;
@@ -478,11 +536,12 @@ try {
 }
 GR4PM_ABI_CATCH
 
-gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out, size_t out_cap,
-                               size_t* n_out)
-try {
-    if (!h || !n_out) return GR4PM_ERR_INVALID;
-    *n_out = 0;
+} // extern "C"
+
+// process() and process_iq(): format iq::kC64 for complex64 samples.  out and out_cap count items of the format
+static gr4pm_status process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, void* out, int format, float gain,
+                            size_t out_cap, size_t* n_out, unsigned long long* clipped)
+{
     if (n_in > h->max_items) {
         set_error("duc: %zu items per row, the handle was made for %zu", n_in, h->max_items);
         return GR4PM_ERR_OVERFLOW;
@@ -515,18 +574,13 @@ try {
         fill(a);
         a.total = t.H + n_in;
         a.u0 = h->at.first();
-        if (F) hipLaunchKernelGGL(k_duc_rational, grid, dim3(kNt), h->smem, h->stream, a, h->d_taps.p, h->d_rot.p);
+        if (F) launch_format(*h, grid, a, format, gain, clipped);
     } else {
         DucArgs a = h->args;
         fill(a);
         a.n_in = n_in;
         a.vec = reinterpret_cast<uintptr_t>(out) % 16 == 0;
-        switch (h->R) {
-        case 1: launch_r<1>(grid, h->smem, h->stream, a, h->d_g.p); break;
-        case 2: launch_r<2>(grid, h->smem, h->stream, a, h->d_g.p); break;
-        case 4: launch_r<4>(grid, h->smem, h->stream, a, h->d_g.p); break;
-        default: launch_r<8>(grid, h->smem, h->stream, a, h->d_g.p); break;
-        }
+        launch_format(*h, grid, a, format, gain, clipped);
     }
     h->tail.launch_history<iq::kC64>(t, in, in_stride, n_in, 0.0f, h->stream);
     GR4PM_HIP_TRY(hipGetLastError());
@@ -535,6 +589,29 @@ try {
     h->pos += F;
     *n_out = static_cast<size_t>(F);
     return GR4PM_OK;
+}
+
+extern "C" {
+
+gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out, size_t out_cap,
+                               size_t* n_out)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    return process(h, in, in_stride, n_in, out, iq::kC64, 0.0f, out_cap, n_out, nullptr);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_duc_process_iq(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, void* out, int format, float gain,
+                                  size_t out_cap, size_t* n_out, unsigned long long* clipped)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    if (!iq::valid(format)) {
+        set_error("duc: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", format);
+        return GR4PM_ERR_INVALID;
+    }
+    return process(h, in, in_stride, n_in, out, format, gain == 0.0f ? iq::default_gain(format) : gain, out_cap, n_out, clipped);
 }
 GR4PM_ABI_CATCH
 

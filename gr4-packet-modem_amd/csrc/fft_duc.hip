@@ -36,7 +36,12 @@
 // length.
 // Built with FFT_FLAGS: the transforms and the products may contract to FMA.  The rotator is written in explicit fmaf
 // (freq_xlate.hpp's cmac), so it is the Duc's under either set of flags.
-#include "spectrum_segment.hpp"
+// Integer output (gr4pm_fft_duc_process_iq / _mixed_process_iq): k_fft_duc_inverse is templated on
+// the output format and packs a sample where it stores it, an item per lane.  The kernel is fft_duc_inverse.hpp's: this
+// unit instantiates it for complex64, fft_duc_iq.hip for the integer formats, so that this unit's kernels compile as they
+// did before there were any.  iq_format.hpp's pack keeps its product and its sum apart under these flags too (cu8's
+// x gain + 127.5 would fuse where the gain is no power of two), so the bytes are gr4pm_iq_pack's.
+#include "fft_duc_inverse.hpp"
 #include "freq_xlate.hpp"
 #include "hostlogic/fft_duc_mixed_plan.hpp"
 
@@ -283,69 +288,6 @@ __global__ __launch_bounds__(256) void k_fft_duc_mixed_history(const float2* his
     hist_new[r.hist_off + i] = v < H ? hist[r.hist_off + v] : in[k * in_stride + (v - H)];
 }
 
-struct InvArgs {
-    const cf* spec; // [segments of the launch][2048]
-    const float4* tT;
-    const cf* cc;
-    cf* out;        // the call's samples
-    size_t seg0;    // the launch's first segment, counted from the call's
-    uint32_t n_seg; // segments of the launch
-    uint32_t run;   // per wave
-    uint32_t hop, V;
-};
-
-__global__ __launch_bounds__(kW64Threads, 2) void k_fft_duc_inverse(InvArgs a)
-{
-    __shared__ float4 lds4[kW64LdsF4]; // twiddles | eight exchange buffers
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    for (int i = tid; i < kW64TwFloat4; i += kW64Threads) lds4[i] = a.tT[i];
-    __syncthreads(); // the only workgroup-wide synchronisation of the kernel
-    float4* xb4 = lds4 + kW64TwFloat4 + wave * kW64BufF4;
-    const uint32_t base = __builtin_amdgcn_readfirstlane(
-        static_cast<uint32_t>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)xb4)));
-    const float4* row = xb4 + (lane & 31) * (kW64Row / 4);
-    const float4* ldsT = lds4;
-    const cf c = a.cc[lane];
-
-    const uint32_t w = blockIdx.x * kW64Waves + wave;
-    const uint64_t first = static_cast<uint64_t>(w) * a.run;
-    if (first >= a.n_seg) return;
-    const uint32_t count = a.n_seg - first < a.run ? static_cast<uint32_t>(a.n_seg - first) : a.run;
-
-    // half h of the launch's segment `seg`: bins lane + 64 j, j = 16 h .. 16 h + 15, real and imaginary parts swapped
-    auto load_half = [&](cf* dst, uint64_t seg, int h) {
-        const cf* x = a.spec + seg * kN + lane;
-#pragma unroll
-        for (int j = 16 * h; j < 16 * h + 16; ++j) dst[j] = swap_xy(x[64 * j]);
-    };
-
-    cf X[32];
-    load_half(X, first, 0);
-    load_half(X, first, 1);
-    for (uint32_t s = 0; s < count; ++s) {
-        cf bq[32];
-        dft32(X);
-        w64_store(X, base);
-        w64_mid_dev<1, true>(lane, row, ldsT, c, bq);
-        const bool has_next = s + 1 < count;
-        if (has_next) load_half(X, first + s + 1, 0);
-        dft32(bq);
-#pragma unroll
-        for (int k = 0; k < 32; k += 4) w64_pin4(bq + k);
-        if (has_next) load_half(X, first + s + 1, 1);
-        // sample p = lane + 64 j of the segment is out[(seg0 + first + s) hop + p - V] for p >= V
-        // (one address per lane, formed in integers: it lies in front of `out` for the lanes of segment 0 that store nothing
-        // at small j)
-        const int64_t at = static_cast<int64_t>((a.seg0 + first + s) * a.hop + lane) - static_cast<int64_t>(a.V);
-        cf* o = reinterpret_cast<cf*>(reinterpret_cast<intptr_t>(a.out) + at * static_cast<int64_t>(sizeof(cf)));
-#pragma unroll
-        for (int j = 0; j < 32; ++j)
-            if (static_cast<uint32_t>(lane + 64 * j) >= a.V) o[64 * j] = swap_xy(bq[j]);
-    }
-}
-
 // G_k[u] = (a_k / N) sum_t h[t] exp(-2 pi j psi t / 2^32), psi = ((c_k + u) 2^21 - w_k) mod 2^32: the FftDdc's table times
 // the gain; the phase of every term an exact integer, the sum in double, each component rounded to float once
 float2 response(const std::vector<float>& h, double gain, uint32_t w, uint32_t c, int32_t u)
@@ -434,13 +376,20 @@ gr4pm_status transform_tables(FftDucBank& h, TransformTables& t)
 }
 
 // the inverse transforms of the `segs` spectra of a launch pair, the call's segments from `done` on
-void launch_inverse(const FftDucBank& h, InvArgs b, size_t done, size_t segs)
+// in the call's format: iq::kC64 for complex64, where gain and clipped are not looked at
+void launch_inverse(const FftDucBank& h, InvArgs b, size_t done, size_t segs, int format, float gain, unsigned long long* clipped)
 {
     const size_t per_wave = (segs + h.max_waves - 1) / h.max_waves;
     const size_t waves = (segs + per_wave - 1) / per_wave;
     b.seg0 = done, b.n_seg = static_cast<uint32_t>(segs), b.run = static_cast<uint32_t>(per_wave);
-    hipLaunchKernelGGL(k_fft_duc_inverse, dim3(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves)), dim3(kW64Threads), 0, h.stream,
-                       b);
+    const dim3 grid(static_cast<unsigned>((waves + kW64Waves - 1) / kW64Waves));
+    InvArgsIq bi = {};
+    static_cast<InvArgs&>(bi) = b;
+    bi.gain = gain, bi.clipped = clipped;
+    if (format == iq::kC64)
+        hipLaunchKernelGGL(k_fft_duc_inverse<iq::kC64>, grid, dim3(kW64Threads), 0, h.stream, b);
+    else
+        fft_duc_launch_inverse_iq(grid, h.stream, bi, format);
 }
 
 // dynamic LDS of both assembling kernels
@@ -556,6 +505,16 @@ gr4pm_status check_slots(const FftDucBank& h, size_t slots)
     return GR4PM_OK;
 }
 
+// a process_iq()'s format: one of the three integer ones (iq::kC64 is the bank's name for complex64, not the ABI's)
+gr4pm_status check_format(const FftDucBank& h, int format)
+{
+    if (!iq::valid(format)) {
+        set_error("%s: format %d is none of GR4PM_IQ_SC16 / SC8 / CU8", h.name, format);
+        return GR4PM_ERR_INVALID;
+    }
+    return GR4PM_OK;
+}
+
 // the same bound in the FftDuc's words, where a slot is an item: its fronts ask this before the bank asks check_slots()
 gr4pm_status check_items(size_t n_in)
 {
@@ -574,10 +533,13 @@ gr4pm_status output_items(const FftDucBank& h, size_t slots, size_t* n_out)
     return GR4PM_OK;
 }
 
-// The call of both handles: `slots` slots of every row, row k's items at in + k in_stride
-gr4pm_status process(FftDucBank& h, const gr4pm_c64* in, size_t in_stride, size_t slots, gr4pm_c64* out, size_t out_cap, size_t* n_out)
+// The call of both handles, process() and process_iq(): `slots` slots of every row, row k's items at in + k in_stride;
+// format iq::kC64 for complex64 samples, else out and out_cap count items of the format
+gr4pm_status process(FftDucBank& h, const gr4pm_c64* in, size_t in_stride, size_t slots, void* out, int format, float gain, size_t out_cap,
+                     size_t* n_out, unsigned long long* clipped)
 {
     *n_out = 0;
+    if (format != iq::kC64 && gain == 0.0f) gain = iq::default_gain(format);
     GR4PM_TRY(check_slots(h, slots));
     if (slots == 0) return GR4PM_OK;
     const FftDucPlan p = fft_duc_plan(h.shape, h.taken, slots); // in slots: a row's items are its ratio times these
@@ -615,7 +577,7 @@ gr4pm_status process(FftDucBank& h, const gr4pm_c64* in, size_t in_stride, size_
             hipLaunchKernelGGL(k_fft_duc_assemble, dim3(static_cast<unsigned>(segs)), dim3(kAsmThreads), lds, h.stream, u);
         else
             hipLaunchKernelGGL(k_fft_duc_mixed_assemble, dim3(static_cast<unsigned>(segs)), dim3(kAsmThreads), lds, h.stream, a);
-        launch_inverse(h, b, done, segs);
+        launch_inverse(h, b, done, segs, format, gain, clipped);
         done += segs;
     }
     // the rows' new carried items into the other buffer, p.left slots' worth each (nothing left: no launch, no swap)
@@ -778,7 +740,18 @@ try {
     if (!h || !n_out) return GR4PM_ERR_INVALID;
     *n_out = 0;
     GR4PM_TRY(check_items(n_in));
-    return process(*h, in, in_stride, n_in, out, out_cap, n_out);
+    return process(*h, in, in_stride, n_in, out, iq::kC64, 0.0f, out_cap, n_out, nullptr);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_process_iq(gr4pm_fft_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, void* out, int format,
+                                      float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    GR4PM_TRY(check_format(*h, format));
+    GR4PM_TRY(check_items(n_in));
+    return process(*h, in, in_stride, n_in, out, format, gain, out_cap, n_out, clipped);
 }
 GR4PM_ABI_CATCH
 
@@ -866,7 +839,17 @@ gr4pm_status gr4pm_fft_duc_mixed_process(gr4pm_fft_duc_mixed* h, const gr4pm_c64
                                          size_t out_cap, size_t* n_out)
 try {
     if (!h || !n_out) return GR4PM_ERR_INVALID;
-    return process(*h, in, in_stride, slots, out, out_cap, n_out);
+    return process(*h, in, in_stride, slots, out, iq::kC64, 0.0f, out_cap, n_out, nullptr);
+}
+GR4PM_ABI_CATCH
+
+gr4pm_status gr4pm_fft_duc_mixed_process_iq(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, void* out,
+                                            int format, float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped)
+try {
+    if (!h || !n_out) return GR4PM_ERR_INVALID;
+    *n_out = 0;
+    GR4PM_TRY(check_format(*h, format));
+    return process(*h, in, in_stride, slots, out, format, gain, out_cap, n_out, clipped);
 }
 GR4PM_ABI_CATCH
 

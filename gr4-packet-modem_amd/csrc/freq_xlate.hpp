@@ -6,6 +6,7 @@
 #pragma once
 #include "common.hpp"
 #include "hostlogic/xlate_geometry.hpp"
+#include "iq_format.hpp"
 
 #include <cmath>
 #include <cstdint>
@@ -89,6 +90,32 @@ __device__ __forceinline__ void store_tile(float2* __restrict__ out, unsigned n,
             *reinterpret_cast<float4*>(out + t) = float4{lo.x, lo.y, hi.x, hi.y};
         } else {
             out[t] = sample(t);
+        }
+    }
+}
+
+// the same tile as integer IQ: items 0 .. n of format F at `out`, item t = pack_item(sample(t)), by the workgroup's kNt
+// threads.  A lane packs the two samples it would have stored as complex64 (the same tile reads) and stores them as one
+// word pair (sc16: 8 bytes) or one word (sc8, cu8: 4 bytes), so a wave instruction writes 512 or 256 contiguous bytes.
+// `out` is aligned to its item only: where it is not aligned to the pair, item 0 leaves alone (head = 1), and the pairs
+// behind it are aligned
+template <int F, typename Sample>
+__device__ __forceinline__ void store_tile_iq(unsigned char* __restrict__ out, unsigned n, float gain, unsigned& clipped, Sample&& sample)
+{
+    constexpr unsigned IB = iq::Fmt<F>::item_bytes;
+    const unsigned tid = threadIdx.x;
+    const unsigned head = static_cast<unsigned>(reinterpret_cast<uintptr_t>(out) / IB) & 1u;
+    if (tid == 0 && head && n) iq::put_item<F>(out, 0, iq::pack_item<F>(sample(0), gain, clipped));
+    for (unsigned t = head + 2 * tid; t < n; t += 2 * kNt) {
+        const uint32_t lo = iq::pack_item<F>(sample(t), gain, clipped);
+        if (t + 1 < n) {
+            const uint32_t hi = iq::pack_item<F>(sample(t + 1), gain, clipped);
+            if constexpr (IB == 4)
+                *reinterpret_cast<uint2*>(out + static_cast<size_t>(t) * IB) = uint2{lo, hi};
+            else
+                *reinterpret_cast<uint32_t*>(out + static_cast<size_t>(t) * IB) = lo | (hi << 16);
+        } else {
+            iq::put_item<F>(out, t, lo);
         }
     }
 }

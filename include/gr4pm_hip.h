@@ -1226,6 +1226,9 @@ gr4pm_status gr4pm_duc_reset(gr4pm_duc* h);
 gr4pm_status gr4pm_duc_output_items(const gr4pm_duc* h, size_t n_in, size_t* n_out);
 /* out: K doubles (host), the quantised frequencies w_k / 2^32 folded to [-0.5, 0.5) */
 gr4pm_status gr4pm_duc_frequencies(const gr4pm_duc* h, double* out);
+/* the consecutive output samples one workgroup of the handle's kernel owns (its tile): what a test needs to know to cut
+ * a call across a tile's end; no result depends on it */
+gr4pm_status gr4pm_duc_tile_items(const gr4pm_duc* h, size_t* samples);
 /* in: DEVICE, row k at in + k in_stride, n_in items each (any number).  out: DEVICE, contiguous, out_cap
  * samples of room; *n_out = n_in I samples are written.  A refused call -- a NULL pointer, in_stride < n_in
  * with K > 1 (GR4PM_ERR_INVALID), more than max_items items or fewer than n_in I samples of room
@@ -1233,6 +1236,16 @@ gr4pm_status gr4pm_duc_frequencies(const gr4pm_duc* h, double* out);
  * stream. */
 gr4pm_status gr4pm_duc_process(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
                                size_t out_cap, size_t* n_out);
+/* The same call with the samples written as integer IQ (gr4pm_iq_format, below): out is
+ * DEVICE memory in ITEMS of `format` (2 or 4 bytes, aligned to the item only), out_cap counts items, gain 0 is
+ * the format's default, clipped is NULL or a DEVICE counter the call ADDS to.  The bytes and the count are
+ * gr4pm_iq_pack's of what gr4pm_duc_process would have written: the kernel packs each sample where it holds it
+ * and has no complex64 store.  Serves rational handles too.  The handle's state stays complex64: calls of any
+ * format mix on one handle.  An unknown format (GR4PM_ERR_INVALID) and everything gr4pm_duc_process refuses,
+ * with its status, are refused before anything is enqueued: gr4pm_last_error set, *n_out = 0, the stream not
+ * moved. */
+gr4pm_status gr4pm_duc_process_iq(gr4pm_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, void* out, int format,
+                                  float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped);
 
 /* ------------------------------------------------------------------------------------
  * Duc, rational resampling by I / D (output rate fs_in I / D) in the same pass: a gr4pm_duc handle made by
@@ -1986,6 +1999,12 @@ gr4pm_status gr4pm_fft_duc_pending(const gr4pm_fft_duc* h, size_t* items);
  * (GR4PM_ERR_INVALID); n_in > 2^40 or fewer than the samples of room (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
 gr4pm_status gr4pm_fft_duc_process(gr4pm_fft_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, gr4pm_c64* out,
                                    size_t out_cap, size_t* n_out);
+/* The same call with the samples written as integer IQ, with gr4pm_duc_process_iq's contract:
+ * out in items of `format`, out_cap in items, gain 0 the format's default, clipped NULL or a DEVICE counter the call
+ * adds to; the bytes and the count are gr4pm_iq_pack's of what gr4pm_fft_duc_process would have written.  An unknown
+ * format (GR4PM_ERR_INVALID) and whatever gr4pm_fft_duc_process refuses are refused before anything is enqueued. */
+gr4pm_status gr4pm_fft_duc_process_iq(gr4pm_fft_duc* h, const gr4pm_c64* in, size_t in_stride, size_t n_in, void* out, int format,
+                                      float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped);
 
 /* ---- MixedFftDuc: an interpolation per row into one shared transform (the project's own block) --
  * The FftDuc with its restriction to one interpolation lifted: carriers of different symbol rates onto one stream in one
@@ -2042,6 +2061,9 @@ gr4pm_status gr4pm_fft_duc_mixed_pending(const gr4pm_fft_duc_mixed* h, size_t* s
  * (GR4PM_ERR_OVERFLOW).  The handle stays usable. */
 gr4pm_status gr4pm_fft_duc_mixed_process(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, gr4pm_c64* out,
                                          size_t out_cap, size_t* n_out);
+/* The same call with the samples written as integer IQ: gr4pm_fft_duc_process_iq's contract on this handle */
+gr4pm_status gr4pm_fft_duc_mixed_process_iq(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, void* out,
+                                            int format, float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the Duc (csrc/duc.hip) against a copy of the output's bytes and against the Ddc, in the same process.
 
-  tools/benchmark_duc.py [--log2-items 28] [--iters 10] [--shape store|issue|both] [--rational]
+  tools/benchmark_duc.py [--log2-items 28] [--iters 10] [--shape store|issue|both] [--rational] [--format sc16|sc8|cu8]
 
 One process_bulk() call that makes 2^log2-items wideband samples per iteration, timed with device events; the median
 over the iterations, in Gsamples/s of OUTPUT.  One JSON line per shape:
@@ -19,7 +19,11 @@ samples per call):
   store  K = 1, 25 / 4, L = 300: 8 B written and 8 * 4 / 25 B read per output sample, 2 K P = 24 FMAs for the filter
          and 8 K for the rotator and the mix; against the copy of the output's bytes, as above.
   issue  K = 8, 16 / 3, L = 192: 2 K P + 8 K = 256 FMAs per output sample (the real-tap loop does half the FMAs per tap of
-         k_duc, the rotator comes per output sample instead of per input item); against the vector FMA peak."""
+         k_duc, the rotator comes per output sample instead of per input item); against the vector FMA peak.
+
+--format F: per shape also the integer output (gr4pm_duc_process_iq), three more figures from the same
+process (tools/iq_out_timing.py): the fused call that writes F, the complex64 call again, and that call followed by
+iq_pack()."""
 import argparse
 import json
 import os
@@ -27,6 +31,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from iq_out_timing import iq_out_figures  # noqa: E402
 
 PEAK_FMA_PER_S = 157.3e12 / 2
 SHAPES = {"store": dict(K=1, I=4, L=48), "issue": dict(K=8, I=16, L=192)}
@@ -56,6 +62,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--shape", choices=["store", "issue", "both"], default="both")
     ap.add_argument("--rational", action="store_true", help="the Duc resampling by I / D beside the integer Duc")
+    ap.add_argument("--format", choices=["sc16", "sc8", "cu8"], help="also the integer output: fused, complex64, complex64 + iq_pack")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -81,6 +88,8 @@ def main():
                "fma_per_sample": fma_per_sample, "tfma_per_s": round(gsps * fma_per_sample / 1e3, 2),
                "fma_ceiling_gsamples_per_s": round(PEAK_FMA_PER_S / fma_per_sample / 1e9, 1),
                "share_of_fma_ceiling": round(gsps * 1e9 * fma_per_sample / PEAK_FMA_PER_S, 3)}
+        if args.format:
+            res.update(iq_out_figures(pkg, torch, median_ms, args.iters, args.format, n, lambda **kw: d.process_bulk(v, **kw)))
         del d, v
         # the integer Duc at the same I, K and L, as many output samples
         vi = torch.view_as_complex(torch.randn((K, n // I, 2), dtype=torch.float32, device="cuda", generator=g))
@@ -112,6 +121,8 @@ def main():
                "tfma_per_s": round(gsps * fma_per_sample / 1e3, 2),
                "fma_ceiling_gsamples_per_s": round(PEAK_FMA_PER_S / fma_per_sample / 1e9, 1),
                "share_of_fma_ceiling": round(gsps * 1e9 * fma_per_sample / PEAK_FMA_PER_S, 3)}
+        if args.format:
+            res.update(iq_out_figures(pkg, torch, median_ms, args.iters, args.format, n, lambda **kw: d.process_bulk(v, **kw)))
         if name == "store":  # the copy of the output's bytes
             src = torch.empty(n, dtype=torch.complex64, device="cuda")
             ms_copy = median_ms(lambda: out.copy_(src), args.iters, torch)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Rate of the MixedFftDuc block (csrc/fft_duc.hip) beside what it replaces, all in the same process.
 
-  tools/benchmark_fft_duc_mixed.py [--log2-items 28] [--iters 20]
+  tools/benchmark_fft_duc_mixed.py [--log2-items 28] [--iters 20] [--format sc16|sc8|cu8]
 
 K = 24 rows, 8 each at I = 16, 32 and 64, default taps (12 a phase), two images, over one call of 2^log2-items output
 samples' worth of items (2^log2-items / I_k items in row k; the whole segments among them are delivered) into a
@@ -10,7 +10,9 @@ preallocated output; timed with device events, the median over the iterations:
   three      three FftDuc handles of 8 rows each at I = 16, 32, 64 and the same overlap into three outputs, and the two
              additions that make one stream of them: what a user does without the block
   all_at_16  FftDuc of the 24 frequencies at I = 16 and the same overlap (every row with the I = 16 rows' item count)
-Prints one JSON line."""
+Prints one JSON line.  --format F: also the integer output of the mixed handle (gr4pm_fft_duc_mixed_process_iq, DESIGN
+section 31), three more figures from the same process (tools/iq_out_timing.py): the fused call that writes F, the
+complex64 call again, and that call followed by iq_pack()."""
 import argparse
 import json
 import os
@@ -20,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from benchmark_channelizer import median_ms  # noqa: E402
+from iq_out_timing import iq_out_figures  # noqa: E402
 
 INTERPOLATIONS = [16] * 8 + [32] * 8 + [64] * 8
 
@@ -28,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--log2-items", type=int, default=28)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--format", choices=["sc16", "sc8", "cu8"], help="also the integer output: fused, complex64, complex64 + iq_pack")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -66,10 +70,16 @@ def main():
     ms = median_ms(run_mixed, args.iters, torch)
     ms_three = median_ms(run_three, args.iters, torch)
     ms_16 = median_ms(run_at16, args.iters, torch)
+
+    def run_format(**kw):
+        mixed.reset()
+        return mixed.process_bulk(v, slots, **kw)
+
+    extra = iq_out_figures(pkg, torch, median_ms, args.iters, args.format, n, run_format) if args.format else {}
     print(json.dumps({"tool": "benchmark_fft_duc_mixed", "rows": K, "interpolations": "8 x 16, 8 x 32, 8 x 64", "overlap": V, "images": 2,
                       "samples": samples, "mixed_ms": round(ms, 4), "mixed_gsamples_per_s": round(samples / ms / 1e6, 2),
                       "three_handles_ms": round(ms_three, 4), "three_over_mixed": round(ms_three / ms, 3),
-                      "all_at_16_ms": round(ms_16, 4), "all_at_16_over_mixed": round(ms_16 / ms, 3),
+                      "all_at_16_ms": round(ms_16, 4), "all_at_16_over_mixed": round(ms_16 / ms, 3), **extra,
                       "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
