@@ -3,7 +3,7 @@
 
     packet_receiver_file.py input_file [syncword_freq_bins=4] [syncword_threshold=9.5] [--out packets.bin] [--zmq]
                             [--format {cf32,sc16,sc8,cu8}] [--scale S] [--tune CYCLES_PER_SAMPLE|auto --decimate N[/M]]
-                            [--refine] [--decimate auto] [--burst-rows] [--fft-ddc]
+                            [--refine] [--decimate auto] [--burst-rows] [--fft-ddc] [--notch F:BW ...] [--notch-taps N]
                             [--scan [--scan-items N] [--bursts] [--waterfall FILE.npy [--waterfall-average R]]]
 
 reads IQ samples from `input_file` in raw little-endian complex64 (std::complex<float>, what
@@ -59,6 +59,14 @@ symbol and removes its residual offset ON THE ROWS, each row with its own measur
 N/M, and its own offset; a row whose carrier line stands less than 6 dB above the rest takes the carrier's medians.  The
 receiver takes the rows.  No streaming `Ddc` runs over the file, and the rate need not be a simple fraction.  If no row
 shows a carrier line, the app says so and falls back to the streaming path.
+
+`--notch F:BW` (repeatable), `--notch-taps N` (odd, default 1025): the band BW cycles per file sample wide around F is
+removed from the file's samples before anything else sees them: a CW interferer inside the channel, the DC spike of an
+rtl_sdr recording (`--notch 0:0.004`), a strong neighbour.  The bands become one band-stop design (`band_filter_taps`, 60
+dB) in an `FftFilter` (gr4pm_fft_filter: fast convolution) in front of the plain receiver, of `--tune`
+and of `--fft-ddc`; it reads the file's format itself and is flushed at the end of the file, so as many samples come out
+as went in, delayed by (N - 1) / 2.  It goes with none of the scanning options (`--scan`, `--tune auto`, `--refine`,
+`--decimate auto`, `--burst-rows`), which look at the file as it is.
 
 The file is streamed: host chunks are staged in pinned memory and copied to the device on a
 copy stream while the previous chunk is being processed; the samples the detector leaves
@@ -255,24 +263,39 @@ def receive_burst_rows(b, syncword_freq_bins=4, syncword_threshold=9.5, rate=Non
     return {"packets": packets, "items": items, "file_items": items, "seconds": dt, "rates": rates, "offsets": offsets, **stats}
 
 
+def notch_band(v):
+    """--notch: `F:BW`, centre and width in cycles per file sample, as (F, BW)"""
+    f, sep, bw = str(v).partition(":")
+    try:
+        if not sep:
+            raise ValueError
+        return float(f), float(bw)
+    except ValueError:
+        raise ValueError(f"--notch: {v!r} is not F:BW") from None
+
+
 def tune_value(v):
     """--tune: cycles per file sample, or `auto`"""
     return "auto" if str(v).lower() == "auto" else float(v)
 
 
 def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items=1 << 24, out=None, pkg=None, zmq_ports=None,
-                 fmt="cf32", scale=None, tune=None, decimate=None, fft_ddc=False):
+                 fmt="cf32", scale=None, tune=None, decimate=None, fft_ddc=False, notch=None):
     """returns dict(packets: list of bytes, items, seconds, headers, invalid_headers, crc_failures).  decimate: an
-    integer, "N/M" or (N, M).  fft_ddc: an FftDdc in place of the Ddc (a power-of-two decimation)"""
+    integer, "N/M" or (N, M).  fft_ddc: an FftDdc in place of the Ddc (a power-of-two decimation).  notch: complex taps
+    of an FftFilter in front of everything else (None: none), flushed at the end of the file"""
     pkg = pkg or ge.load_package()
     file_dtype = FILE_DTYPES[fmt]
     shape = (chunk_items,) if fmt == "cf32" else (chunk_items, 2)  # integer IQ: [items, (I, Q)]
     item_bytes = 8 if fmt == "cf32" else 2 * file_dtype.itemsize
     n_file = os.path.getsize(path) // item_bytes
     dev = torch.device("cuda", torch.cuda.current_device())
+    # a filter in front hands on whole segments: up to one of them more than a chunk holds
+    filt = None if notch is None else pkg.FftFilter(notch)
+    room = chunk_items + 4096 + (0 if filt is None else 2048)
     # packets_only: nothing between the Costas loop and the packer is written to memory (the app delivers packets); the
     # symbol tap of --zmq needs SyncwordRemove's output stream, i.e. the full form
-    rx = pkg.NativePacketReceiver(4, syncword_freq_bins, syncword_threshold, max_items=chunk_items + 4096,
+    rx = pkg.NativePacketReceiver(4, syncword_freq_bins, syncword_threshold, max_items=room,
                                   tags_cap=chunk_items // 768 + 64, decode_headers=True, packets_only=zmq_ports is None)
     if zmq_ports is not None:  # packet_receiver.hpp:163-168
         rx.publish_symbol_pdus(f"tcp://*:{zmq_ports[0]}", f"tcp://*:{zmq_ports[1]}")
@@ -282,11 +305,12 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
         if fft_ddc:
             ddc = pkg.FftDdc([0.0 if tune is None else tune], dec)
         else:
-            ddc = pkg.Ddc([0.0 if tune is None else tune], dec, interpolation=interp, max_frames=chunk_items)
+            ddc = pkg.Ddc([0.0 if tune is None else tune], dec, interpolation=interp, max_frames=room - 4096)
     fft = 3072  # smallest batch the receiver takes in this mode (one header window + one FFT block)
     pinned = [torch.empty(shape, dtype=file_dtype).pin_memory() for _ in range(2)]
     staged = [torch.empty(shape, dtype=file_dtype, device=dev) for _ in range(2)]
-    work = torch.empty(chunk_items + 4096, dtype=torch.complex64, device=dev)
+    work = torch.empty(room, dtype=torch.complex64, device=dev)
+    filtered = None if filt is None else torch.empty(chunk_items + 2048, dtype=torch.complex64, device=dev)
     copy_stream = torch.cuda.Stream()
     events = [torch.cuda.Event(), torch.cuda.Event()]
     packets, stats = [], {"headers": 0, "invalid_headers": 0, "crc_failures": 0}
@@ -322,14 +346,25 @@ def receive_file(path, syncword_freq_bins=4, syncword_threshold=9.5, chunk_items
         nxt = 0
         if got:
             torch.cuda.current_stream().wait_event(events[slot])
-            if ddc is not None:
-                got = ddc.process_bulk(staged[slot][:got], out=work[left:left + got].unsqueeze(0),
-                                       scale=None if fmt == "cf32" else scale).shape[1]
-            elif fmt == "cf32":
-                work[left:left + got].copy_(staged[slot][:got])
+            if filt is not None:
+                # the notch first: the chunk's whole segments as complex64, and at the end of the file what is still owed
+                got = filt.process_bulk(staged[slot][:got], scale=None if fmt == "cf32" else scale, out=filtered).numel()
+                nxt = load(slot ^ 1)
+                if not nxt:
+                    got += filt.flush(out=filtered[got:]).numel()
+                if ddc is not None:
+                    got = ddc.process_bulk(filtered[:got], out=work[left:left + got].unsqueeze(0)).shape[1] if got else 0
+                else:
+                    work[left:left + got].copy_(filtered[:got])
             else:
-                pkg.iq_unpack(staged[slot][:got], scale, out=work[left:left + got])
-            nxt = load(slot ^ 1)          # the next chunk travels while this one is processed
+                if ddc is not None:
+                    got = ddc.process_bulk(staged[slot][:got], out=work[left:left + got].unsqueeze(0),
+                                           scale=None if fmt == "cf32" else scale).shape[1]
+                elif fmt == "cf32":
+                    work[left:left + got].copy_(staged[slot][:got])
+                else:
+                    pkg.iq_unpack(staged[slot][:got], scale, out=work[left:left + got])
+                nxt = load(slot ^ 1)          # the next chunk travels while this one is processed
         n = left + got
         if n < fft:
             break
@@ -393,7 +428,15 @@ def main(argv=None):
                     help="with --tune and a power-of-two --decimate of 4 .. 64: an FftDdc (the fast-convolution form, DESIGN "
                          "section 25) in place of the Ddc; it delivers whole segments, so up to one hop of samples at the "
                          "end of the file stays undelivered")
+    ap.add_argument("--notch", action="append", type=notch_band, metavar="F:BW",
+                    help="remove the band BW cycles per file sample wide around F from the file's samples before anything else "
+                         "sees them (an FftFilter, DESIGN section 32); repeatable")
+    ap.add_argument("--notch-taps", type=int, default=1025, metavar="N", help="taps of the --notch design (odd, 3 .. 1985; default 1025)")
     a = ap.parse_args(argv)
+    if a.notch and (a.scan or a.tune == "auto" or a.refine or a.decimate == "auto" or a.burst_rows):
+        ap.error("--notch goes with none of --scan, --tune auto, --refine, --decimate auto, --burst-rows")
+    if a.notch and a.chunk_items < 2048:
+        ap.error("--notch needs --chunk-items of at least 2048")
     if a.fft_ddc:
         d = a.decimate
         if (a.tune is None or not isinstance(d, tuple) or d[1] != 1 or d[0] not in (4, 8, 16, 32, 64) or a.burst_rows
@@ -458,8 +501,9 @@ def main(argv=None):
                 a.decimate = (dec, interp)
                 print(f"--decimate auto: {r['rate']:.6f} symbols per file sample: --decimate {dec}/{interp}")
     zmq_ports = tuple(a.zmq_ports) if a.zmq_ports else ((5000, 5001) if a.zmq else None)
+    notch = ge.load_package().band_filter_taps(a.notch, "stop", a.notch_taps) if a.notch else None
     r = receive_file(a.input_file, a.syncword_freq_bins, a.syncword_threshold, a.chunk_items, a.out, zmq_ports=zmq_ports,
-                     fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate, fft_ddc=a.fft_ddc)
+                     fmt=a.format, scale=a.scale, tune=a.tune, decimate=a.decimate, fft_ddc=a.fft_ddc, notch=notch)
     print(f"{r['items']} of {r['file_items']} samples in {r['seconds']:.3f} s = {r['items'] / r['seconds'] / 1e6:.1f} Msps "
           f"(file and PCIe included); headers {r['headers']} ({r['invalid_headers']} invalid), packets "
           f"{len(r['packets'])} ({r['crc_failures']} CRC failures), {sum(len(p) for p in r['packets'])} bytes")

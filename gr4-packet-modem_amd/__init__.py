@@ -9,7 +9,7 @@ import numpy as np
 
 from ._abi import (EXPORTS, LIB_PATH, PACKET_TAG_DTYPE, PKT_HEADER_START, PKT_PAYLOAD, PKT_SYNCWORD,  # noqa: F401
                    TAG_DTYPE, TAG_OTHER, TAG_SYNCWORD, Gr4pmError, lib)
-from .blocks import (SYNCWORD, ZmqPduPubSink, NoiseSource, Channel, Channelizer, channelizer_taps, Ddc, ddc_taps, ddc_rational_taps, ddc_burst_span, FftDdc, fft_ddc_taps, MixedFftDdc, fft_ddc_decimation, Duc, duc_taps, duc_rational_taps, FftDuc, fft_duc_taps, MixedFftDuc, Spectrum, spectrum_window, find_carriers, count_carriers, Spectrogram, find_bursts, LineSpectrum, find_line, simplest_ratio, resample_ratio, provisional_decimation, RowResampler, row_resampler_taps, StreamRowResampler, RowBurstGate, RowPacketReceivers, iq_unpack, iq_pack, IQ_FORMATS, NOISE_TYPES, AdditiveScrambler, BurstGenerator, PacketTransmitter, CrcCheck, burst_shaper, mapper, binary_slicer, pack_bits, slice_pack, CoarseFrequencyCorrection, ConstellationLLRDecoder,  # noqa: F401
+from .blocks import (SYNCWORD, ZmqPduPubSink, NoiseSource, Channel, Channelizer, channelizer_taps, Ddc, ddc_taps, ddc_rational_taps, ddc_burst_span, FftDdc, fft_ddc_taps, MixedFftDdc, fft_ddc_decimation, Duc, duc_taps, duc_rational_taps, FftDuc, fft_duc_taps, MixedFftDuc, FftFilter, band_filter_taps, notch_taps, Spectrum, spectrum_window, find_carriers, count_carriers, Spectrogram, find_bursts, LineSpectrum, find_line, simplest_ratio, resample_ratio, provisional_decimation, RowResampler, row_resampler_taps, StreamRowResampler, RowBurstGate, RowPacketReceivers, iq_unpack, iq_pack, IQ_FORMATS, NOISE_TYPES, AdditiveScrambler, BurstGenerator, PacketTransmitter, CrcCheck, burst_shaper, mapper, binary_slicer, pack_bits, slice_pack, CoarseFrequencyCorrection, ConstellationLLRDecoder,  # noqa: F401
                      CostasLoop, HeaderDecoder, HeaderFecDecoder, HeaderPayloadSplit, InterpolatingFirFilter, MultiChannelPacketReceiver, NativeMultiChannelReceiver, NativePacketReceiver, PacketReceiver,
                      PayloadMetadataInsert, PfbArbResampler, Rotator, SymbolFilter, SyncwordDetection,
                      SyncwordDetectionFilter, SyncwordRemove, SyncwordWipeoff, cfc_symbol_filter, cfc_symbol_filter_plan, cfc_symbol_filter_run,

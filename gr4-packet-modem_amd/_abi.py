@@ -224,6 +224,10 @@ class SpectrumParams(C.Structure):
     _fields_ = [("fft_size", C.c_uint32), ("hop", C.c_uint32), ("window", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class FftFilterParams(C.Structure):
+    _fields_ = [("taps", C.c_void_p), ("n_taps", C.c_size_t), ("overlap", C.c_size_t), ("stream", C.c_void_p)]
+
+
 class CarrierParams(C.Structure):
     _fields_ = [("threshold_db", C.c_double), ("max_gap_bins", C.c_size_t), ("min_width_bins", C.c_size_t)]
 
@@ -412,6 +416,9 @@ EXPORTS = [
     "gr4pm_fft_duc_mixed_create", "gr4pm_fft_duc_mixed_destroy", "gr4pm_fft_duc_mixed_reset", "gr4pm_fft_duc_mixed_items_for",
     "gr4pm_fft_duc_mixed_output_items", "gr4pm_fft_duc_mixed_frequencies", "gr4pm_fft_duc_mixed_sizes", "gr4pm_fft_duc_mixed_pending",
     "gr4pm_fft_duc_mixed_process", "gr4pm_fft_duc_mixed_process_iq",
+    "gr4pm_fft_filter_create", "gr4pm_fft_filter_destroy", "gr4pm_fft_filter_reset", "gr4pm_fft_filter_set_taps",
+    "gr4pm_fft_filter_sizes", "gr4pm_fft_filter_pending", "gr4pm_fft_filter_output_items", "gr4pm_fft_filter_process",
+    "gr4pm_fft_filter_process_iq", "gr4pm_fft_filter_flush", "gr4pm_band_filter_taps",
 ]
 
 _lib = None
@@ -721,6 +728,18 @@ def lib():
     L.gr4pm_fft_duc_mixed_pending.argtypes = [vp, szp]
     L.gr4pm_fft_duc_mixed_process.argtypes = [vp, vp, sz, sz, vp, sz, szp]
     L.gr4pm_fft_duc_mixed_process_iq.argtypes = [vp, vp, sz, sz, vp, C.c_int, C.c_float, sz, szp, vp]
+    L.gr4pm_fft_filter_create.argtypes = [C.POINTER(FftFilterParams), C.POINTER(vp)]
+    L.gr4pm_fft_filter_destroy.argtypes = [vp]
+    L.gr4pm_fft_filter_destroy.restype = None
+    L.gr4pm_fft_filter_reset.argtypes = [vp]
+    L.gr4pm_fft_filter_set_taps.argtypes = [vp, vp, sz]
+    L.gr4pm_fft_filter_sizes.argtypes = [vp, szp, szp, szp]
+    L.gr4pm_fft_filter_pending.argtypes = [vp, szp]
+    L.gr4pm_fft_filter_output_items.argtypes = [vp, sz, szp]
+    L.gr4pm_fft_filter_process.argtypes = [vp, vp, sz, vp, sz, szp]
+    L.gr4pm_fft_filter_process_iq.argtypes = [vp, vp, C.c_int, C.c_float, sz, vp, sz, szp]
+    L.gr4pm_fft_filter_flush.argtypes = [vp, vp, sz, szp]
+    L.gr4pm_band_filter_taps.argtypes = [vp, sz, C.c_int, sz, C.c_double, vp]
     L.gr4pm_duc_taps.argtypes = [sz, sz, C.c_double, C.c_double, vp]
     L.gr4pm_duc_create.argtypes = [C.POINTER(DucParams), C.POINTER(vp)]
     L.gr4pm_duc_destroy.argtypes = [vp]

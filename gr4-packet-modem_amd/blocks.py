@@ -2836,6 +2836,129 @@ class Spectrum:
         _destroy(self, "gr4pm_spectrum_destroy")
 
 
+BAND_MODES = {"stop": 0, "pass": 1}
+
+
+def band_filter_taps(bands, mode="stop", n_taps=1025, attenuation_db=60.0):
+    """gr4pm_band_filter_taps: complex64 taps that stop or pass the given bands of a complex stream (host only: works
+    without a GPU).  bands: (centre, width) pairs in cycles per sample; a band may wrap across +-0.5, and bands that
+    overlap or touch are merged on the circle.  n_taps odd: a Kaiser-windowed design (beta from attenuation_db) that delays
+    by (n_taps - 1) / 2 samples, with a transition width of (attenuation_db - 7.95) / (14.36 (n_taps - 1))."""
+    if mode not in BAND_MODES:
+        raise Gr4pmError(f"band_filter_taps: mode is {mode!r}, not 'stop' or 'pass'")
+    b = np.ascontiguousarray(np.asarray(bands, dtype=np.float64).reshape(-1, 2))
+    n = int(n_taps)
+    if not 0 <= n < 1 << 24:
+        raise Gr4pmError("band_filter_taps: n_taps out of range")
+    out = np.zeros(max(n, 1), dtype=np.complex64)
+    check(lib().gr4pm_band_filter_taps(_np_ptr(b) if b.size else None, b.shape[0], BAND_MODES[mode], n, float(attenuation_db),
+                                       _np_ptr(out)), "band_filter_taps")
+    return out[:n]
+
+
+def notch_taps(carriers, widen=1.5, min_width=None, **kw):
+    """band_filter_taps() for find_carriers()' records: one band per carrier at its `frequency`, `bandwidth` * widen wide and
+    not below min_width (None: the design's transition width, (attenuation_db - 7.95) / (14.36 (n_taps - 1))).  kw:
+    band_filter_taps' mode, n_taps, attenuation_db."""
+    n_taps, a = int(kw.get("n_taps", 1025)), float(kw.get("attenuation_db", 60.0))
+    if min_width is None:
+        min_width = (a - 7.95) / (14.36 * max(n_taps - 1, 1))
+    carriers = np.atleast_1d(carriers)
+    bands = [(float(c["frequency"]), max(float(c["bandwidth"]) * float(widen), float(min_width))) for c in carriers]
+    return band_filter_taps(bands, **kw)
+
+
+class FftFilter:
+    """gr4pm_fft_filter: any complex FIR of up to 1985 taps on one wideband stream, by fast convolution on the device
+    (DESIGN section 32): out[n] = sum_t taps[t] x[n - t], output sample n beside input sample n, x[i] = 0 before the
+    stream.  Segments of 2048 samples that overlap by `overlap` (len(taps) - 1 <= overlap <= 1984; None: len(taps) - 1
+    rounded up to a multiple of 256) are transformed, multiplied by the taps' response and transformed back; .hop = 2048 -
+    overlap samples of each are kept.  process_bulk() takes any number of samples and delivers whole segments; the rest
+    stays on the device (.pending samples), and any cutting of the stream into calls gives the same bits.  flush() brings
+    out what is still owed.  The handle works on the stream that is current when it is made."""
+
+    def __init__(self, taps, overlap=None):
+        self.taps = self._taps(taps)
+        if overlap is not None and not 0 <= int(overlap) < 1 << 62:
+            raise Gr4pmError("FftFilter: overlap must not be negative")
+        if overlap is not None and int(overlap) == 0 and self.taps.size > 1:
+            raise Gr4pmError(f"FftFilter: overlap 0 is below len(taps) - 1 = {self.taps.size - 1}")
+        stream = _stream_handle()
+        self._stream = stream.value
+        self._h = C.c_void_p()
+        p = _abi.FftFilterParams(_np_ptr(self.taps) if self.taps.size else None, self.taps.size,
+                                 0 if overlap is None else int(overlap), stream)
+        check(lib().gr4pm_fft_filter_create(C.byref(p), C.byref(self._h)), "FftFilter")
+        v, hop, n = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(lib().gr4pm_fft_filter_sizes(self._h, C.byref(v), C.byref(hop), C.byref(n)), "FftFilter.sizes")
+        self.overlap, self.hop = v.value, hop.value
+
+    @staticmethod
+    def _taps(taps):
+        return np.ascontiguousarray(np.asarray(taps, dtype=np.complex64).reshape(-1))
+
+    @property
+    def pending(self):
+        """samples taken whose outputs are still owed"""
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_filter_pending(self._h, C.byref(n)), "FftFilter.pending")
+        return n.value
+
+    def output_items(self, n):
+        """samples the next process_bulk() of n samples delivers: whole segments of .hop samples, so the count depends on
+        where the handle stands in its stream (the state is unchanged by asking)"""
+        out = C.c_size_t(0)
+        check(lib().gr4pm_fft_filter_output_items(self._h, int(n), C.byref(out)), "FftFilter.output_items")
+        return out.value
+
+    def reset(self):
+        """back to the fresh stream: zero prehistory, nothing pending"""
+        check(lib().gr4pm_fft_filter_reset(self._h), "FftFilter.reset")
+
+    def set_taps(self, taps):
+        """other taps from the next segment delivered on (len(taps) - 1 <= .overlap); the carried samples stay"""
+        taps = self._taps(taps)
+        check(lib().gr4pm_fft_filter_set_taps(self._h, _np_ptr(taps) if taps.size else None, taps.size), "FftFilter.set_taps")
+        self.taps = taps
+
+    def _out(self, out, samples, device):
+        torch = _torch()
+        if out is None:
+            return torch.empty(samples, dtype=torch.complex64, device=device)
+        out = _dev_c64(out, "out")
+        if out.dim() != 1:
+            raise TypeError("out must be one-dimensional")
+        return out
+
+    def process_bulk(self, x, scale=None, out=None):
+        """x: a contiguous CUDA complex64 tensor of any length, or integer IQ: an int16 (sc16), int8 (sc8) or uint8 (cu8)
+        CUDA tensor [n, 2], converted as iq_unpack(x, scale) does where the kernel loads it (the same result bit for bit;
+        calls of any format mix on one handle).  Returns the output_items(n) filtered samples, complex64; out: an optional
+        contiguous CUDA complex64 tensor with room for them to write into."""
+        x, n_in, fmt, scale = _stream_input(x, scale, self._stream)
+        out = self._out(out, self.output_items(n_in), x.device)
+        n = C.c_size_t(0)
+        if fmt is None:
+            check(lib().gr4pm_fft_filter_process(self._h, x.data_ptr(), n_in, out.data_ptr(), out.numel(), C.byref(n)),
+                  "FftFilter.process")
+        else:
+            check(lib().gr4pm_fft_filter_process_iq(self._h, x.data_ptr(), fmt, scale, n_in, out.data_ptr(), out.numel(),
+                                                    C.byref(n)), "FftFilter.process_iq")
+        self._last = x  # the call does not wait: the input lives until the next call
+        return out[: n.value]
+
+    def flush(self, out=None):
+        """the .pending samples still owed (the last segment run over zeros); leaves the handle as reset() does, so the
+        samples out equal the samples in"""
+        out = self._out(out, self.pending, "cuda")
+        n = C.c_size_t(0)
+        check(lib().gr4pm_fft_filter_flush(self._h, out.data_ptr(), out.numel(), C.byref(n)), "FftFilter.flush")
+        return out[: n.value]
+
+    def __del__(self):
+        _destroy(self, "gr4pm_fft_filter_destroy")
+
+
 def find_bursts(power, threshold_db=6.0, max_gap_rows=1, min_rows=2, floor=None, cap=None):
     """gr4pm_find_bursts: the bursts in a band's power over time, rows in time order (host only: works without a GPU).
     floor: the noise level of a row (None: the lower median of the rows, which holds while the band is silent in more

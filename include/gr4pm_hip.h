@@ -2065,6 +2065,66 @@ gr4pm_status gr4pm_fft_duc_mixed_process(gr4pm_fft_duc_mixed* h, const gr4pm_c64
 gr4pm_status gr4pm_fft_duc_mixed_process_iq(gr4pm_fft_duc_mixed* h, const gr4pm_c64* in, size_t in_stride, size_t slots, void* out,
                                             int format, float gain, size_t out_cap, size_t* n_out, unsigned long long* clipped);
 
+/* ---- FftFilter: any complex FIR on one wideband stream by fast convolution (the project's own block; DESIGN.md section
+ * 32) ----
+ * The same stream back with something removed: a CW interferer inside a channel, the DC spike of a recording, a strong
+ * neighbour.  N = 2048, complex finite taps h[0 .. L - 1] with 1 <= L <= N - 63, an overlap V with L - 1 <= V <= N - 64 (any
+ * integer; overlap 0: L - 1 rounded up to a multiple of 256, at most N - 64), hop = N - V.  x[i] = 0 for i < 0.
+ *     segment s: the N items from s hop - V;   X_s = FFT_N(x_s)
+ *     G[k] = (1 / N) sum_t h[t] exp(-2 pi j k t / N)   (host, double, each component rounded to float once)
+ *     y_s = N IFFT_N(X_s G);   p = V .. N - 1 are kept:   out[s hop + p - V] = y_s[p]
+ * So out[n] = sum_t h[t] x[n - t] in exact arithmetic: the causal filter, output sample n beside input sample n.  Segment s
+ * is complete after (s + 1) hop samples; a call of n_in samples delivers whole segments, ((pending + n_in) / hop) hop
+ * samples, the handle carries V + pending < N items, and any cutting of the stream into calls gives the same bits. */
+typedef struct gr4pm_fft_filter gr4pm_fft_filter;
+typedef struct {
+    const gr4pm_c64* taps; /* HOST, n_taps items, finite */
+    size_t n_taps;         /* L: 1 .. 1985 */
+    size_t overlap;        /* V; 0: the default */
+    void* stream;          /* hipStream_t */
+} gr4pm_fft_filter_params;
+/* Refused with GR4PM_ERR_INVALID and no handle: no taps, more than N - 63, a non-finite tap, V below L - 1 or above N - 64. */
+gr4pm_status gr4pm_fft_filter_create(const gr4pm_fft_filter_params* params, gr4pm_fft_filter** out);
+void gr4pm_fft_filter_destroy(gr4pm_fft_filter* h);
+/* the fresh stream: zero prehistory, nothing pending */
+gr4pm_status gr4pm_fft_filter_reset(gr4pm_fft_filter* h);
+/* Other taps from the next segment delivered on; V, hop and the carried samples stay.  Refused with GR4PM_ERR_INVALID and the
+ * handle unchanged: no taps, a non-finite tap, n_taps - 1 > V.  Waits for the handle's stream. */
+gr4pm_status gr4pm_fft_filter_set_taps(gr4pm_fft_filter* h, const gr4pm_c64* taps, size_t n_taps);
+gr4pm_status gr4pm_fft_filter_sizes(const gr4pm_fft_filter* h, size_t* overlap, size_t* hop, size_t* n_taps);
+/* samples taken whose outputs are still owed: taken mod hop */
+gr4pm_status gr4pm_fft_filter_pending(const gr4pm_fft_filter* h, size_t* samples);
+/* samples the next call of n_in samples delivers */
+gr4pm_status gr4pm_fft_filter_output_items(const gr4pm_fft_filter* h, size_t n_in, size_t* n_out);
+/* in: DEVICE, n_in samples.  out: DEVICE, room for out_cap samples.  Enqueues on the handle's stream, reads nothing back
+ * and does not wait.  Refused with gr4pm_last_error set, *n_out = 0, nothing enqueued and the handle unchanged: a NULL in
+ * with n_in > 0, a NULL out when the call delivers samples (GR4PM_ERR_INVALID); n_in > 2^40 or fewer than the samples of
+ * room (GR4PM_ERR_OVERFLOW). */
+gr4pm_status gr4pm_fft_filter_process(gr4pm_fft_filter* h, const gr4pm_c64* in, size_t n_in, gr4pm_c64* out, size_t out_cap,
+                                      size_t* n_out);
+/* The same for integer IQ in (GR4PM_IQ_SC16 / SC8 / CU8; scale 0: the format's default), gr4pm_ddc_process_iq's contract
+ * for the input side: gr4pm_fft_filter_process on gr4pm_iq_unpack(in) bit for bit; calls of any format mix on one handle.
+ * An unknown format is refused with GR4PM_ERR_INVALID before anything is enqueued. */
+gr4pm_status gr4pm_fft_filter_process_iq(gr4pm_fft_filter* h, const void* in, int format, float scale, size_t n_in, gr4pm_c64* out,
+                                         size_t out_cap, size_t* n_out);
+/* The `pending` samples still owed: the last segment run over zeros, its first `pending` kept samples to out.  Leaves the
+ * handle as gr4pm_fft_filter_reset does, so the samples out equal the samples in.  Refused with the handle unchanged: fewer
+ * than `pending` samples of room (GR4PM_ERR_OVERFLOW), a NULL out with samples owed (GR4PM_ERR_INVALID). */
+gr4pm_status gr4pm_fft_filter_flush(gr4pm_fft_filter* h, gr4pm_c64* out, size_t out_cap, size_t* n_out);
+
+/* Host only: complex taps that stop (GR4PM_BAND_STOP) or pass (GR4PM_BAND_PASS) the given bands.  bands: n_bands pairs
+ * (centre, width) in cycles per sample; a band may wrap across +-0.5; bands that overlap or touch are merged on the circle.
+ * n_taps odd, c = (n_taps - 1) / 2; Kaiser window w with beta from attenuation_db = A (A > 50: 0.1102 (A - 8.7); A >= 21:
+ * 0.5842 (A - 21)^0.4 + 0.07886 (A - 21); else 0); per merged band [f_lo, f_hi]
+ *     g_b(m) = (e^{2 pi j f_hi m} - e^{2 pi j f_lo m}) / (2 pi j m),   g_b(0) = f_hi - f_lo
+ *     pass: h[t] = w[t] sum_b g_b(t - c);   stop: h[t] = w[t] (delta[t - c] - sum_b g_b(t - c))
+ * in double, each component rounded to float once.  The filter delays by c samples; its transition width is
+ * (A - 7.95) / (14.36 (n_taps - 1)) cycles per sample.  Refused with GR4PM_ERR_INVALID and a text: a NaN or infinite
+ * input, a width <= 0 or >= 1, an even n_taps or n_taps < 3, A <= 8, bands that merge to the whole circle, an unknown mode. */
+enum { GR4PM_BAND_STOP = 0, GR4PM_BAND_PASS = 1 };
+gr4pm_status gr4pm_band_filter_taps(const double* bands, size_t n_bands, int mode, size_t n_taps, double attenuation_db,
+                                    gr4pm_c64* taps_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,9 @@ BUDGETS = [
     (r"k_row_gate_power", dict(vgpr=64, lds=0, lds_exact=True, scratch=0)),
     (r"k_row_gate_gather", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
     (r"k_row_gate_keep", dict(vgpr=32, lds=0, lds_exact=True, scratch=0)),
+    # the FftFilter block: k_fft_duc_inverse's LDS image, two transforms and one product per segment, two waves per SIMD
+    # 
+    (r"k_fft_filterILi", dict(vgpr=256, lds=151552, lds_exact=True, scratch=0)),
 ]
 
 
